@@ -12,13 +12,28 @@ Configs (BASELINE.json):
   c2            640x480, 1000 features, B = 256 per GPU, weak scaling
   c5            BASELINE config 5: ONE 8-frame batch of 1280x720 @ 4000 features per step, sharded over the
                 N GPUs (8/N frames each), strong scaling
-  c4 is a leg of every run (`c4_frame`): left / right / bird 1280x720 streams, each on its own GPU when
+  c4 is a leg of every `--full` run (`c4_frame`): left / right / bird 1280x720 streams, each on its own GPU when
   the process sees >= 3 devices (stereo pyramid + descriptors moved over xGMI), else all on one.
 
 Multi-GPU: `python bench.py --gpus N` spawns N ranks itself (before any GPU call) when WORLD_SIZE is
 unset; under torch.distributed.run the ranks come from the environment and must number --gpus.
 
-Also on the same line:
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline value needs: set
+up, warm up, time the K steps, write the outputs if `--dump-outputs DIR` is given, print the line (every
+other leg's entry is null).  `ms_per_step` on the line is the wall time of one timed step.
+
+`--dump-outputs DIR` writes what the last timed step produced, as a caller of the batch path reads it back
+(BatchExtractor.counts / results), into DIR as float32 .npy files, at most 64 MB in all:
+  counts.npy       (B,)    keypoints of every frame of the batch
+  frames.npy       (F,)    the frames whose keypoints and descriptors follow: all B when they fit, else a
+                           fixed seeded sample of them, ascending
+  keypoints.npy    (n, 7)  x, y, size, angle, response, octave, class_id of those frames' keypoints, frame
+                           after frame in the extractor's order
+  descriptors.npy  (n, 32) their descriptor bytes
+The frames are seeded synthetic ones and the extraction is deterministic, so two builds run with the same
+arguments are comparable array for array.  Rank 0 writes (its own frames).
+
+`--full` adds every other leg to the same line:
   roofline      dominant kernel's algorithmic bytes per launch / its HIP-event-timed duration (events on
                 liborbgpu's own stream, a separate pass of the same steps); PMC traffic from profiles/
   cpu_baseline  the oracle restatement of ORBextractor (oracle/, kind "port") rebuilt -march=native on
@@ -28,7 +43,8 @@ Also on the same line:
                 brute-force SearchByBoW inner loop), matches/s = distance evaluations per second, its FP4
                 MFMA fraction, and the restated CPU loops beside it
 
-Usage: python bench.py [--gpus N --steps K --warmup W --batch B --config c3|c2|c5 --no-cpu --only-extract]
+Usage: python bench.py [--gpus N --steps K --warmup W --batch B --config c3|c2|c5 --dump-outputs DIR]
+       python bench.py --full [... --no-cpu --only-extract]
 """
 import argparse
 import json
@@ -372,6 +388,34 @@ def c4_leg(cfg, frames, first, dist, rank, world, local):
                     "another GPU) and bird(t) x bird(t-1) Hamming top-2; synchronous per tracking frame"}
 
 
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # all files of one dump together
+DUMP_SEED = 20240607                # of the frame sample, when the whole batch does not fit
+
+
+def dump_outputs(path, e):
+    """The results of extractor context `e`'s last launch as float32 .npy files under `path` (layout: the
+    module docstring): counts of every frame; keypoints and descriptors of all frames, or of the longest prefix
+    of a seeded permutation of them that keeps the dump within DUMP_MAX_BYTES, in ascending frame order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    counts = e.counts()
+    B = len(counts)
+    per_kp = 4 * (7 + 32)                            # float32: 7 KeyPoint fields + 32 descriptor bytes
+    budget = DUMP_MAX_BYTES - 2 * 4 * B - 4 * 256    # less counts.npy, frames.npy and four .npy headers
+    order = np.random.RandomState(DUMP_SEED).permutation(B)
+    fits = int(np.searchsorted(np.cumsum(counts[order].astype(np.int64) * per_kp), budget, side="right"))
+    sel = np.arange(B) if fits >= B else np.sort(order[:fits])
+    kps, desc = [np.zeros((0, 7), np.float32)], [np.zeros((0, 32), np.float32)]
+    for f in sel:
+        k, d = e.results(int(f))
+        kps.append(np.stack([k[n].astype(np.float32) for n in k.dtype.names], axis=1))
+        desc.append(d.astype(np.float32))
+    for name, a in (("counts", counts), ("frames", sel), ("keypoints", np.concatenate(kps)),
+                    ("descriptors", np.concatenate(desc))):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 # ---------------------------------------------------------------- main
 def matcher_leg(img, w, h, nf, device):
     """Per-call latency of SearchByBoW (KF,F) / (KF,KF), SearchForTriangulation, SearchForInitialization
@@ -421,6 +465,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=0, help="frames per step per GPU (default: the config's)")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other leg too (per-kernel pass and roofline, Hamming, stereo, "
+                         "host path, matcher, birdview, C4, CPU baselines); the --no-* switches below trim that run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-hamming", action="store_true")
     ap.add_argument("--no-stereo", action="store_true")
@@ -430,7 +479,8 @@ def main():
     ap.add_argument("--no-profile-pass", action="store_true",
                     help="skip the per-kernel HIP-event pass (a rocprofv3 trace then holds only the timed launches)")
     ap.add_argument("--no-matcher", action="store_true", help="skip the per-call ORBmatcher / ComputeBoW leg")
-    ap.add_argument("--only-extract", action="store_true", help="the extraction steps only (no other leg)")
+    ap.add_argument("--only-extract", action="store_true",
+                    help="with --full: the extraction steps and their per-kernel pass only (no other leg)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher plumbing only (tests/test_dist_cpu.py): ranks, rendezvous, reductions, the rank-0 "
                          "line; no GPU is touched")
@@ -441,6 +491,8 @@ def main():
     args = ap.parse_args()
     if args.pipelines <= 0:
         args.pipelines = CONFIGS[args.config].get("pipelines", 2)
+    if not args.full:   # a plain run: the timed steps and the line, nothing measured beside them
+        args.only_extract = args.no_profile_pass = True
     if args.only_extract:
         args.no_cpu = args.no_hamming = args.no_stereo = args.no_host_path = args.no_bird = args.no_c4 = True
         args.no_matcher = True
@@ -525,6 +577,9 @@ def main():
                           "frames_per_step": B, "first_frame": first, "keypoints_per_step": kps_per_step,
                           "seconds": round(local_time, 6)})
 
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, exs[(args.steps - 1) % len(exs)])   # the context of the last timed step
+
     # per-kernel breakdown (HIP events on the library's stream) from a separate pass of the same steps
     kms = None
     if not args.no_profile_pass:
@@ -587,13 +642,13 @@ def main():
 
     # ---- roofline of the dominant kernel (per-step algorithmic bytes / per-step kernel time)
     per_frame_kps = kps_per_step / B
-    cands_per_frame = 0   # FAST survivors of frame 0 (all levels), from the debug view of the last batch
-    for l in range(8):
-        n = orbgpu._lib.lib().orb_debug_candidates(ex.h, 0, l, None, 0)
-        cands_per_frame += (-n - 1) if n < 0 else n
-    ab = algorithmic_bytes(w, h, per_frame_kps, cands_per_frame)
     roofline, ms_per_step_k = None, None
     if kms is not None:
+        cands_per_frame = 0   # FAST survivors of frame 0 (all levels), from the debug view of the last batch
+        for l in range(8):
+            n = orbgpu._lib.lib().orb_debug_candidates(ex.h, 0, l, None, 0)
+            cands_per_frame += (-n - 1) if n < 0 else n
+        ab = algorithmic_bytes(w, h, per_frame_kps, cands_per_frame)
         steps = args.steps
         # (a small batch runs as one dataflow launch, ORB_K_FLOW: then that is the only extraction kernel)
         ms_per_step_k = {KNAMES[i]: kms[i] / steps for i in (0, 1, 2, 3, 6) if klaunch[i] > 0}

@@ -55,14 +55,14 @@ for s in "$@"; do
       run smoke 120 python -c "import __graft_entry__ as g; g.smoke()"; tail -2 $OUT/${n}_smoke.log | head -1 ;;
     bench|bench=*)
       a=${s#bench}; a=${a#=}
-      run bench 600 python bench.py $a; summ $OUT/${n}_bench.log ;;
+      run bench 600 python bench.py --full $a; summ $OUT/${n}_bench.log ;;
     ab=*)
       spec=${s#ab=}; libs=${spec%%@*}; a=""; [[ "$spec" == *@* ]] && a=${spec#*@}
       IFS=',' read -ra LS <<< "$libs"
       for rep in 1 2; do
         for lib in "${LS[@]}"; do
           if [ "$lib" = tree ]; then unset ORBGPU_LIB_PATH; else export ORBGPU_LIB_PATH=$PWD/$lib; fi
-          run ab 300 python bench.py $a; echo -n "  [$lib] "; summ $OUT/${n}_ab.log
+          run ab 300 python bench.py --full $a; echo -n "  [$lib] "; summ $OUT/${n}_ab.log
         done
       done
       unset ORBGPU_LIB_PATH ;;
