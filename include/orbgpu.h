@@ -358,6 +358,53 @@ int orb_window_match_grid(orb_ctx* ctx, float nnratio, int check_ori, int level0
                           float window, int n2, const uint8_t* desc2, const orb_keypoint* kps2,
                           orb_frame_grid grid2, int* match12, int* nmatches);
 
+/* The projection-gated searches of the tracking thread, one generic core: each query (a projected map point) has
+ * a descriptor (qdesc, 32 B each), a window centre (u, v) and final radius r in the train frame, the
+ * GetFeaturesInArea level arguments with the reference's semantics (Frame.cc:515-527: levels are checked when
+ * min_level > 0 || max_level >= 0; then octave < min_level is skipped, and octave > max_level when max_level >= 0),
+ * and the stereo values.  Trains are the Frame's features: tdesc, kps_t (mvKeysUn / mvKeysBird), t_uright
+ * (mvuRight; NULL = mono / birdview: no stereo gate), t_taken[t] != 0 <=> mvpMapPoints[t] && Observations() > 0
+ * (NULL = none), and the Frame's grid (orb_frame_grid; the birdview grid for the birdview form).  Candidates =
+ * GetFeaturesInArea(u, v, r, min_level, max_level) computed on the GPU, minus taken trains, minus trains with
+ * uright > 0 && fabsf(ur - uright) > ur_tol (ORBmatcher.cc:91-96, :1407-1413).  The acceptance runs in query order:
+ * a train assigned to a query with blocks != 0 is taken for the queries after it; one assigned to a query with
+ * blocks == 0 (a MapPoint without observations, e.g. the temporal points of Tracking::UpdateLastFrame) may be
+ * assigned again, and *nmatches counts both assignments as the reference does.
+ *   ORB_PROJ_BEST (:1397-1442): the smallest distance (first on ties) is accepted when <= max_dist; with check_ori
+ *     the rotation histogram over q.angle - kps_t[best].angle and the ComputeThreeMaxima cull (:1448-1467).
+ *   ORB_PROJ_RATIO_SAME_LEVEL (:76-125, :1952-1994): best and second best with their octaves; accepted when
+ *     best <= max_dist unless bestLevel == bestLevel2 && best > nnratio * best2.  check_ori is not read.
+ * match_t[t] (nt ints) = the last query assigned to train t, -1 = untouched, -2 = reset to NULL by the rotation
+ * cull; *nmatches = the reference function's return value.  How the reference calls map onto it (points the
+ * reference skips before its search are left out by the caller: outliers, !mbTrackInView, isBad, invzc < 0,
+ * projections out of bounds, mnLastFrameSeen == F.mnId, |z| > 0.2):
+ *   SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)   ORBmatcher.cc:1328-1470
+ *     (u, v) the projection (:1370-1371), r = th * mvScaleFactors[octave] (:1381); levels (octave, -1) if bForward,
+ *     (0, octave) if bBackward, else (octave - 1, octave + 1) (:1385-1390); ur = u - mbf * invzc, ur_tol = r;
+ *     angle = LastFrame.mvKeysUn[i].angle; blocks = pMP->Observations() > 0; mode BEST, max_dist TH_HIGH.
+ *   SearchByProjection(Frame& F, const vector<MapPoint*>&, th)                   ORBmatcher.cc:45-129
+ *     (u, v) = (mTrackProjX, mTrackProjY), r = RadiusByViewingCos(mTrackViewCos) [* th if th != 1] *
+ *     mvScaleFactors[mnTrackScaleLevel] (:63-69); levels (level - 1, level); ur = mTrackProjXR, ur_tol = r;
+ *     blocks = 1; mode RATIO_SAME_LEVEL, max_dist TH_HIGH.
+ *   SearchByProjectionBird(Frame& F, const vector<MapPointBird*>&, r)            ORBmatcher.cc:1923-1998
+ *     (u, v) = pt (:1940), the given r; levels (-1, -1); t_uright NULL; blocks = 1; mode RATIO_SAME_LEVEL,
+ *     max_dist TH_HIGH; kps_t = mvKeysBird, tdesc = mDescriptorsBird, t_taken from mvpMapPointsBird, the birdview grid.
+ * ORB_ERR_ARG before any GPU work: an unknown mode, a u, v or r that is not finite, r < 0, max_dist outside
+ * [0, 256], a grid CSR orb_window_match_grid would refuse.  nq == 0 or nt == 0: ORB_OK, *nmatches = 0, match_t all
+ * -1, no GPU work. */
+enum { ORB_PROJ_BEST = 0, ORB_PROJ_RATIO_SAME_LEVEL = 1 };
+typedef struct orb_proj_query {
+    float u, v, r;              /* window centre and final radius (th * scale already applied) */
+    int   min_level, max_level; /* GetFeaturesInArea's arguments, reference semantics */
+    float ur, ur_tol;           /* projected right coordinate and its tolerance */
+    float angle;                /* query keypoint angle (BEST + check_ori) */
+    int   blocks;               /* the query's MapPoint has Observations() > 0 */
+} orb_proj_query;
+int orb_search_by_projection(orb_ctx* ctx, int mode, float nnratio, int check_ori, int max_dist,
+                             int nq, const orb_proj_query* q, const uint8_t* qdesc,
+                             int nt, const uint8_t* tdesc, const orb_keypoint* kps_t, const float* t_uright,
+                             const uint8_t* t_taken, orb_frame_grid grid, int* match_t, int* nmatches);
+
 /* Frame::GetFeaturesInArea over the 64x48 Frame grid (Frame.cc:378-412, 494-560): host helper the
  * C++ mirror uses to build window candidate lists. Returns count or -(needed)-1. */
 int orb_features_in_area(int n, const orb_keypoint* kps_un, float min_x, float max_x, float min_y, float max_y,

@@ -1,6 +1,7 @@
 // gfx950 Hamming-distance kernels for ORBmatcher's vocabulary-gated searches (ORBmatcher.cc): the 256-bit
 // distance (DescriptorDistance, ORBmatcher.cc:1647-1663) as 8 x (v_xor_b32 + v_bcnt_u32_b32) per pair on the VALU,
-// over CSR candidate lists (k_topk), the Frame grid's windows (k_window_topk) and SearchForTriangulation's
+// over CSR candidate lists (k_topk), the Frame grid's windows (k_window_topk: one window size and the query's own
+// level; k_projection_topk: per-query centre, radius, level range and stereo gate) and SearchForTriangulation's
 // epipolar-gated candidates (k_triangulation).  The all-pairs top-2 on the matrix cores is hamming_top2.hip.
 // The selection logic that depends on the order of earlier accepted matches (SearchByBoW's taken set,
 // SearchForInitialization's vMatchedDistance) is replayed on the host from these exact top-k lists
@@ -184,6 +185,107 @@ __global__ __launch_bounds__(256) void k_window_topk(const uint8_t* __restrict__
     if (lane == 0 && out_nvalid) out_nvalid[qi] = nvalid;
 }
 
+// The projection-gated searches' candidates (SearchByProjection(Frame&, const Frame&) :1383-1413,
+// SearchByProjection(Frame&, vector<MapPoint*>) :68-96, SearchByProjectionBird :1945-1965):
+// Frame::GetFeaturesInArea(u, v, r, min_level, max_level) (Frame.cc:494-547) over the train frame's grid in its
+// CSR form, each query with its own centre, radius and level range, then the stereo gate on mvuRight.  As in
+// k_window_topk a candidate's CSR slot is its rank in vIndices, so (dist, slot) is the reference's first minimum.
+// A projection window holds a few to a few dozen candidates; a query gets W lanes: 64 (one wavefront, the form in
+// use) or 16 (one DPP row: four queries per wavefront, sixteen per block; the reductions stay below lane offset 16;
+// measured no faster, DESIGN 5.3, and kept for that A/B).
+// Rows of a wavefront whose query index is past nq stay in the kernel with an empty window, so every shuffle
+// runs with all of its row's lanes active.
+template <int W>
+__global__ __launch_bounds__(256) void k_projection_topk(const orb_proj_query* __restrict__ pq,
+                                                         const uint8_t* __restrict__ q, int nq,
+                                                         const uint8_t* __restrict__ t,
+                                                         const orb_keypoint* __restrict__ kps2,
+                                                         const float* __restrict__ uright,
+                                                         const int* __restrict__ cell_off,
+                                                         const int* __restrict__ cell_idx, ProjGrid g,
+                                                         const int* __restrict__ thr, int k,
+                                                         int* __restrict__ out_dist, int* __restrict__ out_idx,
+                                                         int* __restrict__ out_nvalid) {
+    constexpr int COLS = 64, ROWS = 48;   // Frame.h:39-40
+    static_assert(W == 16 || W == 64, "one DPP row or one wavefront per query");
+    const int qi = blockIdx.x * (256 / W) + (int)(threadIdx.x / W);
+    const int lane = threadIdx.x & (W - 1);
+    const bool live = qi < nq;
+    const int qc = live ? qi : nq - 1;   // (nq >= 1: the launcher returns before an empty launch)
+    const orb_proj_query P = pq[qc];
+    const uint4* qp = reinterpret_cast<const uint4*>(q + (long long)qc * 32);
+    const uint4 qa = qp[0], qb = qp[1];
+    const float x = P.u, y = P.v, r = P.r;
+    // cell rectangle, the reference's float expressions (-ffp-contract=off: no fused forms)
+    const int nMinCellX = max(0, (int)floorf((x - g.min_x - r) * g.inv_w));
+    const int nMaxCellX = min(COLS - 1, (int)ceilf((x - g.min_x + r) * g.inv_w));
+    const int nMinCellY = max(0, (int)floorf((y - g.min_y - r) * g.inv_h));
+    const int nMaxCellY = min(ROWS - 1, (int)ceilf((y - g.min_y + r) * g.inv_h));
+    const bool empty = !live || nMinCellX >= COLS || nMaxCellX < 0 || nMinCellY >= ROWS || nMaxCellY < 0;
+    const bool bCheckLevels = P.min_level > 0 || P.max_level >= 0;   // Frame.cc:515
+    unsigned long long lst[kMaxK];
+#pragma unroll
+    for (int j = 0; j < kMaxK; j++) lst[j] = ~0ull;
+    int nvalid = 0;
+    if (!empty) {
+        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
+            const int s0 = cell_off[ix * ROWS + nMinCellY], s1 = cell_off[ix * ROWS + nMaxCellY + 1];
+            for (int s = s0 + lane; s < s1; s += W) {
+                const int ti = cell_idx[s];
+                const orb_keypoint kp = kps2[ti];
+                if (bCheckLevels) {                                                   // :520-527
+                    if (kp.octave < P.min_level) continue;
+                    if (P.max_level >= 0 && kp.octave > P.max_level) continue;
+                }
+                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;          // :530-533
+                if (uright) {                                                         // ORBmatcher.cc:91-96, :1407-1413
+                    const float urt = uright[ti];
+                    if (urt > 0 && fabsf(P.ur - urt) > P.ur_tol) continue;
+                }
+                const uint4* tp = reinterpret_cast<const uint4*>(t + (long long)ti * 32);
+                const int d = hamming256(qa, qb, tp[0], tp[1]);
+                if (thr && thr[ti] <= d) continue;
+                nvalid++;
+                unsigned long long key = ((unsigned long long)d << 32) | (unsigned)s;
+#pragma unroll
+                for (int j = 0; j < kMaxK; j++) {   // sorted insert (compare-swap chain)
+                    if (j < k && key < lst[j]) {
+                        const unsigned long long tmp = lst[j];
+                        lst[j] = key;
+                        key = tmp;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) nvalid += __shfl_xor(nvalid, o);
+    int head = 0;
+    for (int j = 0; j < k; j++) {
+        unsigned long long mine = ~0ull;
+#pragma unroll
+        for (int s = 0; s < kMaxK; s++)
+            if (s == head) mine = lst[s];
+        unsigned long long m = mine;
+#pragma unroll
+        for (int o = W / 2; o > 0; o >>= 1) {
+            const unsigned long long w = __shfl_xor(m, o);
+            m = w < m ? w : m;
+        }
+        if (mine == m && m != ~0ull) head++;
+        if (lane == 0 && live) {
+            int dd = -1, ii = -1;
+            if (m != ~0ull) {
+                dd = (int)(m >> 32);
+                ii = cell_idx[(int)(m & 0xFFFFFFFFu)];
+            }
+            out_dist[(long long)qi * k + j] = dd;
+            out_idx[(long long)qi * k + j] = ii;
+        }
+    }
+    if (lane == 0 && live) out_nvalid[qi] = nvalid;
+}
+
 /* SearchForTriangulation inner loop (ORBmatcher.cc:712-761) for one (idx1, node) item per
  * wavefront: dist <= TH_LOW, epipole distance gate for mono pairs, CheckDistEpipolarLine
  * (:140-157, float with the final comparison in double).  The reference keeps the LAST candidate
@@ -240,6 +342,21 @@ hipError_t launch_window_topk(const uint8_t* d_q, const int* d_item_q, const flo
     if (k < 1 || k > kMaxK) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_window_topk, dim3((nitems + 3) / 4), dim3(256), 0, stream, d_q, d_item_q, d_centre, nitems,
                        d_kps1, d_t, d_kps2, d_cell_off, d_cell_idx, wg, d_thr, k, d_dist, d_idx, d_nvalid);
+    return hipGetLastError();
+}
+
+hipError_t launch_projection_topk(const orb_proj_query* d_pq, const uint8_t* d_q, int nq, const uint8_t* d_t,
+                                  const orb_keypoint* d_kps2, const float* d_uright, const int* d_cell_off,
+                                  const int* d_cell_idx, const ProjGrid& g, const int* d_thr, int k, int lanes,
+                                  int* d_dist, int* d_idx, int* d_nvalid, hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    if (k < 1 || k > kMaxK || (lanes != 16 && lanes != 64)) return hipErrorInvalidValue;
+    if (lanes == 16)
+        hipLaunchKernelGGL(k_projection_topk<16>, dim3((nq + 15) / 16), dim3(256), 0, stream, d_pq, d_q, nq, d_t, d_kps2,
+                           d_uright, d_cell_off, d_cell_idx, g, d_thr, k, d_dist, d_idx, d_nvalid);
+    else
+        hipLaunchKernelGGL(k_projection_topk<64>, dim3((nq + 3) / 4), dim3(256), 0, stream, d_pq, d_q, nq, d_t, d_kps2,
+                           d_uright, d_cell_off, d_cell_idx, g, d_thr, k, d_dist, d_idx, d_nvalid);
     return hipGetLastError();
 }
 

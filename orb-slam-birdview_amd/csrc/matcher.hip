@@ -8,7 +8,9 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "orbgpu_ctx.h"
@@ -193,6 +195,54 @@ struct TopkSession {
     }
     bool cen = false;
 
+    // Projection mode (orb_search_by_projection): item i = query i with its own window (orb_proj_query) in the
+    // train frame's grid; uright == NULL: no stereo gate.
+    bool proj = false, has_ur = false;
+    int lanes = 64;
+    ProjGrid pg{};
+    size_t o_pq = 0, o_ur = 0;
+    int setup_proj(int nq, const orb_proj_query* q, const uint8_t* qdesc, int ntrain, const uint8_t* tdesc,
+                   const orb_keypoint* kps_t, const float* uright, const orb_frame_grid& g, int nlanes) {
+        nitems = nq;
+        nt = ntrain;
+        if (nitems == 0) return ORB_OK;
+        proj = true;
+        has_ur = uright != nullptr;
+        lanes = nlanes;
+        pg = ProjGrid{g.min_x, g.min_y, g.inv_w, g.inv_h};
+        const int ncells = 64 * 48, nslots = g.cell_off[ncells];
+        st.c = c;
+        o_pq = st.add((size_t)nq * sizeof(orb_proj_query));
+        o_q = st.add((size_t)nq * 32);
+        o_t = st.add((size_t)nt * 32);
+        o_k2 = st.add((size_t)nt * sizeof(orb_keypoint));
+        o_ur = st.add(uright ? (size_t)nt * 4 : 0);
+        o_coff = st.add((size_t)(ncells + 1) * 4);
+        o_cidx = st.add((size_t)nslots * 4);
+        o_thr = st.add((size_t)nt * 4);
+        o_in_end = st.off;
+        o_dist = st.add((size_t)nitems * K * 4);
+        o_idx = st.add((size_t)nitems * K * 4);
+        o_nv = st.add((size_t)nitems * 4);
+        o_end = st.off;
+        const int rr = st.alloc();
+        if (rr != ORB_OK) return rr;
+        auto put = [&](size_t o, const void* src, size_t bytes) {
+            if (bytes) std::memcpy(st.hi<uint8_t>(o), src, bytes);
+        };
+        put(o_pq, q, (size_t)nq * sizeof(orb_proj_query));
+        put(o_q, qdesc, (size_t)nq * 32);
+        put(o_t, tdesc, (size_t)nt * 32);
+        put(o_k2, kps_t, (size_t)nt * sizeof(orb_keypoint));
+        if (uright) put(o_ur, uright, (size_t)nt * 4);
+        put(o_coff, g.cell_off, (size_t)(ncells + 1) * 4);
+        put(o_cidx, g.cell_idx, (size_t)nslots * 4);
+        dist = st.h<int>(o_dist);
+        idx = st.h<int>(o_idx);
+        nvalid = st.h<int>(o_nv);
+        return ORB_OK;
+    }
+
     // Rank items [from, to) (to < 0: nitems) with train thresholds thr (NULL = admit all).
     int run(int from, const int* thr, int to = -1) {
         const int n = (to < 0 ? nitems : to) - from;
@@ -204,7 +254,14 @@ struct TopkSession {
             return set_error("upload", e), ORB_ERR_HIP;
         uploaded = true;
         if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
-        if (grid)
+        if (proj)
+            e = launch_projection_topk(st.di<orb_proj_query>(o_pq) + from, st.di<uint8_t>(o_q) + (size_t)from * 32, n,
+                                       st.di<uint8_t>(o_t), st.di<orb_keypoint>(o_k2),
+                                       has_ur ? st.di<float>(o_ur) : nullptr, st.di<int>(o_coff), st.di<int>(o_cidx), pg,
+                                       thr ? st.di<int>(o_thr) : nullptr, K, lanes,
+                                       st.h<int>(o_dist) + (size_t)from * K, st.h<int>(o_idx) + (size_t)from * K,
+                                       st.h<int>(o_nv) + from, c->stream);
+        else if (grid)
             e = launch_window_topk(st.di<uint8_t>(o_q), st.di<int>(o_item) + from, cen ? st.di<float2>(o_cen) : nullptr, n,
                                    st.di<orb_keypoint>(o_k1), st.di<uint8_t>(o_t), st.di<orb_keypoint>(o_k2),
                                    st.di<int>(o_coff), st.di<int>(o_cidx), wg, thr ? st.di<int>(o_thr) : nullptr, K,
@@ -858,6 +915,18 @@ int orb_search_for_triangulation_batch(orb_ctx* h, int check_ori, int only_stere
 
 namespace orbgpu {
 namespace {
+// What is wrong with a Frame grid CSR (cell_off and, where it has slots, cell_idx not NULL), or NULL: the grid
+// kernels read cell_idx[cell_off[..]] for every rectangle column and index the trains by cell_idx, so a malformed
+// CSR would be an out-of-bounds device read.
+const char* grid_csr_fault(const orb_frame_grid& g, int nt) {
+    if (g.cell_off[0] != 0) return "grid cell_off[0] != 0";
+    for (int i = 0; i < 64 * 48; i++)   // offsets non-decreasing, so every run lies in [0, cell_off[3072])
+        if (g.cell_off[i + 1] < g.cell_off[i]) return "grid cell_off decreases";
+    for (int i = 0, nslots = g.cell_off[64 * 48]; i < nslots; i++)   // the device indexes the trains by these
+        if (g.cell_idx[i] < 0 || g.cell_idx[i] >= nt) return "grid index out of range";
+    return nullptr;
+}
+
 // The window searches' acceptance, replayed in the reference's query order (:440-498): first / second
 // admissible candidate, vMatchedDistance stealing, rotation histogram.
 int window_replay(TopkSession& s, float nnratio, int check_ori, int n1, const orb_keypoint* kps1, int n2,
@@ -889,6 +958,72 @@ int window_replay(TopkSession& s, float nnratio, int check_ori, int n1, const or
     }
     if (check_ori) cull_rotation(rotHist, vnMatches12, nmatches);
     std::memcpy(match12, vnMatches12.data(), (size_t)n1 * sizeof(int));
+    if (nmatches_out) *nmatches_out = nmatches;
+    return ORB_OK;
+}
+
+// The projection-gated searches' acceptance from the top-k lists, in query order.  A train is taken (skipped, as
+// `if(mvpMapPoints[i]) if(Observations()>0) continue;` does, :87-89 / :1403-1405 / :1963-1965) if the caller marked
+// it or an earlier query with blocks != 0 was assigned to it; an assignment by a query with blocks == 0 leaves it
+// open, and a later one overwrites it (both count).  A list the taken set exhausts while the window holds more
+// than K admissible candidates is re-ranked on the GPU from that query on, as bow_kf_f_replay does.
+int proj_replay(TopkSession& s, int mode, float nnratio, int check_ori, int max_dist, const orb_proj_query* q,
+                const orb_keypoint* kps_t, const uint8_t* t_taken, int* match_t, int* nmatches_out) {
+    const int nq = s.nitems, nt = s.nt;
+    std::vector<char> taken(nt, 0);
+    std::vector<int> thr(nt), matches(nt, -1);
+    std::vector<int> rotHist[HISTO_LENGTH];
+    auto fill_thr = [&]() {
+        for (int t = 0; t < nt; t++) thr[t] = taken[t] ? -1 : INT_MAX;
+    };
+    if (t_taken)
+        for (int t = 0; t < nt; t++) taken[t] = t_taken[t] != 0;
+    fill_thr();
+    int st = s.run(0, t_taken ? thr.data() : nullptr);
+    if (st != ORB_OK) return st;
+    const int need = mode == ORB_PROJ_BEST ? 1 : 2;
+    int d[2], ti[2], found = 0;
+    // the first `need` admissible entries of query i's list with a distance below 256 (the reference's running
+    // minima start at 256 and update on '<' only); false if the list cannot decide them
+    auto scan = [&](int i) {
+        found = 0;
+        for (int j = 0; j < K && found < need; j++) {
+            const int dj = s.dist[(size_t)i * K + j];
+            if (dj < 0 || dj >= 256) return true;   // the end of the list, or of its entries that can be a minimum
+            const int t = s.idx[(size_t)i * K + j];
+            if (taken[t]) continue;
+            d[found] = dj;
+            ti[found++] = t;
+        }
+        return found == need || s.nvalid[i] <= K;
+    };
+    int nmatches = 0;
+    for (int i = 0; i < nq; i++) {
+        if (!scan(i)) {
+            fill_thr();
+            if ((st = s.run(i, thr.data())) != ORB_OK) return st;
+            scan(i);
+        }
+        if (found == 0 || d[0] > max_dist) continue;   // :118 / :1426 / :1987
+        if (mode == ORB_PROJ_RATIO_SAME_LEVEL) {       // :120-121 / :1989-1990
+            const int bestLevel = kps_t[ti[0]].octave, bestLevel2 = found == 2 ? kps_t[ti[1]].octave : -1;
+            const int bestDist2 = found == 2 ? d[1] : 256;
+            if (bestLevel == bestLevel2 && static_cast<float>(d[0]) > nnratio * static_cast<float>(bestDist2)) continue;
+        }
+        matches[ti[0]] = i;
+        taken[ti[0]] = q[i].blocks != 0;
+        nmatches++;
+        if (mode == ORB_PROJ_BEST && check_ori) rotHist[rot_bin(q[i].angle, kps_t[ti[0]].angle)].push_back(ti[0]);
+    }
+    if (mode == ORB_PROJ_BEST && check_ori) {   // :1448-1467: every entry of a culled bin resets its train and decrements
+        int i1 = -1, i2 = -1, i3 = -1;          // (no guard: a train entered twice by overwriting queries counts twice)
+        three_maxima(rotHist, i1, i2, i3);
+        for (int b = 0; b < HISTO_LENGTH; b++) {
+            if (b == i1 || b == i2 || b == i3) continue;
+            for (int t : rotHist[b]) { matches[t] = -2; nmatches--; }
+        }
+    }
+    std::memcpy(match_t, matches.data(), (size_t)nt * sizeof(int));
     if (nmatches_out) *nmatches_out = nmatches;
     return ORB_OK;
 }
@@ -928,14 +1063,8 @@ int orb_window_match_grid(orb_ctx* h, float nnratio, int check_ori, int level0_o
     if (n1 < 0 || n2 < 0 || !match12 || (n1 && (!desc1 || !kps1)) || (n2 && (!desc2 || !kps2)) ||
         !grid2.cell_off || (grid2.cell_off[64 * 48] && !grid2.cell_idx))
         return set_error("orb_window_match_grid: bad arguments", hipSuccess), ORB_ERR_ARG;
-    if (grid2.cell_off[0] != 0)
-        return set_error("orb_window_match_grid: grid cell_off[0] != 0", hipSuccess), ORB_ERR_ARG;
-    for (int i = 0; i < 64 * 48; i++)   // offsets non-decreasing, so every run lies in [0, cell_off[3072])
-        if (grid2.cell_off[i + 1] < grid2.cell_off[i])
-            return set_error("orb_window_match_grid: grid cell_off decreases", hipSuccess), ORB_ERR_ARG;
-    for (int i = 0, nslots = grid2.cell_off[64 * 48]; i < nslots; i++)   // the device indexes kps2 by these
-        if (grid2.cell_idx[i] < 0 || grid2.cell_idx[i] >= n2)
-            return set_error("orb_window_match_grid: grid index out of range", hipSuccess), ORB_ERR_ARG;
+    if (const char* why = grid_csr_fault(grid2, n2))
+        return set_error((std::string("orb_window_match_grid: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     TopkSession s{c};
@@ -946,6 +1075,42 @@ int orb_window_match_grid(orb_ctx* h, float nnratio, int check_ori, int level0_o
     const int st = s.setup_grid(desc1, n1, kps1, centres, desc2, n2, kps2, grid2, window);
     if (st != ORB_OK) return st;
     return window_replay(s, nnratio, check_ori, n1, kps1, n2, kps2, match12, nmatches_out);
+}
+
+/* SearchByProjection(Frame&, const Frame&, th, bMono) (:1328-1470), SearchByProjection(Frame&, vector<MapPoint*>, th)
+ * (:45-129) and SearchByProjectionBird (:1923-1998) over one core (orbgpu.h has the mappings). */
+int orb_search_by_projection(orb_ctx* h, int mode, float nnratio, int check_ori, int max_dist, int nq,
+                             const orb_proj_query* q, const uint8_t* qdesc, int nt, const uint8_t* tdesc,
+                             const orb_keypoint* kps_t, const float* t_uright, const uint8_t* t_taken,
+                             orb_frame_grid grid, int* match_t, int* nmatches_out) {
+    // as in orb_window_match_grid the arguments are checked before the context: nothing malformed reaches the device
+    if (mode != ORB_PROJ_BEST && mode != ORB_PROJ_RATIO_SAME_LEVEL)
+        return set_error("orb_search_by_projection: unknown mode", hipSuccess), ORB_ERR_ARG;
+    if (max_dist < 0 || max_dist > 256)
+        return set_error("orb_search_by_projection: max_dist outside [0, 256]", hipSuccess), ORB_ERR_ARG;
+    if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q || !qdesc)) || (nt && (!tdesc || !kps_t)) ||
+        !grid.cell_off || (grid.cell_off[64 * 48] && !grid.cell_idx))
+        return set_error("orb_search_by_projection: bad arguments", hipSuccess), ORB_ERR_ARG;
+    for (int i = 0; i < nq; i++)
+        if (!std::isfinite(q[i].u) || !std::isfinite(q[i].v) || !std::isfinite(q[i].r) || q[i].r < 0)
+            return set_error("orb_search_by_projection: query window not finite or radius negative", hipSuccess),
+                   ORB_ERR_ARG;
+    if (const char* why = grid_csr_fault(grid, nt))
+        return set_error((std::string("orb_search_by_projection: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    CTX_GUARD(c);
+    for (int t = 0; t < nt; t++) match_t[t] = -1;
+    if (nmatches_out) *nmatches_out = 0;
+    if (nq == 0 || nt == 0) return ORB_OK;
+    // lanes per query: a wavefront per query measured 3-4 us per call faster than a query per 16-lane row at
+    // 640x480 / 1,000 queries and level with it at 1280x720 / 2,000, so it is the form in use;
+    // ORBGPU_PROJ_LANES=16 selects the row form (diagnostic: profiles/time_projection.py times both)
+    const char* e = getenv("ORBGPU_PROJ_LANES");
+    const int lanes = (e && atoi(e) == 16) ? 16 : 64;
+    TopkSession s{c};
+    const int st = s.setup_proj(nq, q, qdesc, nt, tdesc, kps_t, t_uright, grid, lanes);
+    if (st != ORB_OK) return st;
+    return proj_replay(s, mode, nnratio, check_ori, max_dist, q, kps_t, t_taken, match_t, nmatches_out);
 }
 
 /* Frame::GetFeaturesInArea over the Frame grid (Frame.cc:378-392, 494-560) */

@@ -287,6 +287,17 @@ hipError_t launch_window_topk(const uint8_t* d_q, const int* d_item_q, const flo
                               const int* d_cell_off, const int* d_cell_idx, const WinGrid& wg, const int* d_thr,
                               int k, int* d_dist, int* d_idx, int* d_nvalid, hipStream_t stream);
 
+// The projection-gated searches (orb_search_by_projection): per query its descriptor and its orb_proj_query (window
+// centre, radius, level range, stereo values); candidates = GetFeaturesInArea over the train frame's grid with the
+// stereo gate on d_uright (NULL: none).  lanes = 16 (a query per 16-lane row) or 64 (a query per wavefront).
+struct ProjGrid {
+    float min_x, min_y, inv_w, inv_h;
+};
+hipError_t launch_projection_topk(const orb_proj_query* d_pq, const uint8_t* d_q, int nq, const uint8_t* d_t,
+                                  const orb_keypoint* d_kps2, const float* d_uright, const int* d_cell_off,
+                                  const int* d_cell_idx, const ProjGrid& g, const int* d_thr, int k, int lanes,
+                                  int* d_dist, int* d_idx, int* d_nvalid, hipStream_t stream);
+
 // SearchForTriangulation's staged inputs, read by k_triangulation straight from the pinned mirror (over PCIe):
 // one record per query (item) holding everything its wave needs, and the candidate trains' records in
 // candidate order, so a wave's reads are two dependent round trips (its item record, then its candidates').

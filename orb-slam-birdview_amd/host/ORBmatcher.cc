@@ -160,6 +160,25 @@ std::vector<size_t> FrameGrid::GetFeaturesInArea(float x, float y, float r, int 
     return vIndices;
 }
 
+orb_frame_grid FrameGrid::Csr(std::vector<int>& off, std::vector<int>& idx) const {
+    const size_t ncells = (size_t)ORBGPU_FRAME_GRID_COLS * ORBGPU_FRAME_GRID_ROWS;
+    off.assign(ncells + 1, 0);
+    idx.clear();
+    for (size_t c = 0; c < ncells && !cells_.empty(); c++) {
+        for (size_t j = 0; j < cells_[c].size(); j++) idx.push_back((int)cells_[c][j]);
+        off[c + 1] = (int)idx.size();
+    }
+    if (idx.empty()) idx.push_back(0);
+    orb_frame_grid g;
+    g.min_x = minX_;
+    g.min_y = minY_;
+    g.inv_w = invW_;
+    g.inv_h = invH_;
+    g.cell_off = off.data();
+    g.cell_idx = idx.data();
+    return g;
+}
+
 /* ---------------- ORBmatcher ---------------- */
 ORBmatcher::ORBmatcher(float nnratio, bool checkOri) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
 
@@ -327,6 +346,111 @@ int ORBmatcher::BirdviewMatch(const FrameData& F1, const FrameData& F2, std::vec
 int ORBmatcher::BirdviewMatch(const FrameData& F1, const FrameData& F2, std::vector<int>& vnMatches12,
                               int windowSize) {
     return window_match(false, F1, F2, nullptr, windowSize, vnMatches12);
+}
+
+/* ---------------- projection-gated searches (orb_search_by_projection) ---------------- */
+int ORBmatcher::projection_search(int mode, const FeatureSet& F, bool stereo, const std::vector<orb_proj_query>& q,
+                                  const std::vector<uint8_t>& qdesc, std::vector<int>& matches, const char* what) {
+    const int n = F.N(), nq = (int)q.size();
+    matches.assign(n, -1);
+    require(F.grid != nullptr, "projection search: Frame grid");
+    require(n == 0 || (F.keys && F.descriptors), "projection search: Frame keys/descriptors");
+    std::vector<int> off, idx;
+    const orb_frame_grid g = F.grid->Csr(off, idx);
+    std::vector<int> out(std::max(n, 1), -1);
+    int nmatches = 0;
+    check(orb_search_by_projection(matcher_ctx(), mode, mfNNratio, mbCheckOrientation, TH_HIGH, nq, nq ? q.data() : nullptr,
+                                   nq ? qdesc.data() : nullptr, n, desc_ptr(F), keys_ptr(F), stereo ? F.uRight : nullptr,
+                                   F.hasMapPoint, g, out.data(), &nmatches),
+          what);
+    std::copy(out.begin(), out.begin() + n, matches.begin());
+    return nmatches;
+}
+
+int ORBmatcher::SearchByProjection(FrameData& CurrentFrame, const ProjectedLastFrame& LastFrame, const float th,
+                                   const bool bMono, std::vector<int>& vpMapPointMatches) {
+    const size_t nq = LastFrame.points.size();
+    require(nq == 0 || (CurrentFrame.scaleFactors && CurrentFrame.nlevels > 0), "SearchByProjection: scale table");
+    const bool bForward = LastFrame.bForward && !bMono, bBackward = LastFrame.bBackward && !bMono;   // :1348-1349
+    std::vector<orb_proj_query> q(nq);
+    std::vector<uint8_t> qdesc(nq * 32);
+    for (size_t i = 0; i < nq; i++) {
+        const ProjectedLastFrame::Point& p = LastFrame.points[i];
+        require(p.descriptor && p.octave >= 0 && p.octave < CurrentFrame.nlevels, "SearchByProjection: map point");
+        const float radius = th * CurrentFrame.scaleFactors[p.octave];   // :1381
+        q[i].u = p.u;
+        q[i].v = p.v;
+        q[i].r = radius;
+        if (bForward) {                                                  // :1385-1390
+            q[i].min_level = p.octave;
+            q[i].max_level = -1;
+        } else if (bBackward) {
+            q[i].min_level = 0;
+            q[i].max_level = p.octave;
+        } else {
+            q[i].min_level = p.octave - 1;
+            q[i].max_level = p.octave + 1;
+        }
+        const float disp = LastFrame.mbf * p.invzc;
+        q[i].ur = p.u - disp;                                            // :1409
+        q[i].ur_tol = radius;                                            // :1411
+        q[i].angle = p.angle;
+        q[i].blocks = p.observed ? 1 : 0;
+        memcpy(&qdesc[i * 32], p.descriptor, 32);
+    }
+    return projection_search(ORB_PROJ_BEST, CurrentFrame, CurrentFrame.uRight != nullptr, q, qdesc, vpMapPointMatches,
+                             "SearchByProjection(CurrentFrame, LastFrame)");
+}
+
+int ORBmatcher::SearchByProjection(FrameData& F, const ProjectedMapPoints& vpMapPoints, const float th,
+                                   std::vector<int>& vpMapPointMatches) {
+    const size_t nq = vpMapPoints.points.size();
+    require(nq == 0 || (F.scaleFactors && F.nlevels > 0), "SearchByProjection: scale table");
+    const bool bFactor = th != 1.0;                                      // :49
+    std::vector<orb_proj_query> q(nq);
+    std::vector<uint8_t> qdesc(nq * 32);
+    for (size_t i = 0; i < nq; i++) {
+        const ProjectedMapPoints::Point& p = vpMapPoints.points[i];
+        require(p.descriptor && p.level >= 0 && p.level < F.nlevels, "SearchByProjection: map point");
+        float r = p.viewCos > 0.998 ? 2.5f : 4.0f;                       // RadiusByViewingCos, :131-137
+        if (bFactor) r *= th;                                            // :65-66
+        const float rr = r * F.scaleFactors[p.level];                    // :69, :94
+        q[i].u = p.projX;
+        q[i].v = p.projY;
+        q[i].r = rr;
+        q[i].min_level = p.level - 1;
+        q[i].max_level = p.level;
+        q[i].ur = p.projXR;
+        q[i].ur_tol = rr;
+        q[i].angle = 0;
+        q[i].blocks = 1;
+        memcpy(&qdesc[i * 32], p.descriptor, 32);
+    }
+    return projection_search(ORB_PROJ_RATIO_SAME_LEVEL, F, F.uRight != nullptr, q, qdesc, vpMapPointMatches,
+                             "SearchByProjection(F, MapPoints)");
+}
+
+int ORBmatcher::SearchByProjectionBird(FrameData& F, const ProjectedBirdPoints& vpMapPointsBird, const float r,
+                                       std::vector<int>& vpMapPointMatchesBird) {
+    const size_t nq = vpMapPointsBird.points.size();
+    std::vector<orb_proj_query> q(nq);
+    std::vector<uint8_t> qdesc(nq * 32);
+    for (size_t i = 0; i < nq; i++) {
+        const ProjectedBirdPoints::Point& p = vpMapPointsBird.points[i];
+        require(p.descriptor != nullptr, "SearchByProjectionBird: map point");
+        q[i].u = p.x;
+        q[i].v = p.y;
+        q[i].r = r;
+        q[i].min_level = -1;   // GetFeaturesInAreaBirdview(pt.x, pt.y, r): the default levels (:1945)
+        q[i].max_level = -1;
+        q[i].ur = 0;
+        q[i].ur_tol = 0;
+        q[i].angle = 0;
+        q[i].blocks = 1;
+        memcpy(&qdesc[i * 32], p.descriptor, 32);
+    }
+    return projection_search(ORB_PROJ_RATIO_SAME_LEVEL, F, false, q, qdesc, vpMapPointMatchesBird,
+                             "SearchByProjectionBird");
 }
 
 std::vector<int> ComputeDistinctiveDescriptors(const std::vector<std::vector<const uint8_t*> >& observations) {

@@ -22,7 +22,7 @@
 #include "ORBextractor.h"
 
 // The matcher lives in ORB_SLAM2 like the reference's.  When integrated next to the reference's own
-// ORB_SLAM2::ORBmatcher (which keeps the projection-based searches), build with
+// ORB_SLAM2::ORBmatcher (which keeps Fuse, SearchBySim3 and the keyframe forms of SearchByProjection), build with
 // -DORBGPU_MATCHER_NAMESPACE=orbgpu_host.
 #ifndef ORBGPU_MATCHER_NAMESPACE
 #define ORBGPU_MATCHER_NAMESPACE ORB_SLAM2
@@ -51,6 +51,9 @@ public:
     // birdview grid: GridElementWidthInv/HeightInv given directly, origin (0, 0)
     static FrameGrid Birdview(const KeyPoint* keysBird, int n, float widthInv, float heightInv);
     std::vector<size_t> GetFeaturesInArea(float x, float y, float r, int minLevel = -1, int maxLevel = -1) const;
+    // the grid as the C-ABI's orb_frame_grid (cells column-major, a cell's keypoints in its vector's order); off and
+    // idx receive the CSR arrays the returned struct points into
+    orb_frame_grid Csr(std::vector<int>& off, std::vector<int>& idx) const;
 
 private:
     void assign(const KeyPoint* keys, int n);
@@ -79,6 +82,41 @@ struct FeatureSet {
 // reference's names: SearchByBoW(KeyFrame*, Frame&) vs SearchByBoW(KeyFrame*, KeyFrame*)).
 struct FrameData : FeatureSet {};
 struct KeyFrameData : FeatureSet {};
+
+// What the projection-gated searches read of each projected map point: values the caller already holds
+// (Frame::isInFrustum stores them in the MapPoint; TrackWithMotionModel computes them in its loop).  The points the
+// reference skips before its search are left out by the caller (each struct says which), as SearchForTriangulation's
+// epipole is computed by the caller.  A result vector holds, per Frame feature, the index (into `points`) of the
+// map point the reference assigns to it, -1 where it assigns none, -2 where the rotation cull reset it to NULL.
+struct ProjectedLastFrame {   // SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)
+    struct Point {            // LastFrame feature i with a MapPoint, !mvbOutlier[i], invzc >= 0, (u, v) inside the
+        float u, v;           //   CurrentFrame's bounds (ORBmatcher.cc:1355-1376): the projection (:1370-1371)
+        float invzc;          // 1 / x3Dc.z (:1365)
+        int octave;           // LastFrame.mvKeys[i].octave (:1378)
+        float angle;          // LastFrame.mvKeysUn[i].angle (:1433)
+        bool observed;        // pMP->Observations() > 0 (false: a temporal point of Tracking::UpdateLastFrame)
+        const uint8_t* descriptor;   // pMP->GetDescriptor(), 32 bytes
+    };
+    std::vector<Point> points;
+    bool bForward = false, bBackward = false;   // :1348-1349 (ignored when bMono)
+    float mbf = 0;                              // CurrentFrame.mbf
+};
+struct ProjectedMapPoints {   // SearchByProjection(Frame& F, const vector<MapPoint*>&, th)
+    struct Point {            // a MapPoint with mbTrackInView && !isBad() (:54-58)
+        float projX, projY, projXR;   // mTrackProjX, mTrackProjY, mTrackProjXR
+        int level;                    // mnTrackScaleLevel
+        float viewCos;                // mTrackViewCos
+        const uint8_t* descriptor;
+    };
+    std::vector<Point> points;
+};
+struct ProjectedBirdPoints {   // SearchByProjectionBird(Frame& F, const vector<MapPointBird*>&, r)
+    struct Point {             // mnLastFrameSeen != F.mnId, |localPos.z| <= 0.2, pt inside the birdview (:1933-1943)
+        float x, y;            // Frame::ProjectXYZ2Birdview(localPos) (:1940)
+        const uint8_t* descriptor;
+    };
+    std::vector<Point> points;
+};
 
 class ORBmatcher {
 public:
@@ -119,11 +157,25 @@ public:
                       std::vector<Point2f>& vPrevMatched, int windowSize = 10);
     int BirdviewMatch(const FrameData& F1, const FrameData& F2, std::vector<int>& vnMatches12, int windowSize = 10);
 
+    // ORBmatcher.cc:1328-1470.  CurrentFrame: keys (mvKeysUn), descriptors, grid, uRight (NULL: monocular, all -1),
+    // hasMapPoint (mvpMapPoints[i] && Observations() > 0; NULL: none), scaleFactors, nlevels.
+    int SearchByProjection(FrameData& CurrentFrame, const ProjectedLastFrame& LastFrame, const float th, const bool bMono,
+                           std::vector<int>& vpMapPointMatches);
+    // ORBmatcher.cc:45-129.  F: as above.
+    int SearchByProjection(FrameData& F, const ProjectedMapPoints& vpMapPoints, const float th,
+                           std::vector<int>& vpMapPointMatches);
+    // ORBmatcher.cc:1923-1998.  F: keys (mvKeysBird), descriptors (mDescriptorsBird), grid (FrameGrid::Birdview),
+    // hasMapPoint (mvpMapPointsBird[i] && Observations() > 0).
+    int SearchByProjectionBird(FrameData& F, const ProjectedBirdPoints& vpMapPointsBird, const float r,
+                               std::vector<int>& vpMapPointMatchesBird);
+
     static const int TH_LOW;
     static const int TH_HIGH;
     static const int HISTO_LENGTH;
 
 protected:
+    int projection_search(int mode, const FeatureSet& F, bool stereo, const std::vector<orb_proj_query>& q,
+                          const std::vector<uint8_t>& qdesc, std::vector<int>& matches, const char* what);
     int window_match(bool level0_only, const FeatureSet& F1, const FeatureSet& F2, const std::vector<Point2f>* centres,
                      int windowSize, std::vector<int>& vnMatches12);
     float mfNNratio;

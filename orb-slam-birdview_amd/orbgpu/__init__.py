@@ -14,7 +14,8 @@ from ._lib import (VARIANT_BLUR_HALFUP, VARIANT_DEFAULT, VARIANT_NO_FMA, VARIANT
                    VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, check, lib)
 
 __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError", "device_count",
-           "features_in_area", "compute_stereo_matches", "ORBVocabulary", "BirdORB", "cornerSubPix",
+           "features_in_area", "frame_grid", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
+           "compute_stereo_matches", "ORBVocabulary", "BirdORB", "cornerSubPix",
            "bird_footprint_mask", "VARIANT_DEFAULT", "VARIANT_TIE_REVERSE", "VARIANT_RESIZE_GENERIC",
            "VARIANT_BLUR_HALFUP", "VARIANT_NO_FMA"]
 
@@ -23,6 +24,12 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 assert KP_DTYPE.itemsize == 28
 
 TH_LOW, TH_HIGH, HISTO_LENGTH = 50, 100, 30   # ORBmatcher.cc:37-39
+
+# orb_proj_query (include/orbgpu.h): one projected map point of the projection-gated searches
+PROJ_QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("r", "<f4"), ("min_level", "<i4"), ("max_level", "<i4"),
+                             ("ur", "<f4"), ("ur_tol", "<f4"), ("angle", "<f4"), ("blocks", "<i4")])
+assert PROJ_QUERY_DTYPE.itemsize == 36
+PROJ_BEST, PROJ_RATIO_SAME_LEVEL = 0, 1   # ORB_PROJ_*
 
 
 def _p(a):
@@ -480,6 +487,91 @@ class ORBmatcher:
                                           len(a[0]), _p(a[0]), _p(a[1]), _p(cen), float(window), len(a[2]), _p(a[2]),
                                           _p(a[3]), g, _p(out), ctypes.byref(nm)), "window match (grid)")
         return nm.value, out[:len(a[0])]
+
+    def search_by_projection(self, mode, queries, qdesc, tdesc, kps_t, grid, t_uright=None, t_taken=None,
+                             min_xy=(0.0, 0.0), max_dist=TH_HIGH):
+        """orb_search_by_projection: the projection-gated searches' core.  queries: PROJ_QUERY_DTYPE array (one per
+        projected map point) with descriptors qdesc; trains tdesc / kps_t with their grid (frame_grid(...)),
+        t_uright (mvuRight; None = no stereo gate) and t_taken (mvpMapPoints[t] && Observations() > 0; None = none).
+        Returns (nmatches, match_t): match_t[t] = the last query assigned to train t, -1 = untouched, -2 = reset
+        by the rotation cull."""
+        inv_w, inv_h, off, idx = grid
+        qa = np.ascontiguousarray(queries, PROJ_QUERY_DTYPE)
+        qd = np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
+        td = np.ascontiguousarray(tdesc, np.uint8).reshape(-1, 32)
+        kt = np.ascontiguousarray(kps_t, KP_DTYPE)
+        assert len(qa) == len(qd) and len(td) == len(kt)
+        ur = None if t_uright is None else np.ascontiguousarray(t_uright, np.float32)
+        tk = None if t_taken is None else np.ascontiguousarray(t_taken, np.uint8)
+        assert (ur is None or len(ur) == len(kt)) and (tk is None or len(tk) == len(kt))
+        off = np.ascontiguousarray(off, np.int32)
+        idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
+        g = OrbFrameGrid(float(min_xy[0]), float(min_xy[1]), inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+        out = np.full(max(len(kt), 1), -1, np.int32)
+        nm = ctypes.c_int()
+        check(lib().orb_search_by_projection(self._ctx.h, int(mode), self.mfNNratio, int(self.mbCheckOrientation),
+                                             int(max_dist), len(qa), _p(qa), _p(qd), len(kt), _p(td), _p(kt), _p(ur),
+                                             _p(tk), g, _p(out), ctypes.byref(nm)), "orb_search_by_projection")
+        return nm.value, out[:len(kt)]
+
+    def SearchByProjection_CF_LF(self, u, v, invzc, octave, angle, observed, desc_mp, scale_factors, mbf, th, bMono,
+                                 desc_cf, kps_cf, grid_cf, uright_cf=None, taken_cf=None, min_xy=(0.0, 0.0),
+                                 bForward=False, bBackward=False):
+        """SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono) (ORBmatcher.cc:1328-1470).
+        Per LastFrame map point the search keeps (the caller drops outliers, invzc < 0 and projections out of
+        bounds, :1355-1376): its projection (u, v) and invzc, LastFrame.mvKeys[i].octave, mvKeysUn[i].angle,
+        Observations() > 0 and descriptor.  bForward / bBackward as :1348-1349 (ignored when bMono).  The
+        CurrentFrame side: mDescriptors, mvKeysUn, its grid, mvuRight, and which mvpMapPoints are observed.
+        Returns (nmatches, match_cf)."""
+        f32 = np.float32
+        u, v, invzc = (np.asarray(a, f32) for a in (u, v, invzc))
+        octave = np.asarray(octave, np.int32)
+        q = np.zeros(len(u), PROJ_QUERY_DTYPE)
+        q["u"], q["v"] = u, v
+        q["r"] = f32(th) * np.asarray(scale_factors, f32)[octave]          # :1381
+        if bForward and not bMono:                                        # :1385-1390
+            q["min_level"], q["max_level"] = octave, -1
+        elif bBackward and not bMono:
+            q["min_level"], q["max_level"] = 0, octave
+        else:
+            q["min_level"], q["max_level"] = octave - 1, octave + 1
+        q["ur"] = u - f32(mbf) * invzc                                     # :1409
+        q["ur_tol"] = q["r"]
+        q["angle"] = np.asarray(angle, f32)
+        q["blocks"] = np.asarray(observed, bool)
+        return self.search_by_projection(PROJ_BEST, q, desc_mp, desc_cf, kps_cf, grid_cf, uright_cf, taken_cf, min_xy)
+
+    def SearchByProjection_F_MapPoints(self, proj_x, proj_y, proj_xr, level, view_cos, desc_mp, scale_factors, th,
+                                       desc_f, kps_f, grid_f, uright_f=None, taken_f=None, min_xy=(0.0, 0.0)):
+        """SearchByProjection(Frame& F, const vector<MapPoint*>&, th) (ORBmatcher.cc:45-129).  Per map point with
+        mbTrackInView && !isBad() (:54-58, filtered by the caller): mTrackProjX / Y / XR, mnTrackScaleLevel,
+        mTrackViewCos and its descriptor.  Returns (nmatches, match_f)."""
+        f32 = np.float32
+        level = np.asarray(level, np.int32)
+        q = np.zeros(len(level), PROJ_QUERY_DTYPE)
+        q["u"], q["v"] = np.asarray(proj_x, f32), np.asarray(proj_y, f32)
+        r = np.where(np.asarray(view_cos, f32).astype(np.float64) > 0.998, f32(2.5), f32(4.0)).astype(f32)   # :131-137
+        if f32(th) != 1.0:                                                 # :49, :65-66
+            r = r * f32(th)
+        q["r"] = r * np.asarray(scale_factors, f32)[level]                 # :69
+        q["min_level"], q["max_level"] = level - 1, level
+        q["ur"] = np.asarray(proj_xr, f32)
+        q["ur_tol"] = q["r"]                                               # :94
+        q["blocks"] = 1
+        return self.search_by_projection(PROJ_RATIO_SAME_LEVEL, q, desc_mp, desc_f, kps_f, grid_f, uright_f, taken_f,
+                                         min_xy)
+
+    def SearchByProjectionBird(self, pt_x, pt_y, desc_mp, r, desc_bird, kps_bird, grid_bird, taken_bird=None):
+        """SearchByProjectionBird(Frame& F, const vector<MapPointBird*>&, r) (ORBmatcher.cc:1923-1998).  Per birdview
+        map point the search keeps (:1933-1943, filtered by the caller): its birdview projection pt and descriptor;
+        the Frame's mDescriptorsBird, mvKeysBird, birdview grid.  Returns (nmatches, match_bird)."""
+        q = np.zeros(len(pt_x), PROJ_QUERY_DTYPE)
+        q["u"], q["v"] = np.asarray(pt_x, np.float32), np.asarray(pt_y, np.float32)
+        q["r"] = np.float32(r)
+        q["min_level"], q["max_level"] = -1, -1                            # GetFeaturesInAreaBirdview's defaults
+        q["blocks"] = 1
+        return self.search_by_projection(PROJ_RATIO_SAME_LEVEL, q, desc_mp, desc_bird, kps_bird, grid_bird, None,
+                                         taken_bird)
 
     def SearchForInitialization(self, desc1, kps1, desc2, kps2, cand_off, cand_idx):
         """SearchForInitialization (ORBmatcher.cc:405-520); candidates = F2.GetFeaturesInArea per query.

@@ -95,6 +95,8 @@ SIGNATURES = {
     "orb_window_match": (ci, [vp, cf, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, ctypes.POINTER(ci)]),
     "orb_window_match_grid": (ci, [vp, cf, ci, ci, ci, vp, vp, vp, cf, ci, vp, vp, OrbFrameGrid, vp,
                                    ctypes.POINTER(ci)]),
+    "orb_search_by_projection": (ci, [vp, ci, cf, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, OrbFrameGrid, vp,
+                                      ctypes.POINTER(ci)]),
     "orb_features_in_area": (ci, [ci, vp, cf, cf, cf, cf, cf, cf, cf, ci, ci, vp, ci]),
     "orb_compute_stereo_matches": (ci, [vp, vp, ci, vp, vp, ci, vp, vp, cf, cf, vp, vp, ctypes.POINTER(ci)]),
     "orb_stereo_batch_device": (ci, [vp, ci, cf, cf, vp, vp, vp]),
