@@ -404,6 +404,51 @@ int orb_search_by_projection(orb_ctx* ctx, int mode, float nnratio, int check_or
                              int nq, const orb_proj_query* q, const uint8_t* qdesc,
                              int nt, const uint8_t* tdesc, const orb_keypoint* kps_t, const float* t_uright,
                              const uint8_t* t_taken, orb_frame_grid grid, int* match_t, int* nmatches);
+/* The keyframe forms of SearchByProjection map onto the same core (points the reference skips before its search are
+ * left out by the caller: isBad, already found, negative depth, !IsInImage, the distance and viewing-angle tests):
+ *   SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>&, vector<MapPoint*>& vpMatched, th)  :290-403
+ *     r = th * mvScaleFactors[nPredictedLevel]; levels (pred - 1, pred); t_uright NULL; blocks = 1;
+ *     t_taken[idx] = vpMatched[idx] != NULL; mode BEST, check_ori 0, max_dist TH_LOW.
+ *   SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>&, th, ORBdist)                  :1472-1599
+ *     r = th * mvScaleFactors[nPredictedLevel]; levels (pred - 1, pred + 1); t_uright NULL; blocks = 1;
+ *     angle = pKF->mvKeysUn[i].angle; t_taken[i2] = CurrentFrame.mvpMapPoints[i2] != NULL; mode BEST, the matcher's
+ *     check_ori (the cull of :1577-1596 is that of :1448-1467), max_dist ORBdist. */
+
+/* The searches that decide every projected point on its own (nothing like a taken set is read inside the search):
+ * Fuse(KeyFrame*, const vector<MapPoint*>&, th) (ORBmatcher.cc:823-975, gate FUSE), Fuse(KeyFrame*, cv::Mat Scw, ...)
+ * (:977-1100, gate NONE) and both directions of SearchBySim3 (:1102-1326, gate NONE).  Many targets (keyframes with
+ * their projected points) go into one call: one staging, one launch, one synchronisation.  Per query of a target the
+ * candidates are KeyFrame::GetFeaturesInArea(u, v, r) (KeyFrame.cc:586-625: Frame::GetFeaturesInArea without level
+ * arguments) over the target's grid, filtered by (min_level, max_level) with orb_proj_query's semantics (the callers
+ * pass (pred - 1, pred): `kpLevel<nPredictedLevel-1 || kpLevel>nPredictedLevel`), and with gate FUSE by the
+ * chi-square reprojection test of :914-938: ex = u - kp.x, ey = v - kp.y, er = ur - uright[t];
+ *   uright[t] >= 0 (not > 0):  skipped when (double)(e2 * inv_sigma2[octave]) > 7.8,  e2 = ex*ex + ey*ey + er*er
+ *   otherwise:                 skipped when (double)(e2 * inv_sigma2[octave]) > 5.99, e2 = ex*ex + ey*ey
+ * in float with the reference build's contractions (tools/fuse_flags_probe.cpp): e2 = fmaf(er, er, fmaf(ex, ex,
+ * ey * ey)) and fmaf(ex, ex, ey * ey).  best_idx / best_dist[i] = the train with the smallest descriptor distance,
+ * the first in candidate order on ties, and that distance; -1 / -1 if no candidate passes.  TH_LOW / TH_HIGH and
+ * what follows (GetMapPoint, Replace, AddObservation, the Sim3 agreement) are the caller's.
+ * ORB_ERR_ARG before any GPU work, and nothing runs if any target is malformed: an unknown gate, ntargets < 0, NULL
+ * outputs with nq > 0, a u, v or r that is not finite or r < 0, with gate FUSE a ur that is not finite, a grid CSR
+ * orb_window_match_grid would refuse, gate FUSE with inv_sigma2 == NULL, nlevels outside [1, ORBGPU_MAX_LEVELS] or a
+ * train octave outside [0, nlevels).  ntargets == 0, a target with nq == 0: ORB_OK; nt == 0: its outputs are -1. */
+enum { ORB_PROJ_GATE_NONE = 0, ORB_PROJ_GATE_FUSE = 1 };
+typedef struct orb_proj_target {
+    int nq; const orb_proj_query* q; const uint8_t* qdesc;   /* u, v, r, min_level, max_level, ur are read;
+                                                                 ur_tol, angle, blocks are ignored */
+    int nt; const uint8_t* tdesc; const orb_keypoint* kps_t; /* mvKeysUn, mDescriptors of the keyframe */
+    const float* t_uright;      /* mvuRight; NULL = every train is monocular (gate FUSE only) */
+    const float* inv_sigma2;    /* mvInvLevelSigma2, nlevels entries (gate FUSE only) */
+    int nlevels;
+    orb_frame_grid grid;        /* the keyframe's mGrid, as for orb_search_by_projection */
+    int* best_idx; int* best_dist;   /* nq each: first minimum in GetFeaturesInArea order; -1 / -1 if none passes */
+} orb_proj_target;
+int orb_project_best_batch(orb_ctx* ctx, int gate, int ntargets, const orb_proj_target* targets);
+/* One query of one target on the CPU (host only, no context): the same arithmetic and the same result as
+ * orb_project_best_batch gives for it, for a caller that replays a point whose descriptor changed after the batched
+ * call.  The target's best_idx / best_dist are not touched.  ORB_ERR_ARG as above, for this target
+ * and this query. */
+int orb_project_best_host(int gate, const orb_proj_target* target, int query, int* best_idx, int* best_dist);
 
 /* Frame::GetFeaturesInArea over the 64x48 Frame grid (Frame.cc:378-412, 494-560): host helper the
  * C++ mirror uses to build window candidate lists. Returns count or -(needed)-1. */

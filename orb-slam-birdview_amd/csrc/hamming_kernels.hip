@@ -1,7 +1,8 @@
 // gfx950 Hamming-distance kernels for ORBmatcher's vocabulary-gated searches (ORBmatcher.cc): the 256-bit
 // distance (DescriptorDistance, ORBmatcher.cc:1647-1663) as 8 x (v_xor_b32 + v_bcnt_u32_b32) per pair on the VALU,
 // over CSR candidate lists (k_topk), the Frame grid's windows (k_window_topk: one window size and the query's own
-// level; k_projection_topk: per-query centre, radius, level range and stereo gate) and SearchForTriangulation's
+// level; k_projection_topk: per-query centre, radius, level range and stereo gate; k_projection_best: the first
+// minimum per projected point over many keyframes' grids, with Fuse's reprojection gate) and SearchForTriangulation's
 // epipolar-gated candidates (k_triangulation).  The all-pairs top-2 on the matrix cores is hamming_top2.hip.
 // The selection logic that depends on the order of earlier accepted matches (SearchByBoW's taken set,
 // SearchForInitialization's vMatchedDistance) is replayed on the host from these exact top-k lists
@@ -286,6 +287,94 @@ __global__ __launch_bounds__(256) void k_projection_topk(const orb_proj_query* _
     if (lane == 0 && live) out_nvalid[qi] = nvalid;
 }
 
+// The searches that decide every projected point on its own: Fuse(KeyFrame*, vector<MapPoint*>, th) (:892-949,
+// GATE 1), Fuse(KeyFrame*, Scw, ...) (:1051-1079) and both directions of SearchBySim3 (:1191-1219, :1271-1299)
+// (GATE 0).  One wavefront per (target, query) item, the items of all targets in one launch; the item's target row
+// gives where its keyframe's descriptors, keypoints, mvuRight, mvInvLevelSigma2 and grid CSR lie in the staging
+// area.  The walk is k_projection_topk's (KeyFrame::GetFeaturesInArea is Frame::GetFeaturesInArea without levels;
+// the level filter of the callers is the query's (min_level, max_level)); a lane keeps one key dist << 32 | slot
+// (a slot is the candidate's rank in vIndices), so the wave minimum is the reference's first minimum.
+// GATE 1: the chi-square reprojection test of :914-938 in the reference build's contracted forms
+// (tools/fuse_flags_probe.cpp; this file builds -ffp-contract=off, so the fmaf below are the only fused operations);
+// the octave indexes inv_sigma2, which the host validated.  Waves past the last item stay in with an empty window.
+template <int GATE>
+__global__ __launch_bounds__(256) void k_projection_best(const uint8_t* __restrict__ base,
+                                                         const ProjTarget* __restrict__ tab,
+                                                         const int* __restrict__ item_tgt,
+                                                         const orb_proj_query* __restrict__ pq,
+                                                         const uint8_t* __restrict__ q, int nitems,
+                                                         int* __restrict__ out_idx, int* __restrict__ out_dist) {
+    constexpr int COLS = 64, ROWS = 48;   // KeyFrame.h: FRAME_GRID_COLS / ROWS
+    const int it = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const bool live = it < nitems;
+    const int ic = live ? it : nitems - 1;   // (nitems >= 1: the launcher returns before an empty launch)
+    const orb_proj_query P = pq[ic];
+    const ProjTarget T = tab[item_tgt[ic]];
+    const uint4* qp = reinterpret_cast<const uint4*>(q + (long long)ic * 32);
+    const uint4 qa = qp[0], qb = qp[1];
+    const uint8_t* t = base + T.o_t;
+    const orb_keypoint* kps = reinterpret_cast<const orb_keypoint*>(base + T.o_kps);
+    const float* uright = T.o_ur >= 0 ? reinterpret_cast<const float*>(base + T.o_ur) : nullptr;
+    const float* inv_sigma2 = reinterpret_cast<const float*>(base + T.o_inv);
+    const int* cell_off = reinterpret_cast<const int*>(base + T.o_coff);
+    const int* cell_idx = reinterpret_cast<const int*>(base + T.o_cidx);
+    const ProjGrid g = T.g;
+    const float x = P.u, y = P.v, r = P.r;
+    const int nMinCellX = max(0, (int)floorf((x - g.min_x - r) * g.inv_w));
+    const int nMaxCellX = min(COLS - 1, (int)ceilf((x - g.min_x + r) * g.inv_w));
+    const int nMinCellY = max(0, (int)floorf((y - g.min_y - r) * g.inv_h));
+    const int nMaxCellY = min(ROWS - 1, (int)ceilf((y - g.min_y + r) * g.inv_h));
+    const bool empty = !live || nMinCellX >= COLS || nMaxCellX < 0 || nMinCellY >= ROWS || nMaxCellY < 0;
+    const bool bCheckLevels = P.min_level > 0 || P.max_level >= 0;
+    unsigned long long best = ~0ull;
+    if (!empty) {
+        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
+            const int s0 = cell_off[ix * ROWS + nMinCellY], s1 = cell_off[ix * ROWS + nMaxCellY + 1];
+            for (int s = s0 + lane; s < s1; s += 64) {
+                const int ti = cell_idx[s];
+                const orb_keypoint kp = kps[ti];
+                if (bCheckLevels) {
+                    if (kp.octave < P.min_level) continue;
+                    if (P.max_level >= 0 && kp.octave > P.max_level) continue;
+                }
+                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;   // KeyFrame.cc:615-619
+                if (GATE == ORB_PROJ_GATE_FUSE) {                               // ORBmatcher.cc:914-938
+                    const float urt = uright ? uright[ti] : -1.0f;
+                    const float ex = x - kp.x, ey = y - kp.y;
+                    const float e2m = fmaf(ex, ex, ey * ey);
+                    const float is2 = inv_sigma2[kp.octave];
+                    if (urt >= 0) {
+                        const float er = P.ur - urt;
+                        const float e2 = fmaf(er, er, e2m);
+                        if ((double)(e2 * is2) > 7.8) continue;
+                    } else {
+                        if ((double)(e2m * is2) > 5.99) continue;
+                    }
+                }
+                const uint4* tp = reinterpret_cast<const uint4*>(t + (long long)ti * 32);
+                const int d = hamming256(qa, qb, tp[0], tp[1]);
+                const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)s;
+                best = key < best ? key : best;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(best, o);
+        best = w < best ? w : best;
+    }
+    if (lane == 0 && live) {
+        int dd = -1, ii = -1;
+        if (best != ~0ull) {
+            dd = (int)(best >> 32);
+            ii = cell_idx[(int)(best & 0xFFFFFFFFu)];
+        }
+        out_idx[it] = ii;
+        out_dist[it] = dd;
+    }
+}
+
 /* SearchForTriangulation inner loop (ORBmatcher.cc:712-761) for one (idx1, node) item per
  * wavefront: dist <= TH_LOW, epipole distance gate for mono pairs, CheckDistEpipolarLine
  * (:140-157, float with the final comparison in double).  The reference keeps the LAST candidate
@@ -357,6 +446,21 @@ hipError_t launch_projection_topk(const orb_proj_query* d_pq, const uint8_t* d_q
     else
         hipLaunchKernelGGL(k_projection_topk<64>, dim3((nq + 3) / 4), dim3(256), 0, stream, d_pq, d_q, nq, d_t, d_kps2,
                            d_uright, d_cell_off, d_cell_idx, g, d_thr, k, d_dist, d_idx, d_nvalid);
+    return hipGetLastError();
+}
+
+hipError_t launch_projection_best(int gate, const uint8_t* d_base, const ProjTarget* d_tab, const int* d_item_tgt,
+                                  const orb_proj_query* d_pq, const uint8_t* d_q, int nitems, int* d_idx, int* d_dist,
+                                  hipStream_t stream) {
+    if (nitems <= 0) return hipSuccess;
+    if (gate == ORB_PROJ_GATE_FUSE)
+        hipLaunchKernelGGL(k_projection_best<ORB_PROJ_GATE_FUSE>, dim3((nitems + 3) / 4), dim3(256), 0, stream, d_base,
+                           d_tab, d_item_tgt, d_pq, d_q, nitems, d_idx, d_dist);
+    else if (gate == ORB_PROJ_GATE_NONE)
+        hipLaunchKernelGGL(k_projection_best<ORB_PROJ_GATE_NONE>, dim3((nitems + 3) / 4), dim3(256), 0, stream, d_base,
+                           d_tab, d_item_tgt, d_pq, d_q, nitems, d_idx, d_dist);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -1027,6 +1027,81 @@ int proj_replay(TopkSession& s, int mode, float nnratio, int check_ori, int max_
     if (nmatches_out) *nmatches_out = nmatches;
     return ORB_OK;
 }
+
+// What is wrong with a target of orb_project_best_batch for its queries [q0, q1), or NULL.  The kernel indexes
+// inv_sigma2 by the train's octave and the trains by the grid's cell_idx, so both are checked here.
+const char* proj_target_fault(int gate, const orb_proj_target& T, int q0, int q1) {
+    if (T.nq < 0 || T.nt < 0) return "negative count";
+    if (T.nq > 0 && (!T.best_idx || !T.best_dist)) return "NULL outputs";
+    if ((T.nq > 0 && (!T.q || !T.qdesc)) || (T.nt > 0 && (!T.tdesc || !T.kps_t)) || !T.grid.cell_off ||
+        (T.grid.cell_off[64 * 48] && !T.grid.cell_idx))
+        return "bad arguments";
+    for (int i = q0; i < q1; i++) {
+        if (!std::isfinite(T.q[i].u) || !std::isfinite(T.q[i].v) || !std::isfinite(T.q[i].r) || T.q[i].r < 0)
+            return "query window not finite or radius negative";
+        if (gate == ORB_PROJ_GATE_FUSE && !std::isfinite(T.q[i].ur)) return "query ur not finite";
+    }
+    if (const char* why = grid_csr_fault(T.grid, T.nt)) return why;
+    if (gate == ORB_PROJ_GATE_FUSE) {
+        if (!T.inv_sigma2) return "inv_sigma2 NULL";
+        if (T.nlevels < 1 || T.nlevels > ORBGPU_MAX_LEVELS) return "nlevels outside [1, ORBGPU_MAX_LEVELS]";
+        for (int t = 0; t < T.nt; t++)
+            if (T.kps_t[t].octave < 0 || T.kps_t[t].octave >= T.nlevels) return "train octave outside [0, nlevels)";
+    }
+    return nullptr;
+}
+
+// Fuse's reprojection gate (ORBmatcher.cc:914-938): true = the candidate is skipped.  The sums in the reference
+// build's contracted forms (tools/fuse_flags_probe.cpp); fmaf is exact whether it is an instruction or libm's.
+bool fuse_gate_skips(float u, float v, float ur, const orb_keypoint& kp, float urt, float inv_sigma2) {
+    const float ex = u - kp.x, ey = v - kp.y;
+    const float e2m = __builtin_fmaf(ex, ex, ey * ey);
+    if (urt >= 0) {
+        const float er = ur - urt;
+        const float e2 = __builtin_fmaf(er, er, e2m);
+        return (double)(e2 * inv_sigma2) > 7.8;
+    }
+    return (double)(e2m * inv_sigma2) > 5.99;
+}
+
+// One query of a (validated) target on the CPU: k_projection_best's walk over the grid CSR, sequentially.
+void proj_best_one(int gate, const orb_proj_target& T, const orb_proj_query& P, const uint8_t* qdesc, int* best_idx,
+                   int* best_dist) {
+    const int COLS = 64, ROWS = 48;
+    const orb_frame_grid& g = T.grid;
+    *best_idx = -1;
+    *best_dist = -1;
+    const float x = P.u, y = P.v, r = P.r;
+    const int x0 = std::max(0, (int)std::floor((x - g.min_x - r) * g.inv_w));
+    const int x1 = std::min(COLS - 1, (int)std::ceil((x - g.min_x + r) * g.inv_w));
+    const int y0 = std::max(0, (int)std::floor((y - g.min_y - r) * g.inv_h));
+    const int y1 = std::min(ROWS - 1, (int)std::ceil((y - g.min_y + r) * g.inv_h));
+    if (x0 >= COLS || x1 < 0 || y0 >= ROWS || y1 < 0) return;
+    const bool checkLevels = P.min_level > 0 || P.max_level >= 0;
+    int bestDist = INT_MAX, bestIdx = -1;
+    for (int ix = x0; ix <= x1; ix++)
+        for (int s = g.cell_off[ix * ROWS + y0]; s < g.cell_off[ix * ROWS + y1 + 1]; s++) {
+            const int ti = g.cell_idx[s];
+            const orb_keypoint& kp = T.kps_t[ti];
+            if (checkLevels) {
+                if (kp.octave < P.min_level) continue;
+                if (P.max_level >= 0 && kp.octave > P.max_level) continue;
+            }
+            if (!(std::fabs(kp.x - x) < r && std::fabs(kp.y - y) < r)) continue;
+            if (gate == ORB_PROJ_GATE_FUSE &&
+                fuse_gate_skips(x, y, P.ur, kp, T.t_uright ? T.t_uright[ti] : -1.0f, T.inv_sigma2[kp.octave]))
+                continue;
+            const int d = orb_descriptor_distance(qdesc, T.tdesc + (size_t)ti * 32);
+            if (d < bestDist) {
+                bestDist = d;
+                bestIdx = ti;
+            }
+        }
+    if (bestIdx >= 0) {
+        *best_idx = bestIdx;
+        *best_dist = bestDist;
+    }
+}
 }  // namespace
 }  // namespace orbgpu
 
@@ -1111,6 +1186,110 @@ int orb_search_by_projection(orb_ctx* h, int mode, float nnratio, int check_ori,
     const int st = s.setup_proj(nq, q, qdesc, nt, tdesc, kps_t, t_uright, grid, lanes);
     if (st != ORB_OK) return st;
     return proj_replay(s, mode, nnratio, check_ori, max_dist, q, kps_t, t_taken, match_t, nmatches_out);
+}
+
+/* Fuse (both overloads) and SearchBySim3's two directions: per (target, query) the first minimum of the descriptor
+ * distance over the gated candidates, every target's items in one k_projection_best launch (orbgpu.h). */
+int orb_project_best_batch(orb_ctx* h, int gate, int ntargets, const orb_proj_target* targets) {
+    // everything is checked before the context and before any output is written: nothing runs if a target is malformed
+    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE)
+        return set_error("orb_project_best_batch: unknown gate", hipSuccess), ORB_ERR_ARG;
+    if (ntargets < 0 || (ntargets > 0 && !targets))
+        return set_error("orb_project_best_batch: ntargets < 0 or targets NULL", hipSuccess), ORB_ERR_ARG;
+    size_t nitems = 0, nused = 0;
+    for (int k = 0; k < ntargets; k++) {
+        if (const char* why = proj_target_fault(gate, targets[k], 0, targets[k].nq))
+            return set_error(("orb_project_best_batch: target " + std::to_string(k) + ": " + why).c_str(), hipSuccess),
+                   ORB_ERR_ARG;
+        if (targets[k].nq > 0 && targets[k].nt > 0) {
+            nitems += (size_t)targets[k].nq;
+            nused++;
+        }
+    }
+    if (nitems > (size_t)INT_MAX / 2)
+        return set_error("orb_project_best_batch: too many queries", hipSuccess), ORB_ERR_ARG;
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    CTX_GUARD(c);
+    for (int k = 0; k < ntargets; k++)
+        for (int i = 0; i < targets[k].nq; i++) targets[k].best_idx[i] = targets[k].best_dist[i] = -1;
+    if (nitems == 0) return ORB_OK;
+    // the staging area: [table | item -> table row | queries | query descriptors | per used target: descriptors,
+    // keypoints, uright, inv_sigma2, cell_off, cell_idx] in one DMA, then the outputs the kernel writes into the mirror
+    const int ncells = 64 * 48;
+    Stage st{c};
+    const size_t o_tab = st.add(nused * sizeof(ProjTarget)), o_item = st.add(nitems * 4),
+                 o_pq = st.add(nitems * sizeof(orb_proj_query)), o_q = st.add(nitems * 32);
+    std::vector<ProjTarget> tab;
+    tab.reserve(nused);
+    for (int k = 0; k < ntargets; k++) {
+        const orb_proj_target& T = targets[k];
+        if (T.nq == 0 || T.nt == 0) continue;
+        ProjTarget R;
+        R.o_t = (long long)st.add((size_t)T.nt * 32);
+        R.o_kps = (long long)st.add((size_t)T.nt * sizeof(orb_keypoint));
+        R.o_ur = gate == ORB_PROJ_GATE_FUSE && T.t_uright ? (long long)st.add((size_t)T.nt * 4) : -1;
+        R.o_inv = gate == ORB_PROJ_GATE_FUSE ? (long long)st.add((size_t)T.nlevels * 4) : 0;
+        R.o_coff = (long long)st.add((size_t)(ncells + 1) * 4);
+        R.o_cidx = (long long)st.add((size_t)T.grid.cell_off[ncells] * 4);
+        R.g = ProjGrid{T.grid.min_x, T.grid.min_y, T.grid.inv_w, T.grid.inv_h};
+        tab.push_back(R);
+    }
+    const size_t o_in_end = st.off;
+    const size_t o_idx = st.add(nitems * 4), o_dist = st.add(nitems * 4);
+    const int rr = st.alloc();
+    if (rr != ORB_OK) return rr;
+    std::memcpy(st.hi<ProjTarget>(o_tab), tab.data(), nused * sizeof(ProjTarget));
+    size_t item = 0, row = 0;
+    for (int k = 0; k < ntargets; k++) {
+        const orb_proj_target& T = targets[k];
+        if (T.nq == 0 || T.nt == 0) continue;
+        const ProjTarget& R = tab[row];
+        for (int i = 0; i < T.nq; i++) st.hi<int>(o_item)[item + i] = (int)row;
+        std::memcpy(st.hi<orb_proj_query>(o_pq) + item, T.q, (size_t)T.nq * sizeof(orb_proj_query));
+        std::memcpy(st.hi<uint8_t>(o_q) + item * 32, T.qdesc, (size_t)T.nq * 32);
+        std::memcpy(st.hi<uint8_t>(R.o_t), T.tdesc, (size_t)T.nt * 32);
+        std::memcpy(st.hi<uint8_t>(R.o_kps), T.kps_t, (size_t)T.nt * sizeof(orb_keypoint));
+        if (R.o_ur >= 0) std::memcpy(st.hi<uint8_t>(R.o_ur), T.t_uright, (size_t)T.nt * 4);
+        if (gate == ORB_PROJ_GATE_FUSE) std::memcpy(st.hi<uint8_t>(R.o_inv), T.inv_sigma2, (size_t)T.nlevels * 4);
+        std::memcpy(st.hi<uint8_t>(R.o_coff), T.grid.cell_off, (size_t)(ncells + 1) * 4);
+        if (T.grid.cell_off[ncells])
+            std::memcpy(st.hi<uint8_t>(R.o_cidx), T.grid.cell_idx, (size_t)T.grid.cell_off[ncells] * 4);
+        item += (size_t)T.nq;
+        row++;
+    }
+    hipError_t e;
+    if ((e = st.up(0, o_in_end)) != hipSuccess) return set_error("upload", e), ORB_ERR_HIP;
+    if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
+    e = launch_projection_best(gate, st.di<uint8_t>(0), st.di<ProjTarget>(o_tab), st.di<int>(o_item),
+                               st.di<orb_proj_query>(o_pq), st.di<uint8_t>(o_q), (int)nitems, st.h<int>(o_idx),
+                               st.h<int>(o_dist), c->stream);
+    if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 0, c->stream);
+    if (e != hipSuccess) return set_error("projection kernel", e), ORB_ERR_HIP;
+    // the kernel writes (idx, dist) straight into the pinned mirror (host-coherent memory): no D2H command
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("download", e), ORB_ERR_HIP;
+    item = 0;
+    for (int k = 0; k < ntargets; k++) {
+        const orb_proj_target& T = targets[k];
+        if (T.nq == 0 || T.nt == 0) continue;
+        std::memcpy(T.best_idx, st.h<int>(o_idx) + item, (size_t)T.nq * 4);
+        std::memcpy(T.best_dist, st.h<int>(o_dist) + item, (size_t)T.nq * 4);
+        item += (size_t)T.nq;
+    }
+    return ORB_OK;
+}
+
+int orb_project_best_host(int gate, const orb_proj_target* target, int query, int* best_idx, int* best_dist) {
+    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE)
+        return set_error("orb_project_best_host: unknown gate", hipSuccess), ORB_ERR_ARG;
+    if (!target || !best_idx || !best_dist || query < 0 || query >= target->nq)
+        return set_error("orb_project_best_host: bad arguments", hipSuccess), ORB_ERR_ARG;
+    orb_proj_target T = *target;   // (the target's own outputs are not this call's: not required, not touched)
+    T.best_idx = best_idx;
+    T.best_dist = best_dist;
+    if (const char* why = proj_target_fault(gate, T, query, query + 1))
+        return set_error((std::string("orb_project_best_host: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
+    proj_best_one(gate, T, T.q[query], T.qdesc + (size_t)query * 32, best_idx, best_dist);
+    return ORB_OK;
 }
 
 /* Frame::GetFeaturesInArea over the Frame grid (Frame.cc:378-392, 494-560) */

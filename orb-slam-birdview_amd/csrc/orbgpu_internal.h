@@ -298,6 +298,18 @@ hipError_t launch_projection_topk(const orb_proj_query* d_pq, const uint8_t* d_q
                                   const int* d_cell_idx, const ProjGrid& g, const int* d_thr, int k, int lanes,
                                   int* d_dist, int* d_idx, int* d_nvalid, hipStream_t stream);
 
+// The per-query searches over many targets (orb_project_best_batch: Fuse, SearchBySim3): the items (target, query)
+// of every target flattened into one launch.  Item i has its orb_proj_query d_pq[i], its descriptor d_q + 32 i and its
+// target's row d_item_tgt[i] of this table; a row's offsets are bytes from d_base (the call's staging area, each
+// region 256-byte aligned).  o_ur < 0: every train is monocular; o_inv is read with gate FUSE only.
+struct ProjTarget {
+    long long o_t, o_kps, o_ur, o_inv, o_coff, o_cidx;
+    ProjGrid g;
+};
+hipError_t launch_projection_best(int gate, const uint8_t* d_base, const ProjTarget* d_tab, const int* d_item_tgt,
+                                  const orb_proj_query* d_pq, const uint8_t* d_q, int nitems, int* d_idx, int* d_dist,
+                                  hipStream_t stream);
+
 // SearchForTriangulation's staged inputs, read by k_triangulation straight from the pinned mirror (over PCIe):
 // one record per query (item) holding everything its wave needs, and the candidate trains' records in
 // candidate order, so a wave's reads are two dependent round trips (its item record, then its candidates').

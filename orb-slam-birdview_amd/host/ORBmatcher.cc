@@ -350,7 +350,8 @@ int ORBmatcher::BirdviewMatch(const FrameData& F1, const FrameData& F2, std::vec
 
 /* ---------------- projection-gated searches (orb_search_by_projection) ---------------- */
 int ORBmatcher::projection_search(int mode, const FeatureSet& F, bool stereo, const std::vector<orb_proj_query>& q,
-                                  const std::vector<uint8_t>& qdesc, std::vector<int>& matches, const char* what) {
+                                  const std::vector<uint8_t>& qdesc, std::vector<int>& matches, const char* what,
+                                  int max_dist, int check_ori, const uint8_t* taken) {
     const int n = F.N(), nq = (int)q.size();
     matches.assign(n, -1);
     require(F.grid != nullptr, "projection search: Frame grid");
@@ -359,9 +360,10 @@ int ORBmatcher::projection_search(int mode, const FeatureSet& F, bool stereo, co
     const orb_frame_grid g = F.grid->Csr(off, idx);
     std::vector<int> out(std::max(n, 1), -1);
     int nmatches = 0;
-    check(orb_search_by_projection(matcher_ctx(), mode, mfNNratio, mbCheckOrientation, TH_HIGH, nq, nq ? q.data() : nullptr,
+    check(orb_search_by_projection(matcher_ctx(), mode, mfNNratio, check_ori < 0 ? (int)mbCheckOrientation : check_ori,
+                                   max_dist < 0 ? TH_HIGH : max_dist, nq, nq ? q.data() : nullptr,
                                    nq ? qdesc.data() : nullptr, n, desc_ptr(F), keys_ptr(F), stereo ? F.uRight : nullptr,
-                                   F.hasMapPoint, g, out.data(), &nmatches),
+                                   taken ? taken : F.hasMapPoint, g, out.data(), &nmatches),
           what);
     std::copy(out.begin(), out.begin() + n, matches.begin());
     return nmatches;
@@ -451,6 +453,163 @@ int ORBmatcher::SearchByProjectionBird(FrameData& F, const ProjectedBirdPoints& 
     }
     return projection_search(ORB_PROJ_RATIO_SAME_LEVEL, F, false, q, qdesc, vpMapPointMatchesBird,
                              "SearchByProjectionBird");
+}
+
+/* ---------------- the keyframe searches (orb_project_best_batch, orb_search_by_projection) ---------------- */
+namespace {
+// A target's marshalled arrays; the orb_proj_target points into them.
+struct TargetArrays {
+    std::vector<orb_proj_query> q;
+    std::vector<uint8_t> qdesc;
+    std::vector<int> off, idx, best_idx, best_dist;
+};
+orb_proj_query kf_query(const ProjectedKFPoint& p, float radius, int level_above, float angle) {
+    orb_proj_query q;
+    q.u = p.u;
+    q.v = p.v;
+    q.r = radius;
+    q.min_level = p.predictedLevel - 1;              // kpLevel<nPredictedLevel-1 || kpLevel>nPredictedLevel
+    q.max_level = p.predictedLevel + level_above;
+    q.ur = p.ur;
+    q.ur_tol = 0;
+    q.angle = angle;
+    q.blocks = 1;
+    return q;
+}
+orb_proj_target make_target(const KeyFrameData& kf, const std::vector<ProjectedKFPoint>& points, bool chi2Gate,
+                            TargetArrays& a) {
+    const size_t nq = points.size();
+    require(kf.grid != nullptr, "keyframe search: KeyFrame grid");
+    require(kf.n == 0 || (kf.keys && kf.descriptors), "keyframe search: KeyFrame keys/descriptors");
+    require(!chi2Gate || (kf.invLevelSigma2 && kf.nlevels > 0), "Fuse: mvInvLevelSigma2");
+    a.q.resize(nq);
+    a.qdesc.resize(nq * 32);
+    for (size_t i = 0; i < nq; i++) {
+        require(points[i].descriptor != nullptr, "keyframe search: map point descriptor");
+        a.q[i] = kf_query(points[i], points[i].radius, 0, 0);
+        memcpy(&a.qdesc[i * 32], points[i].descriptor, 32);
+    }
+    a.best_idx.assign(std::max<size_t>(nq, 1), -1);
+    a.best_dist.assign(std::max<size_t>(nq, 1), -1);
+    orb_proj_target t;
+    t.nq = (int)nq;
+    t.q = a.q.data();
+    t.qdesc = a.qdesc.data();
+    t.nt = kf.n;
+    t.tdesc = desc_ptr(kf);
+    t.kps_t = keys_ptr(kf);
+    t.t_uright = chi2Gate ? kf.uRight : nullptr;
+    t.inv_sigma2 = chi2Gate ? kf.invLevelSigma2 : nullptr;
+    t.nlevels = chi2Gate ? kf.nlevels : 0;
+    t.grid = kf.grid->Csr(a.off, a.idx);
+    t.best_idx = a.best_idx.data();
+    t.best_dist = a.best_dist.data();
+    return t;
+}
+}  // namespace
+
+void ORBmatcher::FuseSearch(const std::vector<FuseTarget>& targets, bool chi2Gate,
+                            std::vector<std::vector<FuseBest> >& best) {
+    const size_t nt = targets.size();
+    std::vector<TargetArrays> arrays(nt);
+    std::vector<orb_proj_target> T(nt);
+    for (size_t t = 0; t < nt; t++) T[t] = make_target(targets[t].kf, targets[t].points, chi2Gate, arrays[t]);
+    check(orb_project_best_batch(matcher_ctx(), chi2Gate ? ORB_PROJ_GATE_FUSE : ORB_PROJ_GATE_NONE, (int)nt,
+                                 nt ? T.data() : nullptr),
+          "FuseSearch");
+    best.assign(nt, std::vector<FuseBest>());
+    for (size_t t = 0; t < nt; t++) {
+        best[t].resize(targets[t].points.size());
+        for (size_t i = 0; i < best[t].size(); i++) best[t][i] = FuseBest{arrays[t].best_idx[i], arrays[t].best_dist[i]};
+    }
+}
+
+FuseBest ORBmatcher::FuseSearchOne(const FuseTarget& target, int point, const uint8_t* descriptor, bool chi2Gate) {
+    require(point >= 0 && point < (int)target.points.size() && descriptor, "FuseSearchOne: point");
+    ProjectedKFPoint p = target.points[point];
+    p.descriptor = descriptor;
+    TargetArrays a;
+    const orb_proj_target t = make_target(target.kf, std::vector<ProjectedKFPoint>(1, p), chi2Gate, a);
+    FuseBest b{-1, -1};
+    check(orb_project_best_host(chi2Gate ? ORB_PROJ_GATE_FUSE : ORB_PROJ_GATE_NONE, &t, 0, &b.idx, &b.dist),
+          "FuseSearchOne");
+    return b;
+}
+
+int ORBmatcher::SearchBySim3(const KeyFrameData& KF1, const KeyFrameData& KF2, const ProjectedSim3Points& points1in2,
+                             const ProjectedSim3Points& points2in1, std::vector<int>& vnMatch12) {
+    require(points1in2.index.size() == points1in2.points.size() && points2in1.index.size() == points2in1.points.size(),
+            "SearchBySim3: one index per point");
+    TargetArrays a[2];
+    orb_proj_target T[2] = {make_target(KF2, points1in2.points, false, a[0]),
+                            make_target(KF1, points2in1.points, false, a[1])};
+    check(orb_project_best_batch(matcher_ctx(), ORB_PROJ_GATE_NONE, 2, T), "SearchBySim3");
+    const int N1 = KF1.N(), N2 = KF2.N();
+    std::vector<int> vnMatch1(N1, -1), vnMatch2(N2, -1);                     // :1144-1145
+    for (size_t k = 0; k < points1in2.points.size(); k++) {
+        const int i1 = points1in2.index[k];
+        require(i1 >= 0 && i1 < N1, "SearchBySim3: point index");
+        if (a[0].best_idx[k] >= 0 && a[0].best_dist[k] <= TH_HIGH) vnMatch1[i1] = a[0].best_idx[k];   // :1221-1224
+    }
+    for (size_t k = 0; k < points2in1.points.size(); k++) {
+        const int i2 = points2in1.index[k];
+        require(i2 >= 0 && i2 < N2, "SearchBySim3: point index");
+        if (a[1].best_idx[k] >= 0 && a[1].best_dist[k] <= TH_HIGH) vnMatch2[i2] = a[1].best_idx[k];   // :1301-1304
+    }
+    vnMatch12.assign(N1, -1);
+    int nFound = 0;
+    for (int i1 = 0; i1 < N1; i1++) {                                        // :1310-1323
+        const int idx2 = vnMatch1[i1];
+        if (idx2 >= 0) {
+            const int idx1 = vnMatch2[idx2];
+            if (idx1 == i1) {
+                vnMatch12[i1] = idx2;
+                nFound++;
+            }
+        }
+    }
+    return nFound;
+}
+
+int ORBmatcher::SearchByProjection(KeyFrameData& KF, const ProjectedLoopPoints& vpPoints, const int th,
+                                   std::vector<int>& vpMatched) {
+    const size_t nq = vpPoints.points.size();
+    require((int)vpMatched.size() == KF.N(), "SearchByProjection(KF, Scw): vpMatched has one entry per feature");
+    require(nq == 0 || (KF.scaleFactors && KF.nlevels > 0), "SearchByProjection(KF, Scw): scale table");
+    std::vector<orb_proj_query> q(nq);
+    std::vector<uint8_t> qdesc(nq * 32), taken(std::max<size_t>(vpMatched.size(), 1), 0);
+    for (size_t i = 0; i < vpMatched.size(); i++) taken[i] = vpMatched[i] != -1;   // :375
+    for (size_t i = 0; i < nq; i++) {
+        const ProjectedKFPoint& p = vpPoints.points[i];
+        require(p.descriptor && p.predictedLevel >= 0 && p.predictedLevel < KF.nlevels, "SearchByProjection(KF, Scw): map point");
+        q[i] = kf_query(p, th * KF.scaleFactors[p.predictedLevel], 0, 0);   // :360, :380
+        memcpy(&qdesc[i * 32], p.descriptor, 32);
+    }
+    std::vector<int> res;
+    const int nmatches = projection_search(ORB_PROJ_BEST, KF, false, q, qdesc, res, "SearchByProjection(KF, Scw)", TH_LOW,
+                                           0, taken.data());
+    for (size_t i = 0; i < res.size(); i++)
+        if (res[i] >= 0) vpMatched[i] = res[i];                              // :396
+    return nmatches;
+}
+
+int ORBmatcher::SearchByProjection(FrameData& CurrentFrame, const ProjectedKeyFramePoints& vpPoints, const float th,
+                                   const int ORBdist, std::vector<int>& vpMapPointMatches) {
+    const size_t nq = vpPoints.points.size();
+    require(vpPoints.angle.size() == nq, "SearchByProjection(F, KF): one angle per point");
+    require(nq == 0 || (CurrentFrame.scaleFactors && CurrentFrame.nlevels > 0), "SearchByProjection(F, KF): scale table");
+    std::vector<orb_proj_query> q(nq);
+    std::vector<uint8_t> qdesc(nq * 32);
+    for (size_t i = 0; i < nq; i++) {
+        const ProjectedKFPoint& p = vpPoints.points[i];
+        require(p.descriptor && p.predictedLevel >= 0 && p.predictedLevel < CurrentFrame.nlevels,
+                "SearchByProjection(F, KF): map point");
+        q[i] = kf_query(p, th * CurrentFrame.scaleFactors[p.predictedLevel], 1, vpPoints.angle[i]);   // :1526-1528, :1562
+        memcpy(&qdesc[i * 32], p.descriptor, 32);
+    }
+    // the rotation cull of :1577-1596 is statement for statement that of :1448-1467, which BEST mode replays
+    return projection_search(ORB_PROJ_BEST, CurrentFrame, false, q, qdesc, vpMapPointMatches, "SearchByProjection(F, KF)",
+                             ORBdist);
 }
 
 std::vector<int> ComputeDistinctiveDescriptors(const std::vector<std::vector<const uint8_t*> >& observations) {

@@ -22,7 +22,7 @@
 #include "ORBextractor.h"
 
 // The matcher lives in ORB_SLAM2 like the reference's.  When integrated next to the reference's own
-// ORB_SLAM2::ORBmatcher (which keeps Fuse, SearchBySim3 and the keyframe forms of SearchByProjection), build with
+// ORB_SLAM2::ORBmatcher (which keeps SearchByMatchBird and the pose arithmetic of the projection searches), build with
 // -DORBGPU_MATCHER_NAMESPACE=orbgpu_host.
 #ifndef ORBGPU_MATCHER_NAMESPACE
 #define ORBGPU_MATCHER_NAMESPACE ORB_SLAM2
@@ -76,6 +76,7 @@ struct FeatureSet {
     const float* levelSigma2 = nullptr;               // mvLevelSigma2
     int nlevels = 0;                                  // mnScaleLevels (length of the two tables above)
     const FrameGrid* grid = nullptr;                  // mGrid / mGridBirdview
+    const float* invLevelSigma2 = nullptr;            // mvInvLevelSigma2 (Fuse's reprojection gate)
     int N() const { return n; }
 };
 // Tags standing for the reference's Frame& and KeyFrame* arguments (so the overloads keep the
@@ -116,6 +117,34 @@ struct ProjectedBirdPoints {   // SearchByProjectionBird(Frame& F, const vector<
         const uint8_t* descriptor;
     };
     std::vector<Point> points;
+};
+
+// The keyframe searches (Fuse, SearchBySim3, the keyframe forms of SearchByProjection).  The caller keeps the pose
+// arithmetic (Rcw*p3Dw+tcw, IsInImage, the distance and viewing-angle tests, PredictScale), leaves out the points the
+// reference skips before its search, and keeps each point's index.
+struct ProjectedKFPoint {
+    float u, v, ur;              // the projection; ur = u - bf*invz (read by Fuse's reprojection gate only)
+    int predictedLevel;          // pMP->PredictScale(dist3D, pKF)
+    float radius;                // th * pKF->mvScaleFactors[predictedLevel]
+    const uint8_t* descriptor;   // pMP->GetDescriptor(), 32 bytes
+};
+struct FuseTarget {              // one Fuse call: a target keyframe and the map points projected into it
+    KeyFrameData kf;             // keys (mvKeysUn), descriptors, grid; uRight and invLevelSigma2 with the chi2 gate
+    std::vector<ProjectedKFPoint> points;
+};
+struct FuseBest {                // bestIdx / bestDist of ORBmatcher.cc:901-949, before `bestDist<=TH_LOW`; -1 / -1: none
+    int idx, dist;
+};
+struct ProjectedSim3Points {     // SearchBySim3: one keyframe's map points projected into the other (:1150-1189),
+    std::vector<int> index;      //   without vbAlreadyMatched ones; index[k] = the point's feature in its own keyframe
+    std::vector<ProjectedKFPoint> points;
+};
+struct ProjectedLoopPoints {     // SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th): the points left after
+    std::vector<ProjectedKFPoint> points;   // :317-355
+};
+struct ProjectedKeyFramePoints { // SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist): pKF's map points
+    std::vector<ProjectedKFPoint> points;   // left after :1492-1521 ...
+    std::vector<float> angle;               // ... and pKF->mvKeysUn[i].angle of each
 };
 
 class ORBmatcher {
@@ -169,13 +198,36 @@ public:
     int SearchByProjectionBird(FrameData& F, const ProjectedBirdPoints& vpMapPointsBird, const float r,
                                std::vector<int>& vpMapPointMatchesBird);
 
+    // The inner searches of Fuse for many target keyframes in one GPU call: chi2Gate = true is Fuse(KeyFrame*, const
+    // vector<MapPoint*>&, th) (ORBmatcher.cc:823-975, LocalMapping::SearchInNeighbors), false is Fuse(KeyFrame*, Scw,
+    // ...) (:977-1100, LoopClosing::SearchAndFuse).  best[t][i] belongs to targets[t].points[i]; what follows the
+    // search (:952-971) is the caller's replay.
+    void FuseSearch(const std::vector<FuseTarget>& targets, bool chi2Gate, std::vector<std::vector<FuseBest> >& best);
+    // One point of one target on the CPU with another descriptor: a point whose descriptor changed during the replay.
+    FuseBest FuseSearchOne(const FuseTarget& target, int point, const uint8_t* descriptor, bool chi2Gate);
+    // ORBmatcher.cc:1102-1326: both directions in one GPU call, TH_HIGH and the agreement loop.  vnMatch12[i1] = the
+    // KF2 feature both directions agree on, else -1; returns nFound.
+    int SearchBySim3(const KeyFrameData& KF1, const KeyFrameData& KF2, const ProjectedSim3Points& points1in2,
+                     const ProjectedSim3Points& points2in1, std::vector<int>& vnMatch12);
+    // ORBmatcher.cc:290-403.  vpMatched: in, per feature != -1 <=> vpMatched[idx] != NULL; out, the features the call
+    // matched hold the index of their point.  Returns nmatches.
+    // The radius is th * KF.scaleFactors[predictedLevel] (:360; the points' own radius is not read).
+    int SearchByProjection(KeyFrameData& KF, const ProjectedLoopPoints& vpPoints, const int th,
+                           std::vector<int>& vpMatched);
+    // ORBmatcher.cc:1472-1599.  CurrentFrame.hasMapPoint[i2] = mvpMapPoints[i2] != NULL; the result as for the other
+    // Frame forms (-2: reset by the rotation cull).
+    int SearchByProjection(FrameData& CurrentFrame, const ProjectedKeyFramePoints& vpPoints, const float th,
+                           const int ORBdist, std::vector<int>& vpMapPointMatches);
+
     static const int TH_LOW;
     static const int TH_HIGH;
     static const int HISTO_LENGTH;
 
 protected:
     int projection_search(int mode, const FeatureSet& F, bool stereo, const std::vector<orb_proj_query>& q,
-                          const std::vector<uint8_t>& qdesc, std::vector<int>& matches, const char* what);
+                          const std::vector<uint8_t>& qdesc, std::vector<int>& matches, const char* what,
+                          int max_dist = -1 /* TH_HIGH */, int check_ori = -1 /* mbCheckOrientation */,
+                          const uint8_t* taken = nullptr /* F.hasMapPoint */);
     int window_match(bool level0_only, const FeatureSet& F1, const FeatureSet& F2, const std::vector<Point2f>* centres,
                      int windowSize, std::vector<int>& vnMatches12);
     float mfNNratio;

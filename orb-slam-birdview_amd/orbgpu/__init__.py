@@ -11,10 +11,12 @@ import ctypes
 import numpy as np
 
 from ._lib import (VARIANT_BLUR_HALFUP, VARIANT_DEFAULT, VARIANT_NO_FMA, VARIANT_RESIZE_GENERIC,
-                   VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, check, lib)
+                   VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, OrbProjTarget, check,
+                   lib)
 
 __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError", "device_count",
            "features_in_area", "frame_grid", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
+           "PROJ_GATE_NONE", "PROJ_GATE_FUSE", "proj_queries", "project_best_host",
            "compute_stereo_matches", "ORBVocabulary", "BirdORB", "cornerSubPix",
            "bird_footprint_mask", "VARIANT_DEFAULT", "VARIANT_TIE_REVERSE", "VARIANT_RESIZE_GENERIC",
            "VARIANT_BLUR_HALFUP", "VARIANT_NO_FMA"]
@@ -30,6 +32,7 @@ PROJ_QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("r", "<f4"), ("min_lev
                              ("ur", "<f4"), ("ur_tol", "<f4"), ("angle", "<f4"), ("blocks", "<i4")])
 assert PROJ_QUERY_DTYPE.itemsize == 36
 PROJ_BEST, PROJ_RATIO_SAME_LEVEL = 0, 1   # ORB_PROJ_*
+PROJ_GATE_NONE, PROJ_GATE_FUSE = 0, 1     # ORB_PROJ_GATE_*
 
 
 def _p(a):
@@ -307,6 +310,68 @@ def frame_grid(kps_un, min_x, max_x, min_y, max_y):
     return float(inv_w), float(inv_h), np.cumsum(off).astype(np.int32), order.astype(np.int32)
 
 
+def proj_queries(u, v, radius, level, ur=None, level_above=0, angle=None):
+    """PROJ_QUERY_DTYPE array of projected map points with predicted levels `level`: the window (u, v, radius), the
+    level range (level - 1, level + level_above), ur (Fuse's gate), angle (the rotation check); blocks = 1."""
+    level = np.asarray(level, np.int32)
+    q = np.zeros(len(level), PROJ_QUERY_DTYPE)
+    q["u"], q["v"], q["r"] = np.asarray(u, np.float32), np.asarray(v, np.float32), np.asarray(radius, np.float32)
+    q["min_level"], q["max_level"] = level - 1, level + int(level_above)
+    if ur is not None:
+        q["ur"] = np.asarray(ur, np.float32)
+    if angle is not None:
+        q["angle"] = np.asarray(angle, np.float32)
+    q["blocks"] = 1
+    return q
+
+
+class _ProjTargets:
+    """orb_proj_target array over a list of target dicts: q (PROJ_QUERY_DTYPE), qdesc, tdesc, kps_t, grid
+    (frame_grid(...)), and optionally min_xy ((mnMinX, mnMinY), default (0, 0)), t_uright (mvuRight), inv_sigma2
+    (mvInvLevelSigma2).  Holds the marshalled arrays alive and the per-target outputs (best_idx, best_dist)."""
+
+    def __init__(self, targets):
+        self.keep, self.out = [], []
+        self.arr = (OrbProjTarget * max(len(targets), 1))()
+        for k, t in enumerate(targets):
+            inv_w, inv_h, off, idx = t["grid"]
+            q = np.ascontiguousarray(t["q"], PROJ_QUERY_DTYPE)
+            qd = np.ascontiguousarray(t["qdesc"], np.uint8).reshape(-1, 32)
+            td = np.ascontiguousarray(t["tdesc"], np.uint8).reshape(-1, 32)
+            kt = np.ascontiguousarray(t["kps_t"], KP_DTYPE)
+            assert len(q) == len(qd) and len(td) == len(kt)
+            ur = None if t.get("t_uright") is None else np.ascontiguousarray(t["t_uright"], np.float32)
+            inv = None if t.get("inv_sigma2") is None else np.ascontiguousarray(t["inv_sigma2"], np.float32)
+            assert ur is None or len(ur) == len(kt)
+            off = np.ascontiguousarray(off, np.int32)
+            idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
+            mx, my = t.get("min_xy", (0.0, 0.0))
+            bi, bd = np.full(max(len(q), 1), -1, np.int32), np.full(max(len(q), 1), -1, np.int32)
+            g = OrbFrameGrid(float(mx), float(my), inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+            self.arr[k] = OrbProjTarget(len(q), _p(q), _p(qd), len(kt), _p(td), _p(kt), _p(ur), _p(inv),
+                                        0 if inv is None else len(inv), g, _p(bi), _p(bd))
+            self.keep.append((q, qd, td, kt, ur, inv, off, idx))
+            self.out.append((bi[:len(q)], bd[:len(q)]))
+
+
+def project_best_host(gate, target, query):
+    """orb_project_best_host: one query of one target (a dict as for ORBmatcher.project_best_batch) on the CPU, with
+    the arithmetic and the result of the batched GPU call; no context, no GPU.  Returns (best_idx, best_dist)."""
+    T = _ProjTargets([target])
+    bi, bd = ctypes.c_int(-1), ctypes.c_int(-1)
+    check(lib().orb_project_best_host(int(gate), ctypes.addressof(T.arr), int(query), ctypes.byref(bi),
+                                      ctypes.byref(bd)), "orb_project_best_host")
+    return bi.value, bd.value
+
+
+def _kf_target(kf, pts, level_above=0):
+    """A target dict from a keyframe dict (desc, kps, grid, and optionally min_xy, uright, inv_sigma2) and its
+    projected points (u, v, radius, level, desc, and optionally ur)."""
+    return dict(q=proj_queries(pts["u"], pts["v"], pts["radius"], pts["level"], pts.get("ur"), level_above),
+                qdesc=pts["desc"], tdesc=kf["desc"], kps_t=kf["kps"], grid=kf["grid"],
+                min_xy=kf.get("min_xy", (0.0, 0.0)), t_uright=kf.get("uright"), inv_sigma2=kf.get("inv_sigma2"))
+
+
 class ORBmatcher:
     """ORB_SLAM2::ORBmatcher's descriptor matchers (ORBmatcher.cc) on the GPU."""
 
@@ -572,6 +637,71 @@ class ORBmatcher:
         q["blocks"] = 1
         return self.search_by_projection(PROJ_RATIO_SAME_LEVEL, q, desc_mp, desc_bird, kps_bird, grid_bird, None,
                                          taken_bird)
+
+    project_best_host = staticmethod(project_best_host)
+
+    def project_best_batch(self, gate, targets):
+        """orb_project_best_batch: the per-query searches (Fuse, SearchBySim3) of many targets in one GPU call.
+        targets: dicts with q (PROJ_QUERY_DTYPE; proj_queries(...)), qdesc, tdesc, kps_t, grid (frame_grid(...)) and
+        optionally min_xy, t_uright, inv_sigma2 (gate PROJ_GATE_FUSE needs inv_sigma2).  Returns per target
+        (best_idx, best_dist): the train with the smallest distance (first in GetFeaturesInArea order on ties) among
+        the candidates that pass the level filter and the gate, -1 / -1 where none does."""
+        T = _ProjTargets(targets)
+        check(lib().orb_project_best_batch(self._ctx.h, int(gate), len(targets), ctypes.addressof(T.arr)),
+              "orb_project_best_batch")
+        return T.out
+
+    def Fuse(self, targets):
+        """The search of Fuse(KeyFrame* pKF, const vector<MapPoint*>&, th) (ORBmatcher.cc:823-975) for every target
+        keyframe of LocalMapping::SearchInNeighbors in one call.  targets: (kf, pts) pairs; kf = dict(desc
+        (mDescriptors), kps (mvKeysUn), grid, min_xy, uright (mvuRight), inv_sigma2 (mvInvLevelSigma2)); pts = the
+        points left after the tests of :846-885, dict(u, v, ur (:863-870), level (nPredictedLevel), radius (:890),
+        desc).  Returns per target (bestIdx, bestDist) per point; bestDist <= TH_LOW and the graph updates of
+        :952-971 are the caller's (INTEGRATION.md has the replay rule)."""
+        return self.project_best_batch(PROJ_GATE_FUSE, [_kf_target(kf, pts) for kf, pts in targets])
+
+    def Fuse_Scw(self, targets):
+        """The search of Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>&, th, vpReplacePoint)
+        (ORBmatcher.cc:977-1100) for every corrected keyframe of LoopClosing::SearchAndFuse in one call: as Fuse,
+        without the reprojection gate (ur, uright and inv_sigma2 are not read)."""
+        return self.project_best_batch(PROJ_GATE_NONE, [_kf_target(kf, pts) for kf, pts in targets])
+
+    def SearchBySim3(self, kf1, kf2, pts1in2, pts2in1):
+        """SearchBySim3 (ORBmatcher.cc:1102-1326).  pts1in2: KF1's map points projected into KF2 that pass
+        :1150-1183 and are not already matched: dict(index (i1), u, v, level, radius, desc); pts2in1 likewise with
+        index = i2.  Both directions are one GPU call.  Returns (nFound, vnMatch12): vnMatch12[i1] = the KF2
+        feature both directions agree on, else -1."""
+        (b1, d1), (b2, d2) = self.project_best_batch(PROJ_GATE_NONE, [_kf_target(kf2, pts1in2), _kf_target(kf1, pts2in1)])
+        n1, n2 = len(kf1["kps"]), len(kf2["kps"])
+        vn1, vn2 = np.full(n1, -1, np.int32), np.full(n2, -1, np.int32)
+        ok1, ok2 = (b1 >= 0) & (d1 <= TH_HIGH), (b2 >= 0) & (d2 <= TH_HIGH)      # :1221, :1301
+        vn1[np.asarray(pts1in2["index"], np.int64)[ok1]] = b1[ok1]
+        vn2[np.asarray(pts2in1["index"], np.int64)[ok2]] = b2[ok2]
+        out = np.full(n1, -1, np.int32)
+        for i1 in range(n1):                                                    # :1308-1323
+            idx2 = vn1[i1]
+            if idx2 >= 0 and vn2[idx2] == i1:
+                out[i1] = idx2
+        return int((out >= 0).sum()), out
+
+    def SearchByProjection_KF_Scw(self, pts, kf, matched):
+        """SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vpMatched, th)
+        (ORBmatcher.cc:290-403).  pts: the points left after :317-355: dict(u, v, level, radius, desc); kf: dict(desc,
+        kps, grid, min_xy); matched[idx] = vpMatched[idx] != NULL.  Returns (nmatches, match_kf): match_kf[idx] = the
+        point now matched to feature idx, -1 where the call matched none."""
+        q = proj_queries(pts["u"], pts["v"], pts["radius"], pts["level"])
+        m = ORBmatcher(self.mfNNratio, False)
+        return m.search_by_projection(PROJ_BEST, q, pts["desc"], kf["desc"], kf["kps"], kf["grid"], None, matched,
+                                      kf.get("min_xy", (0.0, 0.0)), max_dist=TH_LOW)
+
+    def SearchByProjection_F_KF(self, pts, frame, has_mp, orb_dist):
+        """SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th, ORBdist)
+        (ORBmatcher.cc:1472-1599).  pts: the keyframe's map points left after :1492-1521: dict(u, v, level, radius,
+        angle (pKF->mvKeysUn[i].angle), desc); frame: dict(desc, kps, grid, min_xy); has_mp[i2] =
+        CurrentFrame.mvpMapPoints[i2] != NULL.  Returns (nmatches, match_f) as search_by_projection does."""
+        q = proj_queries(pts["u"], pts["v"], pts["radius"], pts["level"], None, 1, pts["angle"])
+        return self.search_by_projection(PROJ_BEST, q, pts["desc"], frame["desc"], frame["kps"], frame["grid"], None,
+                                         has_mp, frame.get("min_xy", (0.0, 0.0)), max_dist=int(orb_dist))
 
     def SearchForInitialization(self, desc1, kps1, desc2, kps2, cand_off, cand_idx):
         """SearchForInitialization (ORBmatcher.cc:405-520); candidates = F2.GetFeaturesInArea per query.

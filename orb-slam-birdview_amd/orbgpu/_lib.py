@@ -51,6 +51,11 @@ class OrbFrameGrid(ctypes.Structure):
     _fields_ = [("min_x", cf), ("min_y", cf), ("inv_w", cf), ("inv_h", cf), ("cell_off", vp), ("cell_idx", vp)]
 
 
+class OrbProjTarget(ctypes.Structure):   # orb_proj_target
+    _fields_ = [("nq", ci), ("q", vp), ("qdesc", vp), ("nt", ci), ("tdesc", vp), ("kps_t", vp), ("t_uright", vp),
+                ("inv_sigma2", vp), ("nlevels", ci), ("grid", OrbFrameGrid), ("best_idx", vp), ("best_dist", vp)]
+
+
 # name -> (restype, argtypes); mirrors include/orbgpu.h
 SIGNATURES = {
     "orb_abi_version": (ci, []),
@@ -97,6 +102,8 @@ SIGNATURES = {
                                    ctypes.POINTER(ci)]),
     "orb_search_by_projection": (ci, [vp, ci, cf, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, OrbFrameGrid, vp,
                                       ctypes.POINTER(ci)]),
+    "orb_project_best_batch": (ci, [vp, ci, ci, vp]),
+    "orb_project_best_host": (ci, [ci, vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "orb_features_in_area": (ci, [ci, vp, cf, cf, cf, cf, cf, cf, cf, ci, ci, vp, ci]),
     "orb_compute_stereo_matches": (ci, [vp, vp, ci, vp, vp, ci, vp, vp, cf, cf, vp, vp, ctypes.POINTER(ci)]),
     "orb_stereo_batch_device": (ci, [vp, ci, cf, cf, vp, vp, vp]),
