@@ -414,6 +414,43 @@ int orb_search_by_projection(orb_ctx* ctx, int mode, float nnratio, int check_or
  *     angle = pKF->mvKeysUn[i].angle; t_taken[i2] = CurrentFrame.mvpMapPoints[i2] != NULL; mode BEST, the matcher's
  *     check_ori (the cull of :1577-1596 is that of :1448-1467), max_dist ORBdist. */
 
+/* int ORBmatcher::SearchByMatchBird(KeyFrame* pKF, Frame& F, vector<MapPointBird*>& vpMapPointMatchesBird, r)
+ *     ORBmatcher.cc:2000-2114 (Tracking::TrackReferenceKeyFrame, Tracking.cc:1046 / :1049).
+ * Queries = the keyframe's birdview keypoints k whose MapPointBird* is not NULL (the caller leaves the others out):
+ * q_id[i] = k (NULL: q_id[i] = i), q_xy[2 i], q_xy[2 i + 1] = pKF->mvKeysBird[k].pt, q_angle[i] = mvKeysBird[k].angle
+ * (NULL with check_ori == 0), qdesc = the map point's GetDescriptor() (32 B each); one radius r for all.  Trains =
+ * F.mvKeysBird / mDescriptorsBird with the birdview grid.  Candidates = GetFeaturesInAreaBirdview(x, y, r) without
+ * level arguments (Frame.cc:891-945), computed on the GPU in the grid's order and ranked there (k_projection_topk, as
+ * orb_search_by_projection); the acceptance is replayed on the host in query order, line for line:
+ *   a candidate with vMatchedDistanceBird[idx] <= dist is skipped (:2051); best and second best start at INT_MAX and
+ *   update on '<' only, with their octaves (bestLevel2 starts at -1; a distance of 256 is a legitimate second best);
+ *   accepted when bestDist <= max_dist && (bestLevel != bestLevel2 || bestDist < (float)bestDist2 * nnratio) (:2070-2072,
+ *   with (float)INT_MAX * nnratio when there is no second); then match_t[bestIdx] = q_id[i],
+ *   vMatchedDistanceBird[bestIdx] = bestDist, nmatches++ (never decremented when an earlier owner is overwritten), and
+ *   with check_ori bestIdx enters rotHist[bin(q_angle[i] - kps_t[bestIdx].angle)];
+ *   the cull (:2093-2111): every entry of a bin outside the three maxima sets its train to -2 and decrements nmatches
+ *   (no guard: a train entered twice counts twice, and is culled even if its last owner's bin is kept).
+ * match_t[t] (nt ints) = the last owning q_id, -1 = untouched, -2 = reset by the cull; *nmatches = the reference's
+ * return value (it can differ from the number of non-negative entries, in either direction).
+ * ORB_ERR_ARG before the context is touched or any output is written: a centre or r that is not finite, r < 0,
+ * max_dist outside [0, 256], NULL arrays with non-zero counts, a grid CSR orb_window_match_grid would refuse.
+ * nq == 0 or nt == 0: ORB_OK, *nmatches = 0, match_t all -1, no GPU work. */
+int orb_search_by_match_bird(orb_ctx* ctx, float nnratio, int check_ori, int max_dist, float r,
+                             int nq, const int* q_id, const float* q_xy, const float* q_angle, const uint8_t* qdesc,
+                             int nt, const uint8_t* tdesc, const orb_keypoint* kps_t, orb_frame_grid grid,
+                             int* match_t, int* nmatches);
+/* int ORBmatcher::SearchByMatchBird(Frame& CurrentFrame, const Frame& LastFrame, windowSize)   ORBmatcher.cc:1901-1921
+ *     (Tracking::TrackWithMotionModel, Tracking.cc:1241 / :1245).
+ * BirdviewMatch(LastFrame, CurrentFrame, vnMatches12, windowSize) (:1790-1899) = orb_window_match_grid with centres =
+ * NULL and level0_only = 0 over CurrentFrame's birdview grid, one GPU call; then on the host, for each k with
+ * vnMatches12[k] >= 0 and has_mp_last[k] != 0 (LastFrame.mvpMapPointsBird[k] != NULL): match_cur[vnMatches12[k]] = k.
+ * match_cur: n_cur ints, -1 = untouched; *nmatches = the carried points (not BirdviewMatch's return value).
+ * has_mp_last == NULL: no point carries a map point (0, all -1).  Arguments are checked as orb_window_match_grid's. */
+int orb_search_by_match_bird_frame(orb_ctx* ctx, float nnratio, int check_ori, float window,
+                                   int n_last, const uint8_t* desc_last, const orb_keypoint* kps_last,
+                                   const uint8_t* has_mp_last, int n_cur, const uint8_t* desc_cur,
+                                   const orb_keypoint* kps_cur, orb_frame_grid grid_cur, int* match_cur, int* nmatches);
+
 /* The searches that decide every projected point on its own (nothing like a taken set is read inside the search):
  * Fuse(KeyFrame*, const vector<MapPoint*>&, th) (ORBmatcher.cc:823-975, gate FUSE), Fuse(KeyFrame*, cv::Mat Scw, ...)
  * (:977-1100, gate NONE) and both directions of SearchBySim3 (:1102-1326, gate NONE).  Many targets (keyframes with

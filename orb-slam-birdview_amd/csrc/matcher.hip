@@ -1028,6 +1028,65 @@ int proj_replay(TopkSession& s, int mode, float nnratio, int check_ori, int max_
     return ORB_OK;
 }
 
+// SearchByMatchBird(KeyFrame*, Frame&, ...)'s acceptance (ORBmatcher.cc:2014-2111) from the top-k lists, in query
+// order.  Unlike proj_replay there is no taken set and no cut at 256: a candidate is skipped when
+// vMatchedDistanceBird[idx] <= dist (:2051), the running minima start at INT_MAX, a closer later query overwrites a
+// train without giving the count back, and the rotation histogram holds trains, the same one twice after a steal.
+// The (dist, slot) order of a list is the order of the reference's strict-'<' updates, so its first two admissible
+// entries are (bestDist, bestIdx, bestLevel) and (bestDist2, bestLevel2).  A list that cannot give both while the
+// window held more than K candidates is re-ranked on the GPU from that query on against the current table, as
+// window_replay does (the table only decreases, so an entry the kernel dropped stays inadmissible).
+int match_bird_replay(TopkSession& s, float nnratio, int check_ori, int max_dist, const int* q_id,
+                      const float* q_angle, const orb_keypoint* kps_t, int* match_t, int* nmatches_out) {
+    const int nq = s.nitems, nt = s.nt;
+    int st = s.run(0, nullptr);
+    if (st != ORB_OK) return st;
+    std::vector<int> vMatchedDistanceBird(nt, INT_MAX), matches(nt, -1);
+    std::vector<int> rotHist[HISTO_LENGTH];
+    int d[2], ti[2], found = 0;
+    auto scan = [&](int i) {
+        found = 0;
+        for (int j = 0; j < K && found < 2; j++) {
+            const int dj = s.dist[(size_t)i * K + j];
+            if (dj < 0) break;
+            const int t = s.idx[(size_t)i * K + j];
+            if (vMatchedDistanceBird[t] <= dj) continue;   // :2051
+            d[found] = dj;
+            ti[found++] = t;
+        }
+        return found == 2 || s.nvalid[i] <= K;
+    };
+    int nmatches = 0;
+    for (int i = 0; i < nq; i++) {
+        if (!scan(i)) {
+            if ((st = s.run(i, vMatchedDistanceBird.data())) != ORB_OK) return st;
+            scan(i);
+        }
+        if (found == 0) continue;   // :2025, or every candidate skipped: bestDist stays INT_MAX
+        const int bestDist = d[0], bestIdx = ti[0], bestLevel = kps_t[bestIdx].octave;
+        const int bestDist2 = found == 2 ? d[1] : INT_MAX, bestLevel2 = found == 2 ? kps_t[ti[1]].octave : -1;
+        if (bestDist <= max_dist) {                                                      // :2070
+            if (bestLevel != bestLevel2 || bestDist < (float)bestDist2 * nnratio) {      // :2072
+                matches[bestIdx] = q_id ? q_id[i] : i;
+                vMatchedDistanceBird[bestIdx] = bestDist;
+                if (check_ori) rotHist[rot_bin(q_angle[i], kps_t[bestIdx].angle)].push_back(bestIdx);
+                nmatches++;
+            }
+        }
+    }
+    if (check_ori) {   // :2093-2111, no guard
+        int i1 = -1, i2 = -1, i3 = -1;
+        three_maxima(rotHist, i1, i2, i3);
+        for (int b = 0; b < HISTO_LENGTH; b++) {
+            if (b == i1 || b == i2 || b == i3) continue;
+            for (int t : rotHist[b]) { matches[t] = -2; nmatches--; }
+        }
+    }
+    std::memcpy(match_t, matches.data(), (size_t)nt * sizeof(int));
+    if (nmatches_out) *nmatches_out = nmatches;
+    return ORB_OK;
+}
+
 // What is wrong with a target of orb_project_best_batch for its queries [q0, q1), or NULL.  The kernel indexes
 // inv_sigma2 by the train's octave and the trains by the grid's cell_idx, so both are checked here.
 const char* proj_target_fault(int gate, const orb_proj_target& T, int q0, int q1) {
@@ -1186,6 +1245,76 @@ int orb_search_by_projection(orb_ctx* h, int mode, float nnratio, int check_ori,
     const int st = s.setup_proj(nq, q, qdesc, nt, tdesc, kps_t, t_uright, grid, lanes);
     if (st != ORB_OK) return st;
     return proj_replay(s, mode, nnratio, check_ori, max_dist, q, kps_t, t_taken, match_t, nmatches_out);
+}
+
+/* SearchByMatchBird(KeyFrame*, Frame&, vector<MapPointBird*>&, r) (:2000-2114): the grid walk and the ranking are
+ * orb_search_by_projection's (k_projection_topk over the birdview grid, levels (-1, -1), no stereo gate), the
+ * acceptance is match_bird_replay. */
+int orb_search_by_match_bird(orb_ctx* h, float nnratio, int check_ori, int max_dist, float r, int nq, const int* q_id,
+                             const float* q_xy, const float* q_angle, const uint8_t* qdesc, int nt,
+                             const uint8_t* tdesc, const orb_keypoint* kps_t, orb_frame_grid grid, int* match_t,
+                             int* nmatches_out) {
+    // the arguments are checked before the context: nothing malformed reaches the device, no output is written
+    if (max_dist < 0 || max_dist > 256)
+        return set_error("orb_search_by_match_bird: max_dist outside [0, 256]", hipSuccess), ORB_ERR_ARG;
+    if (!std::isfinite(r) || r < 0)
+        return set_error("orb_search_by_match_bird: radius not finite or negative", hipSuccess), ORB_ERR_ARG;
+    if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q_xy || !qdesc || (check_ori && !q_angle))) ||
+        (nt && (!tdesc || !kps_t)) || !grid.cell_off || (grid.cell_off[64 * 48] && !grid.cell_idx))
+        return set_error("orb_search_by_match_bird: bad arguments", hipSuccess), ORB_ERR_ARG;
+    for (int i = 0; i < nq; i++) {
+        if (!std::isfinite(q_xy[2 * i]) || !std::isfinite(q_xy[2 * i + 1]))
+            return set_error("orb_search_by_match_bird: query centre not finite", hipSuccess), ORB_ERR_ARG;
+        if (q_id && q_id[i] < 0)   // (match_t keeps the negative values for "untouched" and "culled")
+            return set_error("orb_search_by_match_bird: negative query id", hipSuccess), ORB_ERR_ARG;
+    }
+    if (const char* why = grid_csr_fault(grid, nt))
+        return set_error((std::string("orb_search_by_match_bird: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    CTX_GUARD(c);
+    for (int t = 0; t < nt; t++) match_t[t] = -1;
+    if (nmatches_out) *nmatches_out = 0;
+    if (nq == 0 || nt == 0) return ORB_OK;
+    std::vector<orb_proj_query> q(nq);
+    for (int i = 0; i < nq; i++)   // GetFeaturesInAreaBirdview(pt.x, pt.y, r): the default levels (:2023)
+        q[i] = orb_proj_query{q_xy[2 * i], q_xy[2 * i + 1], r, -1, -1, 0.0f, 0.0f, 0.0f, 0};
+    TopkSession s{c};
+    const int st = s.setup_proj(nq, q.data(), qdesc, nt, tdesc, kps_t, nullptr, grid, 64);
+    if (st != ORB_OK) return st;
+    return match_bird_replay(s, nnratio, check_ori, max_dist, q_id, q_angle, kps_t, match_t, nmatches_out);
+}
+
+/* SearchByMatchBird(Frame& CurrentFrame, const Frame& LastFrame, windowSize) (:1901-1921): BirdviewMatch(LastFrame,
+ * CurrentFrame, ...) through orb_window_match_grid's path, then the carry-over of mvpMapPointsBird on the host. */
+int orb_search_by_match_bird_frame(orb_ctx* h, float nnratio, int check_ori, float window, int n_last,
+                                   const uint8_t* desc_last, const orb_keypoint* kps_last, const uint8_t* has_mp_last,
+                                   int n_cur, const uint8_t* desc_cur, const orb_keypoint* kps_cur,
+                                   orb_frame_grid grid_cur, int* match_cur, int* nmatches_out) {
+    if (n_last < 0 || n_cur < 0 || (n_cur && !match_cur) || (n_last && (!desc_last || !kps_last)) ||
+        (n_cur && (!desc_cur || !kps_cur)) || !grid_cur.cell_off || (grid_cur.cell_off[64 * 48] && !grid_cur.cell_idx))
+        return set_error("orb_search_by_match_bird_frame: bad arguments", hipSuccess), ORB_ERR_ARG;
+    if (const char* why = grid_csr_fault(grid_cur, n_cur))
+        return set_error((std::string("orb_search_by_match_bird_frame: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    CTX_GUARD(c);
+    std::vector<int> vnMatches12((size_t)std::max(n_last, 1), -1);
+    if (has_mp_last && n_last > 0 && n_cur > 0) {   // (without map points nothing is carried whatever matches)
+        const int st = orb_window_match_grid(h, nnratio, check_ori, 0, n_last, desc_last, kps_last, nullptr, window,
+                                             n_cur, desc_cur, kps_cur, grid_cur, vnMatches12.data(), nullptr);
+        if (st != ORB_OK) return st;
+    }
+    int nmatches = 0;
+    for (int t = 0; t < n_cur; t++) match_cur[t] = -1;
+    for (int k = 0; k < n_last && has_mp_last; k++) {   // :1907-1918
+        const int idx2 = vnMatches12[k];
+        if (idx2 < 0) continue;
+        if (has_mp_last[k]) {
+            match_cur[idx2] = k;
+            nmatches++;
+        }
+    }
+    if (nmatches_out) *nmatches_out = nmatches;
+    return ORB_OK;
 }
 
 /* Fuse (both overloads) and SearchBySim3's two directions: per (target, query) the first minimum of the descriptor

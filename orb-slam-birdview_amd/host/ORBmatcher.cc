@@ -455,6 +455,56 @@ int ORBmatcher::SearchByProjectionBird(FrameData& F, const ProjectedBirdPoints& 
                              "SearchByProjectionBird");
 }
 
+/* ---------------- SearchByMatchBird (orb_search_by_match_bird, orb_search_by_match_bird_frame) ---------------- */
+int ORBmatcher::SearchByMatchBird(const KeyFrameBirdPoints& KF, FrameData& F, std::vector<int>& vpMapPointMatchesBird,
+                                  const float r) {
+    const int n = F.N(), nq = (int)KF.points.size();
+    vpMapPointMatchesBird.assign(n, -1);   // :2004 vector<MapPointBird*>(F.mvKeysBird.size(), NULL)
+    require(F.grid != nullptr, "SearchByMatchBird: Frame grid");
+    require(n == 0 || (F.keys && F.descriptors), "SearchByMatchBird: Frame keys/descriptors");
+    std::vector<int> id(nq);
+    std::vector<float> xy(2 * (size_t)nq), angle(nq);
+    std::vector<uint8_t> qdesc((size_t)nq * 32);
+    for (int i = 0; i < nq; i++) {
+        const KeyFrameBirdPoints::Point& p = KF.points[i];
+        require(p.descriptor != nullptr && p.index >= 0, "SearchByMatchBird: keyframe point");
+        id[i] = p.index;
+        xy[2 * i] = p.x;
+        xy[2 * i + 1] = p.y;
+        angle[i] = p.angle;
+        memcpy(&qdesc[(size_t)i * 32], p.descriptor, 32);
+    }
+    std::vector<int> off, idx;
+    const orb_frame_grid g = F.grid->Csr(off, idx);
+    std::vector<int> out(std::max(n, 1), -1);
+    int nmatches = 0;
+    check(orb_search_by_match_bird(matcher_ctx(), mfNNratio, mbCheckOrientation, TH_HIGH, r, nq, nq ? id.data() : nullptr,
+                                   nq ? xy.data() : nullptr, nq ? angle.data() : nullptr, nq ? qdesc.data() : nullptr, n,
+                                   desc_ptr(F), keys_ptr(F), g, out.data(), &nmatches),
+          "SearchByMatchBird(KF, F)");
+    std::copy(out.begin(), out.begin() + n, vpMapPointMatchesBird.begin());
+    return nmatches;
+}
+
+int ORBmatcher::SearchByMatchBird(FrameData& CurrentFrame, const FrameData& LastFrame, const int windowSize,
+                                  std::vector<int>& vpMapPointsBird) {
+    const int nc = CurrentFrame.N(), nl = LastFrame.N();
+    vpMapPointsBird.assign(nc, -1);
+    require(CurrentFrame.grid != nullptr, "SearchByMatchBird: CurrentFrame grid");
+    require(nc == 0 || (CurrentFrame.keys && CurrentFrame.descriptors), "SearchByMatchBird: CurrentFrame keys/descriptors");
+    require(nl == 0 || (LastFrame.keys && LastFrame.descriptors), "SearchByMatchBird: LastFrame keys/descriptors");
+    std::vector<int> off, idx;
+    const orb_frame_grid g = CurrentFrame.grid->Csr(off, idx);
+    std::vector<int> out(std::max(nc, 1), -1);
+    int nmatches = 0;
+    check(orb_search_by_match_bird_frame(matcher_ctx(), mfNNratio, mbCheckOrientation, (float)windowSize, nl,
+                                         desc_ptr(LastFrame), keys_ptr(LastFrame), LastFrame.hasMapPoint, nc,
+                                         desc_ptr(CurrentFrame), keys_ptr(CurrentFrame), g, out.data(), &nmatches),
+          "SearchByMatchBird(CurrentFrame, LastFrame)");
+    std::copy(out.begin(), out.begin() + nc, vpMapPointsBird.begin());
+    return nmatches;
+}
+
 /* ---------------- the keyframe searches (orb_project_best_batch, orb_search_by_projection) ---------------- */
 namespace {
 // A target's marshalled arrays; the orb_proj_target points into them.

@@ -22,7 +22,7 @@
 #include "ORBextractor.h"
 
 // The matcher lives in ORB_SLAM2 like the reference's.  When integrated next to the reference's own
-// ORB_SLAM2::ORBmatcher (which keeps SearchByMatchBird and the pose arithmetic of the projection searches), build with
+// ORB_SLAM2::ORBmatcher (which keeps the pose arithmetic of the projection searches), build with
 // -DORBGPU_MATCHER_NAMESPACE=orbgpu_host.
 #ifndef ORBGPU_MATCHER_NAMESPACE
 #define ORBGPU_MATCHER_NAMESPACE ORB_SLAM2
@@ -119,6 +119,15 @@ struct ProjectedBirdPoints {   // SearchByProjectionBird(Frame& F, const vector<
     std::vector<Point> points;
 };
 
+struct KeyFrameBirdPoints {    // SearchByMatchBird(KeyFrame* pKF, Frame& F, vector<MapPointBird*>&, r)
+    struct Point {             // a birdview keypoint k of pKF with GetMapPointMatchesBird()[k] != NULL (:2016-2018)
+        int index;             // k: what the result vector holds for the Frame feature this point is matched to
+        float x, y, angle;     // pKF->mvKeysBird[k].pt and .angle (:2020-2021, :2079)
+        const uint8_t* descriptor;   // pMPBird->GetDescriptor(), 32 bytes
+    };
+    std::vector<Point> points; // in ascending k, the order of the reference's loop
+};
+
 // The keyframe searches (Fuse, SearchBySim3, the keyframe forms of SearchByProjection).  The caller keeps the pose
 // arithmetic (Rcw*p3Dw+tcw, IsInImage, the distance and viewing-angle tests, PredictScale), leaves out the points the
 // reference skips before its search, and keeps each point's index.
@@ -197,6 +206,20 @@ public:
     // hasMapPoint (mvpMapPointsBird[i] && Observations() > 0).
     int SearchByProjectionBird(FrameData& F, const ProjectedBirdPoints& vpMapPointsBird, const float r,
                                std::vector<int>& vpMapPointMatchesBird);
+
+    // ORBmatcher.cc:2000-2114.  F: keys (mvKeysBird), descriptors (mDescriptorsBird), grid (FrameGrid::Birdview).
+    // vpMapPointMatchesBird (sized to F.N()): per Frame feature the `index` of the keyframe point whose MapPointBird
+    // the reference leaves there, -1 = none, -2 = reset to NULL by the rotation cull.  The return value is the
+    // reference's nmatches (steals count twice, culled double entries are taken off twice).  TrackReferenceKeyFrame's
+    // retry with the larger radius (Tracking.cc:1046 / :1049) is a second call.
+    int SearchByMatchBird(const KeyFrameBirdPoints& KF, FrameData& F, std::vector<int>& vpMapPointMatchesBird,
+                          const float r);
+    // ORBmatcher.cc:1901-1921.  LastFrame: keys (mvKeysBird), descriptors, hasMapPoint (mvpMapPointsBird[k] != NULL;
+    // NULL: none); CurrentFrame: keys, descriptors, grid (FrameGrid::Birdview).  vpMapPointsBird (sized to
+    // CurrentFrame.N()): per CurrentFrame feature the LastFrame feature whose MapPointBird the reference writes into
+    // CurrentFrame.mvpMapPointsBird there, -1 where it leaves the slot as it is.  Returns the points carried over.
+    int SearchByMatchBird(FrameData& CurrentFrame, const FrameData& LastFrame, const int windowSize,
+                          std::vector<int>& vpMapPointsBird);
 
     // The inner searches of Fuse for many target keyframes in one GPU call: chi2Gate = true is Fuse(KeyFrame*, const
     // vector<MapPoint*>&, th) (ORBmatcher.cc:823-975, LocalMapping::SearchInNeighbors), false is Fuse(KeyFrame*, Scw,

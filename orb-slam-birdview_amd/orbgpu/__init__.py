@@ -638,6 +638,54 @@ class ORBmatcher:
         return self.search_by_projection(PROJ_RATIO_SAME_LEVEL, q, desc_mp, desc_bird, kps_bird, grid_bird, None,
                                          taken_bird)
 
+    def SearchByMatchBird(self, index, pt_x, pt_y, angle, desc_mp, r, desc_bird, kps_bird, grid_bird,
+                          max_dist=TH_HIGH):
+        """SearchByMatchBird(KeyFrame* pKF, Frame& F, vector<MapPointBird*>&, r) (ORBmatcher.cc:2000-2114).  Per
+        birdview keypoint k of the keyframe with a MapPointBird (the caller leaves the others out): index = k,
+        pKF->mvKeysBird[k].pt and .angle, the map point's descriptor; the Frame's mDescriptorsBird, mvKeysBird and
+        birdview grid.  Returns (nmatches, match_bird): match_bird[t] = the k whose map point feature t now holds,
+        -1 = untouched, -2 = reset by the rotation cull; nmatches is the reference's return value."""
+        inv_w, inv_h, off, idx = grid_bird
+        ids = np.ascontiguousarray(index, np.int32)
+        xy = np.ascontiguousarray(np.stack([np.asarray(pt_x, np.float32), np.asarray(pt_y, np.float32)], 1))
+        ang = np.ascontiguousarray(angle, np.float32)
+        qd = np.ascontiguousarray(desc_mp, np.uint8).reshape(-1, 32)
+        td = np.ascontiguousarray(desc_bird, np.uint8).reshape(-1, 32)
+        kt = np.ascontiguousarray(kps_bird, KP_DTYPE)
+        assert len(ids) == len(xy) == len(ang) == len(qd) and len(td) == len(kt)
+        off = np.ascontiguousarray(off, np.int32)
+        idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
+        g = OrbFrameGrid(0.0, 0.0, inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+        out = np.full(max(len(kt), 1), -1, np.int32)
+        nm = ctypes.c_int()
+        check(lib().orb_search_by_match_bird(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation), int(max_dist),
+                                             float(r), len(qd), _p(ids), _p(xy), _p(ang), _p(qd), len(kt), _p(td),
+                                             _p(kt), g, _p(out), ctypes.byref(nm)), "orb_search_by_match_bird")
+        return nm.value, out[:len(kt)]
+
+    def SearchByMatchBirdFrame(self, desc_last, kps_last, has_mp_last, desc_cur, kps_cur, grid_cur, windowSize):
+        """SearchByMatchBird(Frame& CurrentFrame, const Frame& LastFrame, windowSize) (ORBmatcher.cc:1901-1921):
+        BirdviewMatch(LastFrame, CurrentFrame) over CurrentFrame's birdview grid, then the carry-over of
+        LastFrame.mvpMapPointsBird.  has_mp_last[k] = mvpMapPointsBird[k] != NULL (None: none).  Returns (nmatches,
+        match_cur): match_cur[i] = the LastFrame feature whose map point CurrentFrame feature i receives, else -1."""
+        inv_w, inv_h, off, idx = grid_cur
+        dl = np.ascontiguousarray(desc_last, np.uint8).reshape(-1, 32)
+        kl = np.ascontiguousarray(kps_last, KP_DTYPE)
+        dc = np.ascontiguousarray(desc_cur, np.uint8).reshape(-1, 32)
+        kc = np.ascontiguousarray(kps_cur, KP_DTYPE)
+        mp = None if has_mp_last is None else np.ascontiguousarray(has_mp_last, np.uint8)
+        assert len(dl) == len(kl) and len(dc) == len(kc) and (mp is None or len(mp) == len(kl))
+        off = np.ascontiguousarray(off, np.int32)
+        idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
+        g = OrbFrameGrid(0.0, 0.0, inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+        out = np.full(max(len(kc), 1), -1, np.int32)
+        nm = ctypes.c_int()
+        check(lib().orb_search_by_match_bird_frame(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation),
+                                                   float(windowSize), len(kl), _p(dl), _p(kl), _p(mp), len(kc),
+                                                   _p(dc), _p(kc), g, _p(out), ctypes.byref(nm)),
+              "orb_search_by_match_bird_frame")
+        return nm.value, out[:len(kc)]
+
     project_best_host = staticmethod(project_best_host)
 
     def project_best_batch(self, gate, targets):

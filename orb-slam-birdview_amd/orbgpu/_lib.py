@@ -102,6 +102,10 @@ SIGNATURES = {
                                    ctypes.POINTER(ci)]),
     "orb_search_by_projection": (ci, [vp, ci, cf, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, OrbFrameGrid, vp,
                                       ctypes.POINTER(ci)]),
+    "orb_search_by_match_bird": (ci, [vp, cf, ci, ci, cf, ci, vp, vp, vp, vp, ci, vp, vp, OrbFrameGrid, vp,
+                                      ctypes.POINTER(ci)]),
+    "orb_search_by_match_bird_frame": (ci, [vp, cf, ci, cf, ci, vp, vp, vp, ci, vp, vp, OrbFrameGrid, vp,
+                                            ctypes.POINTER(ci)]),
     "orb_project_best_batch": (ci, [vp, ci, ci, vp]),
     "orb_project_best_host": (ci, [ci, vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "orb_features_in_area": (ci, [ci, vp, cf, cf, cf, cf, cf, cf, cf, ci, ci, vp, ci]),

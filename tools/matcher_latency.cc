@@ -18,11 +18,19 @@
 // including the per-keypoint GetFeaturesInArea queries on the frame's grid, as the reference loop
 // makes them.  Every GPU output is checked equal to the oracle's before anything is timed.
 //
-// usage: matcher_latency <frames.raw> <w> <h> <nfeatures> <vocab.bin> <reps> [cpu_reps]
+//   SearchByMatchBird (both forms)       ORBmatcher(0.99, true)  Tracking::TrackReferenceKeyFrame, Tracking.cc:1046 (r = 15), and
+//     TrackWithMotionModel, :1241 (window 15): only with a trailing `bird` argument, on the two frames' features
+//     standing for the birdview stream's (run it at 1280x720 / 2000 features, the stream's size); GPU = the C-ABI
+//     calls the host mirror makes (orb_search_by_match_bird, orb_search_by_match_bird_frame), CPU = the reference
+//     loops (ORBmatcher.cc:1790-1921, :2000-2114) written out below over the Frame's own grid, single thread.
+//
+// usage: matcher_latency <frames.raw> <w> <h> <nfeatures> <vocab.bin> <reps> [cpu_reps [bird]]
 // Prints one JSON line.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <limits.h>
 
 #include <algorithm>
 #include <chrono>
@@ -34,6 +42,7 @@
 #include "../orb-slam-birdview_amd/host/ORBVocabulary.h"
 #include "../orb-slam-birdview_amd/host/ORBextractor.h"
 #include "../orb-slam-birdview_amd/host/Stereo.h"
+#include "../include/orbgpu.h"
 #include "ORBmatcher.h"   // tests/cpp/slam_api: the reference's declaration, modelled
 
 using namespace ORB_SLAM2;
@@ -394,6 +403,138 @@ int main(int argc, char** argv) {
         oracle_destroy(oL);
         oracle_destroy(oR);
         emit("ComputeStereoMatches", g, c, nm, onm, ok);
+    }
+    // ---- SearchByMatchBird, both forms: frame 0's features as the keyframe's / last frame's birdview keypoints (70 %
+    // of them with a MapPointBird, whose descriptor is the keypoint's), frame 1's as the current frame's
+    if (argc > 8 && !strcmp(argv[8], "bird")) {
+        orb_params prm;   // a matcher context, as the host mirror creates it
+        memset(&prm, 0, sizeof prm);
+        prm.nfeatures = 1000;
+        prm.scaleFactor = 1.2f;
+        prm.nlevels = 8;
+        prm.iniThFAST = 20;
+        prm.minThFAST = 7;
+        prm.device = getenv("ORBGPU_DEVICE") ? atoi(getenv("ORBGPU_DEVICE")) : 0;
+        int err = 0;
+        orb_ctx* ctx = orb_create(&prm, &err);
+        if (!ctx) {
+            fprintf(stderr, "bird leg: no context (%d)\n", err);
+            return 2;
+        }
+        const Frame& Fc = F[1];
+        std::vector<int> off(FRAME_GRID_COLS * FRAME_GRID_ROWS + 1, 0), idx;
+        for (int ix = 0; ix < FRAME_GRID_COLS; ix++)
+            for (int iy = 0; iy < FRAME_GRID_ROWS; iy++) {
+                for (size_t j : Fc.mGrid[ix][iy]) idx.push_back((int)j);
+                off[ix * FRAME_GRID_ROWS + iy + 1] = (int)idx.size();
+            }
+        if (idx.empty()) idx.push_back(0);
+        const orb_frame_grid g = {0.f, 0.f, Fc.mfGridElementWidthInv, Fc.mfGridElementHeightInv, off.data(), idx.data()};
+        std::vector<uint8_t> has(nA + 1, 0);
+        std::vector<int> qid;
+        std::vector<float> qxy, qang;
+        std::vector<uint8_t> qd;
+        uint32_t s = 77u;
+        for (int k = 0; k < nA; k++) {
+            if (lcg(s) % 10 >= 7) continue;
+            has[k] = 1;
+            qid.push_back(k);
+            qxy.push_back(fe[0].kps[k].pt.x);
+            qxy.push_back(fe[0].kps[k].pt.y);
+            qang.push_back(fe[0].kps[k].angle);
+            qd.insert(qd.end(), fe[0].desc.data + (size_t)k * 32, fe[0].desc.data + (size_t)k * 32 + 32);
+        }
+        const int nq = (int)qid.size();
+        const float nnr = 0.99f, r = 15.f;
+        const orb_keypoint* kA = reinterpret_cast<const orb_keypoint*>(fe[0].kps.data());
+        const orb_keypoint* kB = reinterpret_cast<const orb_keypoint*>(fe[1].kps.data());
+        std::vector<int> gm(nB + 1, -1), cm(nB + 1, -1);
+        int gn = 0;
+        auto gpu_kf = [&] {
+            return orb_search_by_match_bird(ctx, nnr, 1, 100, r, nq, qid.data(), qxy.data(), qang.data(), qd.data(), nB,
+                                            fe[1].desc.data, kB, g, gm.data(), &gn);
+        };
+        auto cpu_kf = [&] {   // ORBmatcher.cc:2000-2114
+            std::fill(cm.begin(), cm.end(), -1);
+            std::vector<int> vMatchedDistanceBird(nB, INT_MAX), hist[30];
+            int nmatches = 0;
+            for (int i = 0; i < nq; i++) {
+                const float x = qxy[2 * i], y = qxy[2 * i + 1];
+                const std::vector<size_t> vIndices = Fc.GetFeaturesInArea(x, y, r);
+                if (vIndices.empty()) continue;
+                int bestDist = INT_MAX, bestLevel = -1, bestDist2 = INT_MAX, bestLevel2 = -1, bestIdx = -1;
+                for (size_t id : vIndices) {
+                    const int dist = oracle_descriptor_distance(&qd[(size_t)i * 32], fe[1].desc.data + id * 32);
+                    if (vMatchedDistanceBird[id] <= dist) continue;
+                    if (dist < bestDist) {
+                        bestDist2 = bestDist;
+                        bestDist = dist;
+                        bestLevel2 = bestLevel;
+                        bestLevel = fe[1].kps[id].octave;
+                        bestIdx = (int)id;
+                    } else if (dist < bestDist2) {
+                        bestLevel2 = fe[1].kps[id].octave;
+                        bestDist2 = dist;
+                    }
+                }
+                if (bestDist <= 100 && (bestLevel != bestLevel2 || bestDist < (float)bestDist2 * nnr)) {
+                    cm[bestIdx] = qid[i];
+                    vMatchedDistanceBird[bestIdx] = bestDist;
+                    hist[oracle_rot_bin(qang[i], fe[1].kps[bestIdx].angle)].push_back(bestIdx);
+                    nmatches++;
+                }
+            }
+            int sizes[30], i1 = -1, i2 = -1, i3 = -1;
+            for (int b = 0; b < 30; b++) sizes[b] = (int)hist[b].size();
+            oracle_three_maxima(sizes, 30, &i1, &i2, &i3);
+            for (int b = 0; b < 30; b++) {
+                if (b == i1 || b == i2 || b == i3) continue;
+                for (int t : hist[b]) {
+                    cm[t] = -2;
+                    nmatches--;
+                }
+            }
+            return nmatches;
+        };
+        if (gpu_kf() != ORB_OK) return fprintf(stderr, "orb_search_by_match_bird: %s\n", orb_last_error()), 2;
+        int cn = cpu_kf();
+        bool ok = gn == cn && std::equal(gm.begin(), gm.begin() + nB, cm.begin());
+        double gt = median_us([&] { gpu_kf(); }, reps), ct = median_us([&] { cpu_kf(); }, cpu_reps);
+        emit("SearchByMatchBird_KF_F", gt, ct, gn, cn, ok);
+        // the frame form: BirdviewMatch(LastFrame, CurrentFrame, 15) + the carry-over
+        auto gpu_f = [&] {
+            return orb_search_by_match_bird_frame(ctx, nnr, 1, 15.f, nA, fe[0].desc.data, kA, has.data(), nB,
+                                                  fe[1].desc.data, kB, g, gm.data(), &gn);
+        };
+        std::vector<int> coff(nA + 1, 0), cand, m12(nA + 1, -1);
+        auto cpu_f = [&] {   // :1790-1921: the per-keypoint grid query on the query's own octave + the restated body
+            cand.clear();
+            for (int i = 0; i < nA; i++) {
+                const int lv = fe[0].kps[i].octave;
+                for (size_t j : Fc.GetFeaturesInArea(fe[0].kps[i].pt.x, fe[0].kps[i].pt.y, 15.f, lv, lv)) cand.push_back((int)j);
+                coff[i + 1] = (int)cand.size();
+            }
+            if (cand.empty()) cand.push_back(0);
+            oracle_window_match(nnr, 1, 0, nA, fe[0].desc.data, okA, nB, fe[1].desc.data, okB, coff.data(), cand.data(),
+                                m12.data());
+            std::fill(cm.begin(), cm.end(), -1);
+            int nmatches = 0;
+            for (int k = 0; k < nA; k++)
+                if (m12[k] >= 0 && has[k]) {
+                    cm[m12[k]] = k;
+                    nmatches++;
+                }
+            return nmatches;
+        };
+        if (gpu_f() != ORB_OK) return fprintf(stderr, "orb_search_by_match_bird_frame: %s\n", orb_last_error()), 2;
+        cn = cpu_f();
+        ok = gn == cn && std::equal(gm.begin(), gm.begin() + nB, cm.begin());
+        gt = median_us([&] { gpu_f(); }, reps);
+        ct = median_us([&] { cpu_f(); }, cpu_reps);
+        emit("SearchByMatchBird_F_F", gt, ct, gn, cn, ok);
+        snprintf(buf, sizeof buf, ", \"bird_queries\": %d", nq);
+        out += buf;
+        orb_destroy(ctx);
     }
     snprintf(buf, sizeof buf, ", \"keypoints\": [%d, %d], \"gpu_reps\": %d, \"cpu_reps\": %d, \"all_equal\": %s}", nA, nB,
              reps, cpu_reps, all_ok ? "true" : "false");
