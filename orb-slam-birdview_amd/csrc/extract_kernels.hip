@@ -134,10 +134,41 @@ __device__ __forceinline__ int4 rs_row_entry(const ResizeCoef& c, int sy0) {
                      GENERIC ? c.c1 : c.c1 << 12);
 }
 // one output pixel's vertical pass from the two rows' horizontal sums (weights from rs_row_entry)
+// in two steps, so that k_resize_rows keeps a source row's sums in the form the vertical pass reads (rs_hkeep:
+// the `>> 4` as a mask, once per sum) and combines two rows' kept sums per output row (rs_vsum)
+template <bool GENERIC>
+__device__ __forceinline__ unsigned rs_hkeep(unsigned h) {
+    return GENERIC ? h : h & ~15u;
+}
+template <bool GENERIC>
+__device__ __forceinline__ unsigned rs_vsum(unsigned c0, unsigned c1, unsigned k0, unsigned k1) {
+    if (GENERIC) return min((__umul24(c0, k0) + __umul24(c1, k1) + (1u << 21)) >> 22, 255u);
+    return (mul_hi_u24(c0, k0) + mul_hi_u24(c1, k1) + 2) >> 2;
+}
 template <bool GENERIC>
 __device__ __forceinline__ unsigned rs_vpass(unsigned c0, unsigned c1, unsigned h0, unsigned h1) {
-    if (GENERIC) return min((__umul24(c0, h0) + __umul24(c1, h1) + (1u << 21)) >> 22, 255u);
-    return (mul_hi_u24(c0, h0 & ~15u) + mul_hi_u24(c1, h1 & ~15u) + 2) >> 2;
+    return rs_vsum<GENERIC>(c0, c1, rs_hkeep<GENERIC>(h0), rs_hkeep<GENERIC>(h1));
+}
+// rs_vsum of 4 pixels with wave-uniform weights, packed into a dword.  The 3.x form without the per-pixel shift,
+// mask and or: t >> 2 of t = a + b + 2 is a byte (as the or-ed pack of rs_vsum's values assumes), so
+// (t0 | t1 << 16) << 6 holds t0 >> 2 and t1 >> 2 in bytes 1 and 3, and one v_perm gathers the four bytes.  The weights are SGPRs (the VOP2 form takes one as src0).
+template <bool GENERIC>
+__device__ __forceinline__ uint32_t rs_vsum4(unsigned c0, unsigned c1, const unsigned (&k0)[4], const unsigned (&k1)[4]) {
+    if (GENERIC) {
+        uint32_t packed = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) packed |= rs_vsum<true>(c0, c1, k0[i], k1[i]) << (8 * i);
+        return packed;
+    }
+    unsigned t[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        unsigned a, b;
+        asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(a) : "s"(c0), "v"(k0[i]));
+        asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(b) : "s"(c1), "v"(k1[i]));
+        t[i] = a + b + 2;
+    }
+    return __builtin_amdgcn_perm((t[2] | (t[3] << 16)) << 6, (t[0] | (t[1] << 16)) << 6, 0x07050301u);
 }
 
 // Cache policy of the loads and stores that hand data between workgroups inside one launch (the small-batch
@@ -329,6 +360,110 @@ __global__ __launch_bounds__(256) void k_resize_tiled(const Geom* __restrict__ g
     __shared__ int4 s_cy[kRsTileH];
     resize_tile<kRsTileH, GENERIC, 0, KP>(g, coef, level, frames, framePitch, rowStride, pyr, blockIdx.z, blockIdx.x,
                                           blockIdx.y, threadIdx.x, s_src, s_cx, s_cy, true);
+}
+
+/* The per-level launch of large batches: the same arithmetic with each source row's horizontal pass made once.
+ * k_resize_tiled's thread makes both source rows' horizontal sums for every output row, and its rows are 8 apart, so
+ * nothing carries over; at scale 1.2 an output row's lower source row is the next row's upper one five times out of
+ * six.  Here a block produces a 256 x 32 tile and a wave owns a strip of kRrStrip consecutive output rows across its
+ * 64 lanes (4 px each): it walks the strip in order and keeps the last source row's four sums (rs_hkeep form) in
+ * registers, so an output row costs one horizontal pass (its lower source row; where s1 == s0, the clamped last
+ * row, that is the kept row again), and a second one only when its upper row is not the one kept: a strip's first
+ * row, or source rows skipped between two output rows.  Which of the two an output row takes depends on the row
+ * tables alone: the wave reads its strip's entries with scalar loads and the decision is a scalar branch.
+ *
+ * Host-checked (rr_geometry; the source 16-byte aligned: launch_extract): each lane's bytes within 8, a tile's
+ * source span at most kRrMaxChunks chunks x 8 KP rows, staged by 32 lanes per row, 8 rows per pass, row step in the
+ * load's scalar offset.  The x tables go from global memory to registers (4 entries per lane); no LDS tables.
+ * Tiles in XCD-local order: blocks are dealt round-robin over the 8 XCDs, and each XCD takes a contiguous range of
+ * a frame's tiles (as k_fast_wave), so the 128-byte lines and source rows that neighbouring tiles share are fetched
+ * into one L2; tile -> (row, column) by the host's recip20(tiles per row). */
+template <bool GENERIC, int KP>
+__global__ __launch_bounds__(256) void k_resize_rows(const Geom* __restrict__ g, const ResizeCoef* __restrict__ coef,
+                                                     int level, const uint8_t* __restrict__ frames,
+                                                     long long framePitch, int rowStride, uint8_t* __restrict__ pyr,
+                                                     int gx, unsigned gxRecip) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_src[];
+    const int f = blockIdx.y;
+    const int nb = gridDim.x, bq = nb >> 3, br = nb & 7, xcd = blockIdx.x & 7, bj = blockIdx.x >> 3;
+    const int tile = (xcd < br ? xcd * (bq + 1) : br * (bq + 1) + (xcd - br) * bq) + bj;
+    const int by = (int)(((unsigned)tile * gxRecip) >> 20), bx = tile - by * gx;
+    const int tid = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: the strip's row entries are scalar loads
+    const int dw = g->L[level].w, dh = g->L[level].h, lp = g->L[level].rr_pitch;
+    const int x0 = bx * kRrTileW, y0 = by * kRrTileH;
+    const LevelPtr src = level_ptr(g, level - 1, frames, framePitch, rowStride, pyr, f);
+    const int nx = min(kRrTileW, dw - x0), ny = min(kRrTileH, dh - y0);
+    const ResizeCoef* __restrict__ cys = coef + dw;
+    // source span (the coefficient tables are monotone)
+    const int sx0 = coef[x0].s0 & ~15, sx1 = coef[x0 + nx - 1].s1;
+    const int sy0 = cys[y0].s0, sy1 = cys[y0 + ny - 1].s1;
+    const int nr = sy1 - sy0 + 1, nq = ((sx1 - sx0) >> 4) + 1;
+    // the span through a buffer descriptor that ends with its last chunk: the loads are unconditional (all in
+    // flight before the first wait) and the range check drops those past the last row (a row past it starts at
+    // nr * stride, beyond the records: the span's bytes lie within a source row) and, by their offset, the lanes
+    // past the last chunk
+    const uint64_t pb = reinterpret_cast<uint64_t>(src.p + (long long)sy0 * src.stride + sx0);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(pb), 0, (nr - 1) * src.stride + 16 * nq,
+                                                        0x00020000);
+    const int sq = tid & 31, sr = tid >> 5;
+    const int soff = sq < nq ? (int)__umul24((unsigned)sr, (unsigned)src.stride) + 16 * sq : 0x40000000;
+    uint32x4_t v[KP];
+#pragma unroll
+    for (int k = 0; k < KP; k++) v[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, soff + 8 * k * src.stride, 0, 0);
+    const int tx = (tid & 63) * 4;
+    ResizeCoef cx[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) cx[i] = coef[min(x0 + tx + i, dw - 1)];
+    const int ys = y0 + wv * kRrStrip;
+    ResizeCoef cy[kRrStrip];
+#pragma unroll
+    for (int k = 0; k < kRrStrip; k++) cy[k] = cys[min(ys + k, dh - 1)];
+#pragma unroll
+    for (int k = 0; k < KP; k++)
+        if (sq < nq && sr + 8 * k < nr) *reinterpret_cast<uint32x4_t*>(&s_src[(sr + 8 * k) * lp + 16 * sq]) = v[k];
+    __syncthreads();
+    if (tx >= nx || ys >= y0 + ny) return;
+    // The 4 pixels' source bytes lie within 8 bytes from the first one's: a row's 3 dwords from LDS, realigned to
+    // it, give each pixel's byte pair as 16-bit lanes through one v_perm, and the horizontal sum is one v_dot2 with
+    // (c0, c1).  Weights are <= 2048 and pixels <= 255, so every product fits 24-bit multiplies.
+    const int bo = cx[0].s0 - sx0;
+    unsigned sel[4];
+    uint32_t cc[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        sel[i] = (unsigned)(cx[i].s0 - sx0 - bo) | 0x0C00u | ((unsigned)(cx[i].s1 - sx0 - bo) << 16) | 0x0C000000u;
+        cc[i] = (unsigned)cx[i].c0 | ((unsigned)cx[i].c1 << 16);
+    }
+    const uint8_t* lrow = s_src + (bo & ~3);
+    const unsigned bsh = bo & 3;
+    auto hpass = [&](unsigned (&h)[4], int srow) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(lrow + (srow - sy0) * lp);
+        const uint32_t u0 = q[0], u1 = q[1], u2 = q[2];
+        const uint32_t a0 = __builtin_amdgcn_alignbyte(u1, u0, bsh), a1 = __builtin_amdgcn_alignbyte(u2, u1, bsh);
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            h[i] = rs_hkeep<GENERIC>(__builtin_amdgcn_udot2(__builtin_bit_cast(ushort2_t, cc[i]),
+                                                            __builtin_bit_cast(ushort2_t, __builtin_amdgcn_perm(a1, a0, sel[i])), 0u, false));
+    };
+    // the level's rows through a buffer descriptor: the row and tile column in the store's scalar offset
+    const uint64_t lb = reinterpret_cast<uint64_t>(pyr + (long long)f * g->pyr_bytes + g->L[level].pyr_off);
+    const auto dsr = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lb), 0, 0x7FFFFFFF, 0x00020000);
+    const int pitch = g->L[level].pitch;
+    unsigned hc[4] = {0, 0, 0, 0}, hn[4];
+    int cur = -1;   // the source row whose sums hc holds
+#pragma unroll
+    for (int k = 0; k < kRrStrip; k++) {
+        if (ys + k >= y0 + ny) break;
+        if (cy[k].s0 != cur) hpass(hc, cy[k].s0);
+        hpass(hn, cy[k].s1);   // (also where s1 == s0, the clamped last row: the same sums again, no merge of two paths)
+        const unsigned c0 = GENERIC ? cy[k].c0 : cy[k].c0 << 12, c1 = GENERIC ? cy[k].c1 : cy[k].c1 << 12;
+        // the pitch is a multiple of 64, so the dword never leaves the row (pad bytes are never read)
+        __builtin_amdgcn_raw_buffer_store_b32(rs_vsum4<GENERIC>(c0, c1, hc, hn), dsr, tx, (ys + k) * pitch + x0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; i++) hc[i] = hn[i];
+        cur = cy[k].s1;
+    }
 }
 
 /* Few-launch pyramid for small batches (the host path's single frame, C5's per-GPU frame): the levels
@@ -2952,7 +3087,18 @@ hipError_t launch_extract(const Geom& g, const ExtractBuffers& b, const uint8_t*
         const int t = g.L[l].rs_tiled;
         const ResizeCoef* cf = b.d_rcoef + b.rcoef_off[l];
         const bool gen = (g.variant & ORB_VARIANT_RESIZE_GENERIC) != 0;
-        if (t & 3) {
+        // batches past the few-launch pyramid's: k_resize_rows where the level's geometry takes it and the source
+        // (the frames for level 1; pyramid levels are 64-byte aligned) allows 16-byte loads
+        const bool src16 = l > 1 || ((reinterpret_cast<uintptr_t>(d_frames) | (uintptr_t)frame_pitch | (uintptr_t)row_stride) & 15) == 0;
+        if (nframes > kChainMaxFrames && g.L[l].rr_rows > 0 && src16) {
+            const int gx = cdiv(g.L[l].w, kRrTileW), gy = cdiv(g.L[l].h, kRrTileH);
+            const size_t lds = (size_t)g.L[l].rr_rows * g.L[l].rr_pitch;
+            const bool kp6 = g.L[l].rr_rows <= 48;   // staging passes of 8 rows: 6 cover scale 1.2's 41-row spans
+            auto kern = gen ? (kp6 ? k_resize_rows<true, 6> : k_resize_rows<true, kRrMaxRows / 8>)
+                            : (kp6 ? k_resize_rows<false, 6> : k_resize_rows<false, kRrMaxRows / 8>);
+            hipLaunchKernelGGL(kern, dim3(gx * gy, nframes), dim3(256), lds, s, b.d_geom, cf, l, d_frames, frame_pitch,
+                               row_stride, b.d_pyr, gx, recip20((uint32_t)gx));
+        } else if (t & 3) {
             const int th = (t & 2) ? 32 : 16;
             const dim3 grid(cdiv(g.L[l].w, kRsTileW), cdiv(g.L[l].h, th), nframes);
             const size_t lds = (size_t)g.L[l].rs_span_rows * kRsPitch;

@@ -170,6 +170,9 @@ int build_geometry(Ctx* c, int W, int H, Geom& g, std::vector<ResizeCoef>& coefs
                 }
                 L.rs_chunks = nq_max * nr_max;
             }
+            const RrGeom rr = rr_geometry(cx, L.w, cy, L.h);
+            L.rr_rows = rr.rows;
+            L.rr_pitch = rr.pitch;
         }
         L.maxBX = L.w - kEdgeThreshold + 3;
         L.maxBY = L.h - kEdgeThreshold + 3;

@@ -29,6 +29,13 @@ constexpr int kDescTapTiles = 3;      // k_describe MFMA row pass: 16-column til
 constexpr int kRsTileW = 128;         // k_resize_tiled<TH>: output tile 128 x TH, 4 px per thread
 constexpr int kRsPitch = 272;         // LDS source tile: up to 272 bytes (from a 16-B aligned column) x (2*TH + 8) rows
 constexpr int rs_rows(int th) { return 2 * th + 8; }
+// k_resize_rows (the per-level launch of batches above kChainMaxFrames): output tile 256 x 32, a wave per strip of
+// 8 consecutive rows, 4 px per lane
+constexpr int kRrTileW = 256;
+constexpr int kRrTileH = 32;
+constexpr int kRrStrip = 8;
+constexpr int kRrMaxRows = 64;        // source rows of a tile it stages at most (8 per staging pass)
+constexpr int kRrMaxChunks = 32;      // 16-byte chunks of a source row it stages at most (one per staging lane)
 
 // Per-level geometry (host-computed once per image size; lives in device memory).
 struct LevelGeom {
@@ -51,6 +58,9 @@ struct LevelGeom {
     int rs_span_rows;    // k_resize_tiled: the largest source span (rows) of a tile: its LDS tile height
     int rs_chunks;       // k_resize_tiled: the most 16-byte source chunks of a tile (rows x chunks per row), so
                          // the launch issues ceil(rs_chunks / 256) loads per thread, not the worst case's
+    int rr_rows;         // k_resize_rows: the largest source span (rows) of a 256 x 32 tile (0: the level's geometry
+                         // does not take that kernel, rr_geometry below)
+    int rr_pitch;        // k_resize_rows: row pitch of its LDS source tile
 };
 
 struct Geom {
@@ -103,6 +113,35 @@ struct ResizeCoef {
     int s0, s1;          // source column/row indices (clamped)
     int c0, c1;          // 11-bit fixed-point weights (saturate_cast<short>(w*2048))
 };
+
+// k_resize_rows' geometry of one level, from its column table cx[0..w) and row table cy[0..h): the LDS source tile
+// (rows, pitch) its launch allocates, or rows = 0 when the kernel does not take the level.  It takes a level when
+//  * the 4 pixels of every lane (the last group clamped to w - 1) read source bytes at most 8 apart (its v_perm
+//    selects from 8 bytes: scale factors up to 2);
+//  * every tile's source rows, from a 16-byte aligned column, are at most kRrMaxChunks 16-byte chunks;
+//  * every tile's source span is at most kRrMaxRows rows.
+// A lane reads the three dwords from its first byte's dword on, so a row is padded by 11 bytes past the widest span.
+struct RrGeom {
+    int rows, pitch;
+};
+inline RrGeom rr_geometry(const ResizeCoef* cx, int w, const ResizeCoef* cy, int h) {
+    const RrGeom none{0, 0};
+    for (int x = 0; x < w; x += 4)
+        if (cx[x + 3 < w ? x + 3 : w - 1].s1 - cx[x].s0 > 7) return none;
+    int span = 0, rows = 0;
+    for (int x0 = 0; x0 < w; x0 += kRrTileW) {
+        const int x1 = (x0 + kRrTileW < w ? x0 + kRrTileW : w) - 1;
+        const int s = cx[x1].s1 - (cx[x0].s0 & ~15) + 1;
+        span = s > span ? s : span;
+    }
+    for (int y0 = 0; y0 < h; y0 += kRrTileH) {
+        const int y1 = (y0 + kRrTileH < h ? y0 + kRrTileH : h) - 1;
+        const int r = cy[y1].s1 - cy[y0].s0 + 1;
+        rows = r > rows ? r : rows;
+    }
+    if ((span + 15) / 16 > kRrMaxChunks || rows > kRrMaxRows) return none;
+    return RrGeom{rows, (span + 11 + 15) & ~15};
+}
 
 // One workgroup of k_pyramid_chain (the few-launch pyramid of small batches): an output tile of
 // `level`, computed from level `base` (the frame, or a level an earlier launch wrote) through the
