@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "orbgpu_ctx.h"
+#include "topk_scan.h"
 
 namespace orbgpu {
 namespace {
@@ -21,6 +22,11 @@ namespace {
 constexpr int TH_LOW = 50;          // ORBmatcher.cc:38
 constexpr int HISTO_LENGTH = 30;    // :39
 constexpr int K = 8;
+
+// A refused argument: the message "<fn>: <why>" for orb_last_error(), and the status.
+int arg_error(const char* fn, const std::string& why) {
+    return set_error((std::string(fn) + ": " + why).c_str(), hipSuccess), ORB_ERR_ARG;
+}
 
 int rot_bin(float a1, float a2) {   // ORBmatcher.cc:236-243 (round(rot*(1/30)): bins 0..12, upstream quirk)
     const float factor = 1.0f / HISTO_LENGTH;
@@ -60,6 +66,18 @@ void cull_rotation(const std::vector<int>* rotHist, std::vector<int>& matches, i
     }
 }
 
+// The same cull where the reference has no ">= 0" guard (SearchForTriangulation :792-813, SearchByProjection
+// :1448-1467, SearchByMatchBird :2093-2111): every entry of a culled bin resets its slot to reset_value and
+// decrements the count, so a slot the histogram holds twice counts twice.
+void cull_rotation_all(const std::vector<int>* rotHist, std::vector<int>& matches, int& nmatches, int reset_value) {
+    int i1 = -1, i2 = -1, i3 = -1;
+    three_maxima(rotHist, i1, i2, i3);
+    for (int i = 0; i < HISTO_LENGTH; i++) {
+        if (i == i1 || i == i2 || i == i3) continue;
+        for (int q : rotHist[i]) { matches[q] = reset_value; nmatches--; }
+    }
+}
+
 // A FeatureVector CSR the walks below can trust: offsets start at 0 and never decrease (so the features of the
 // nodes a walk visits number at most offsets[nnodes], the size the staging is allocated for), every feature index
 // lies in [0, n) (the walks index the descriptors, keypoints and map-point flags with it), and node ids ascend
@@ -89,6 +107,12 @@ void for_common_nodes(const orb_featvec& a, const orb_featvec& b, F f) {   // st
 
 // One matcher call: static data on the device, re-rankable from any item with fresh thresholds.
 struct TopkSession {
+    // which ranking kernel the session drives, and so which input regions its arena holds before the common tail
+    enum Mode {
+        LIST,   // k_topk: inputs [q | t | rng | cand]
+        GRID,   // k_window_topk (orb_window_match_grid): [q | item | cen | k1 | t | k2 | cell_off | cell_idx]
+        PROJ    // k_projection_topk (orb_search_by_projection): [pq | q | t | k2 | ur | cell_off | cell_idx]
+    };
     Ctx* c;
     int nitems = 0, nt = 0;
     std::vector<int> item_q;         // query feature per item
@@ -100,52 +124,79 @@ struct TopkSession {
     const int* cand = nullptr;       // host candidate list
     int ncand = 0;
     Stage st{c};
-    // arena offsets: inputs [q | t | rng | cand | thr], outputs [dist | idx | nvalid]
-    size_t o_q = 0, o_t = 0, o_rng = 0, o_cand = 0, o_thr = 0, o_in_end = 0, o_dist = 0, o_idx = 0, o_nv = 0, o_end = 0;
+    Mode mode = LIST;
+    // arena offsets: the mode's inputs, then the tail every mode shares: [thr] (o_in_end: the end of the uploaded
+    // span) and the outputs [dist | idx | nvalid]
+    size_t o_q = 0, o_t = 0, o_rng = 0, o_cand = 0, o_item = 0, o_cen = 0, o_k1 = 0, o_k2 = 0, o_pq = 0, o_ur = 0,
+           o_coff = 0, o_cidx = 0;
+    size_t o_thr = 0, o_in_end = 0, o_dist = 0, o_idx = 0, o_nv = 0;
     bool uploaded = false;
-    // grid mode (orb_window_match_grid): the candidates come from F2's grid on the device
-    bool grid = false;
-    WinGrid wg{};
-    size_t o_item = 0, o_cen = 0, o_k1 = 0, o_k2 = 0, o_coff = 0, o_cidx = 0;
+    WinGrid wg{};          // GRID / PROJ: the train frame's grid geometry as the kernel takes it
+    ProjGrid pg{};
+    bool cen = false;      // GRID: window centres given (else kps1)
+    bool has_ur = false;   // PROJ: stereo gate
+    int lanes = 64;        // PROJ: lanes per query
     // host results (indexed by item), in the pinned mirror
     const int* dist = nullptr;
     const int* idx = nullptr;
     const int* nvalid = nullptr;
 
-    int setup(const uint8_t* qdesc, const uint8_t* tdesc, int ntrain) {
-        nitems = (int)item_q.size();
+    // The layout of a call: begin(), the mode's input regions in the kernel's order with st.add() (and add_grid()),
+    // finish_layout(), which appends the shared tail and allocates, then the inputs with put() in that same order:
+    // the upload starts at offset 0, with the lines written first.
+    // begin() returns false when there is nothing to rank: no GPU work at all
+    bool begin(Mode m, int n_items, int ntrain) {
+        mode = m;
+        nitems = n_items;
         nt = ntrain;
-        if (nitems == 0) return ORB_OK;   // nothing to rank: no GPU work at all
         st.c = c;
-        o_q = st.add((size_t)nitems * 32);
-        o_t = st.add((size_t)nt * 32);
-        o_rng = st.add((size_t)nitems * 8);
-        o_cand = st.add((size_t)ncand * 4);
+        return nitems > 0;
+    }
+    void add_grid(const orb_frame_grid& g) {
+        o_coff = st.add((size_t)(kFrameGridCells + 1) * 4);
+        o_cidx = st.add((size_t)g.cell_off[kFrameGridCells] * 4);
+    }
+    int finish_layout() {
         o_thr = st.add((size_t)nt * 4);
         o_in_end = st.off;
         o_dist = st.add((size_t)nitems * K * 4);
         o_idx = st.add((size_t)nitems * K * 4);
         o_nv = st.add((size_t)nitems * 4);
-        o_end = st.off;
         const int r = st.alloc();
+        if (r != ORB_OK) return r;
+        dist = st.h<int>(o_dist);
+        idx = st.h<int>(o_idx);
+        nvalid = st.h<int>(o_nv);
+        return ORB_OK;
+    }
+    void put(size_t o, const void* src, size_t bytes) {
+        if (bytes) std::memcpy(st.hi<uint8_t>(o), src, bytes);
+    }
+    void put_grid(const orb_frame_grid& g) {
+        put(o_coff, g.cell_off, (size_t)(kFrameGridCells + 1) * 4);
+        put(o_cidx, g.cell_idx, (size_t)g.cell_off[kFrameGridCells] * 4);
+    }
+
+    // List mode: item i = query item_q[i] (or the row item_src[i]) against the candidates cand[item_rng[i]].
+    int setup(const uint8_t* qdesc, const uint8_t* tdesc, int ntrain) {
+        if (!begin(LIST, (int)item_q.size(), ntrain)) return ORB_OK;
+        o_q = st.add((size_t)nitems * 32);
+        o_t = st.add((size_t)nt * 32);
+        o_rng = st.add((size_t)nitems * 8);
+        o_cand = st.add((size_t)ncand * 4);
+        const int r = finish_layout();
         if (r != ORB_OK) return r;
         uint8_t* hq = st.hi<uint8_t>(o_q);
         for (int i = 0; i < nitems; i++)
             std::memcpy(hq + (size_t)i * 32, item_src.empty() ? qdesc + (size_t)item_q[i] * 32 : item_src[i], 32);
-        if (tparts.empty()) {
-            if (nt) std::memcpy(st.hi<uint8_t>(o_t), tdesc, (size_t)nt * 32);
-        } else {
-            size_t o = 0;
-            for (const auto& tp : tparts) {
-                if (tp.second) std::memcpy(st.hi<uint8_t>(o_t) + o, tp.first, (size_t)tp.second * 32);
-                o += (size_t)tp.second * 32;
-            }
+        if (tparts.empty()) put(o_t, tdesc, (size_t)nt * 32);
+        size_t o = o_t;
+        for (const auto& tp : tparts) {
+            put(o, tp.first, (size_t)tp.second * 32);
+            o += (size_t)tp.second * 32;
         }
-        std::memcpy(st.hi<int2>(o_rng), item_rng.data(), (size_t)nitems * 8);
-        if (ncand) std::memcpy(st.hi<int>(o_cand), cand, (size_t)ncand * 4);
-        dist = st.h<int>(o_dist);
-        idx = st.h<int>(o_idx);
-        nvalid = st.h<int>(o_nv);
+        put(o_rng, item_rng.data(), (size_t)nitems * 8);
+        put(o_cand, cand, (size_t)ncand * 4);
         return ORB_OK;
     }
 
@@ -153,93 +204,52 @@ struct TopkSession {
     // the window around centres[item_q[i]] (NULL: kps1) in F2's grid.
     int setup_grid(const uint8_t* desc1, int n1, const orb_keypoint* kps1, const float* centres, const uint8_t* desc2,
                    int n2, const orb_keypoint* kps2, const orb_frame_grid& g, float r) {
-        nitems = (int)item_q.size();
-        nt = n2;
-        if (nitems == 0) return ORB_OK;
-        grid = true;
+        if (!begin(GRID, (int)item_q.size(), n2)) return ORB_OK;
         wg = WinGrid{g.min_x, g.min_y, g.inv_w, g.inv_h, r};
-        const int ncells = 64 * 48, nslots = g.cell_off[ncells];
-        st.c = c;
+        cen = centres != nullptr;
+        const size_t kp1 = (size_t)n1 * sizeof(orb_keypoint), kp2 = (size_t)n2 * sizeof(orb_keypoint);
         o_q = st.add((size_t)n1 * 32);
         o_item = st.add((size_t)nitems * 4);
-        o_cen = st.add(centres ? (size_t)n1 * 8 : 0);
-        o_k1 = st.add((size_t)n1 * sizeof(orb_keypoint));
+        o_cen = st.add(cen ? (size_t)n1 * 8 : 0);
+        o_k1 = st.add(kp1);
         o_t = st.add((size_t)n2 * 32);
-        o_k2 = st.add((size_t)n2 * sizeof(orb_keypoint));
-        o_coff = st.add((size_t)(ncells + 1) * 4);
-        o_cidx = st.add((size_t)nslots * 4);
-        o_thr = st.add((size_t)n2 * 4);
-        o_in_end = st.off;
-        o_dist = st.add((size_t)nitems * K * 4);
-        o_idx = st.add((size_t)nitems * K * 4);
-        o_nv = st.add((size_t)nitems * 4);
-        o_end = st.off;
-        const int rr = st.alloc();
+        o_k2 = st.add(kp2);
+        add_grid(g);
+        const int rr = finish_layout();
         if (rr != ORB_OK) return rr;
-        auto put = [&](size_t o, const void* src, size_t bytes) {
-            if (bytes) std::memcpy(st.hi<uint8_t>(o), src, bytes);
-        };
         put(o_q, desc1, (size_t)n1 * 32);
         put(o_item, item_q.data(), (size_t)nitems * 4);
-        if (centres) put(o_cen, centres, (size_t)n1 * 8);
-        put(o_k1, kps1, (size_t)n1 * sizeof(orb_keypoint));
+        if (cen) put(o_cen, centres, (size_t)n1 * 8);
+        put(o_k1, kps1, kp1);
         put(o_t, desc2, (size_t)n2 * 32);
-        put(o_k2, kps2, (size_t)n2 * sizeof(orb_keypoint));
-        put(o_coff, g.cell_off, (size_t)(ncells + 1) * 4);
-        put(o_cidx, g.cell_idx, (size_t)nslots * 4);
-        cen = centres != nullptr;
-        dist = st.h<int>(o_dist);
-        idx = st.h<int>(o_idx);
-        nvalid = st.h<int>(o_nv);
+        put(o_k2, kps2, kp2);
+        put_grid(g);
         return ORB_OK;
     }
-    bool cen = false;
 
     // Projection mode (orb_search_by_projection): item i = query i with its own window (orb_proj_query) in the
     // train frame's grid; uright == NULL: no stereo gate.
-    bool proj = false, has_ur = false;
-    int lanes = 64;
-    ProjGrid pg{};
-    size_t o_pq = 0, o_ur = 0;
     int setup_proj(int nq, const orb_proj_query* q, const uint8_t* qdesc, int ntrain, const uint8_t* tdesc,
                    const orb_keypoint* kps_t, const float* uright, const orb_frame_grid& g, int nlanes) {
-        nitems = nq;
-        nt = ntrain;
-        if (nitems == 0) return ORB_OK;
-        proj = true;
+        if (!begin(PROJ, nq, ntrain)) return ORB_OK;
+        pg = ProjGrid{g.min_x, g.min_y, g.inv_w, g.inv_h};
         has_ur = uright != nullptr;
         lanes = nlanes;
-        pg = ProjGrid{g.min_x, g.min_y, g.inv_w, g.inv_h};
-        const int ncells = 64 * 48, nslots = g.cell_off[ncells];
-        st.c = c;
-        o_pq = st.add((size_t)nq * sizeof(orb_proj_query));
+        const size_t pq = (size_t)nq * sizeof(orb_proj_query), kp = (size_t)nt * sizeof(orb_keypoint);
+        o_pq = st.add(pq);
         o_q = st.add((size_t)nq * 32);
         o_t = st.add((size_t)nt * 32);
-        o_k2 = st.add((size_t)nt * sizeof(orb_keypoint));
-        o_ur = st.add(uright ? (size_t)nt * 4 : 0);
-        o_coff = st.add((size_t)(ncells + 1) * 4);
-        o_cidx = st.add((size_t)nslots * 4);
-        o_thr = st.add((size_t)nt * 4);
-        o_in_end = st.off;
-        o_dist = st.add((size_t)nitems * K * 4);
-        o_idx = st.add((size_t)nitems * K * 4);
-        o_nv = st.add((size_t)nitems * 4);
-        o_end = st.off;
-        const int rr = st.alloc();
+        o_k2 = st.add(kp);
+        o_ur = st.add(has_ur ? (size_t)nt * 4 : 0);
+        add_grid(g);
+        const int rr = finish_layout();
         if (rr != ORB_OK) return rr;
-        auto put = [&](size_t o, const void* src, size_t bytes) {
-            if (bytes) std::memcpy(st.hi<uint8_t>(o), src, bytes);
-        };
-        put(o_pq, q, (size_t)nq * sizeof(orb_proj_query));
+        put(o_pq, q, pq);
         put(o_q, qdesc, (size_t)nq * 32);
         put(o_t, tdesc, (size_t)nt * 32);
-        put(o_k2, kps_t, (size_t)nt * sizeof(orb_keypoint));
-        if (uright) put(o_ur, uright, (size_t)nt * 4);
-        put(o_coff, g.cell_off, (size_t)(ncells + 1) * 4);
-        put(o_cidx, g.cell_idx, (size_t)nslots * 4);
-        dist = st.h<int>(o_dist);
-        idx = st.h<int>(o_idx);
-        nvalid = st.h<int>(o_nv);
+        put(o_k2, kps_t, kp);
+        if (has_ur) put(o_ur, uright, (size_t)nt * 4);
+        put_grid(g);
         return ORB_OK;
     }
 
@@ -253,50 +263,49 @@ struct TopkSession {
         if ((e = uploaded ? (thr ? st.up(o_thr, o_thr + (size_t)nt * 4) : hipSuccess) : st.up(0, o_in_end)) != hipSuccess)
             return set_error("upload", e), ORB_ERR_HIP;
         uploaded = true;
+        const int* d_thr = thr ? st.di<int>(o_thr) : nullptr;
+        // the kernel writes the lists straight into the pinned mirror (host-coherent memory; items before
+        // `from` keep their values): no D2H command, one synchronisation
+        int* const out_dist = st.h<int>(o_dist) + (size_t)from * K;
+        int* const out_idx = st.h<int>(o_idx) + (size_t)from * K;
+        int* const out_nv = st.h<int>(o_nv) + from;
         if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
-        if (proj)
+        switch (mode) {
+        case PROJ:
             e = launch_projection_topk(st.di<orb_proj_query>(o_pq) + from, st.di<uint8_t>(o_q) + (size_t)from * 32, n,
                                        st.di<uint8_t>(o_t), st.di<orb_keypoint>(o_k2),
                                        has_ur ? st.di<float>(o_ur) : nullptr, st.di<int>(o_coff), st.di<int>(o_cidx), pg,
-                                       thr ? st.di<int>(o_thr) : nullptr, K, lanes,
-                                       st.h<int>(o_dist) + (size_t)from * K, st.h<int>(o_idx) + (size_t)from * K,
-                                       st.h<int>(o_nv) + from, c->stream);
-        else if (grid)
+                                       d_thr, K, lanes, out_dist, out_idx, out_nv, c->stream);
+            break;
+        case GRID:
             e = launch_window_topk(st.di<uint8_t>(o_q), st.di<int>(o_item) + from, cen ? st.di<float2>(o_cen) : nullptr, n,
                                    st.di<orb_keypoint>(o_k1), st.di<uint8_t>(o_t), st.di<orb_keypoint>(o_k2),
-                                   st.di<int>(o_coff), st.di<int>(o_cidx), wg, thr ? st.di<int>(o_thr) : nullptr, K,
-                                   st.h<int>(o_dist) + (size_t)from * K, st.h<int>(o_idx) + (size_t)from * K,
-                                   st.h<int>(o_nv) + from, c->stream);
-        else
+                                   st.di<int>(o_coff), st.di<int>(o_cidx), wg, d_thr, K, out_dist, out_idx, out_nv,
+                                   c->stream);
+            break;
+        case LIST:
             e = launch_hamming_topk(st.di<uint8_t>(o_q) + (size_t)from * 32, n, st.di<uint8_t>(o_t), nt,
-                                    st.di<int2>(o_rng) + from, st.di<int>(o_cand), thr ? st.di<int>(o_thr) : nullptr, K,
-                                    st.h<int>(o_dist) + (size_t)from * K, st.h<int>(o_idx) + (size_t)from * K,
-                                    st.h<int>(o_nv) + from, c->stream);
+                                    st.di<int2>(o_rng) + from, st.di<int>(o_cand), d_thr, K, out_dist, out_idx, out_nv,
+                                    c->stream);
+            break;
+        }
         if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 0, c->stream);
         if (e != hipSuccess) return set_error("hamming kernel", e), ORB_ERR_HIP;
-        // the kernel writes the lists straight into the pinned mirror (host-coherent memory; items before
-        // `from` keep their values): no D2H command, one synchronisation
         if ((e = hipStreamSynchronize(c->stream)) != hipSuccess)
             return set_error("download top-k", e), ORB_ERR_HIP;
         return ORB_OK;
     }
 
-    // First two admissible entries of item i's list. Returns false if the list cannot decide them.
-    template <class Admit>
-    bool best_two(int i, Admit admit, int& d1, int& i1, int& d2, int init) const {
-        d1 = init;
-        i1 = -1;
-        d2 = init;
-        int found = 0;
-        for (int j = 0; j < K; j++) {
-            const int d = dist[(size_t)i * K + j];
-            if (d < 0) break;
-            const int t = idx[(size_t)i * K + j];
-            if (!admit(t, d)) continue;
-            if (found == 0) { d1 = d; i1 = t; found = 1; }
-            else { d2 = d; found = 2; break; }
-        }
-        return found == 2 || nvalid[i] <= K;
+    // The first `need` entries of item i's list that admit(train, distance) accepts (topk_scan.h).  A list that cannot
+    // decide them is ranked again from item i on (to `to`) against the thresholds fill_thr() returns, which state
+    // what the replay admits now, and scanned once more: the new list starts with the item's best admissible trains.
+    template <class Admit, class FillThr>
+    int pick(int i, int need, Admit admit, int stop_at, FillThr fill_thr, int to, TopkPick& p) {
+        if (topk_scan(dist, idx, nvalid, K, i, need, admit, stop_at, p)) return ORB_OK;
+        const int r = run(i, fill_thr(), to);
+        if (r != ORB_OK) return r;
+        topk_scan(dist, idx, nvalid, K, i, need, admit, stop_at, p);
+        return ORB_OK;
     }
 };
 
@@ -311,14 +320,15 @@ int bow_kf_f_replay(TopkSession& s, int ib, int ie, float nnratio, int check_ori
     std::vector<int> rotHist[HISTO_LENGTH];
     int nmatches = 0;
     auto admit = [&](int t, int) { return matches[t] < 0; };   // if(vpMapPointMatches[realIdxF]) continue;
+    auto fill_thr = [&]() {
+        for (int t = 0; t < n_f; t++) thr[t] = matches[t] >= 0 ? -1 : INT_MAX;
+        return thr.data();
+    };
+    TopkPick p;
     for (int i = ib; i < ie; i++) {
-        int d1, i1, d2;
-        if (!s.best_two(i, admit, d1, i1, d2, 256)) {
-            for (int t = 0; t < n_f; t++) thr[t] = matches[t] >= 0 ? -1 : INT_MAX;
-            const int st = s.run(i, thr.data(), ie);
-            if (st != ORB_OK) return st;
-            s.best_two(i, admit, d1, i1, d2, 256);
-        }
+        const int st = s.pick(i, 2, admit, kTopkNoStop, fill_thr, ie, p);
+        if (st != ORB_OK) return st;
+        const int d1 = p.dist(0, 256), i1 = p.t[0], d2 = p.dist(1, 256);   // bestDist1 = bestDist2 = 256 (:201-203)
         if (d1 <= TH_LOW && static_cast<float>(d1) < nnratio * static_cast<float>(d2)) {   // :228-230
             const int realIdxKF = s.item_q[i];
             matches[i1] = realIdxKF;
@@ -341,15 +351,16 @@ int bow_kf_kf_replay(TopkSession& s, int ib, int ie, int tb, std::vector<int>& t
     std::vector<int> matches(n1, -1);
     std::vector<int> rotHist[HISTO_LENGTH];
     int nmatches = 0;
-    auto admit = [&](int t, int) { return !matched2[t - tb]; };
+    auto admit = [&](int t, int) { return !matched2[t - tb]; };   // if(vbMatched2[idx2] || !pMP2) continue; (:576-577)
+    auto fill_thr = [&]() {
+        for (int t = 0; t < n2; t++) thr[tb + t] = (matched2[t] || !mp2[t]) ? -1 : INT_MAX;
+        return thr.data();
+    };
+    TopkPick p;
     for (int i = ib; i < ie; i++) {
-        int d1, i1, d2;
-        if (!s.best_two(i, admit, d1, i1, d2, 256)) {
-            for (int t = 0; t < n2; t++) thr[tb + t] = (matched2[t] || !mp2[t]) ? -1 : INT_MAX;
-            const int st = s.run(i, thr.data(), ie);
-            if (st != ORB_OK) return st;
-            s.best_two(i, admit, d1, i1, d2, 256);
-        }
+        const int st = s.pick(i, 2, admit, kTopkNoStop, fill_thr, ie, p);
+        if (st != ORB_OK) return st;
+        const int d1 = p.dist(0, 256), i1 = p.t[0], d2 = p.dist(1, 256);   // bestDist1 = bestDist2 = 256 (:566-568)
         if (d1 < TH_LOW && static_cast<float>(d1) < nnratio * static_cast<float>(d2)) {   // :598-600
             const int idx1 = s.item_q[i], j2 = i1 - tb;
             matches[idx1] = j2;
@@ -625,7 +636,7 @@ int orb_search_by_bow_kf_f(orb_ctx* h, float nnratio, int check_ori, int n_kf, c
     CTX_GUARD(c);
     if (n_kf < 0 || n_f < 0 || !match_f) return ORB_ERR_ARG;
     if (!featvec_ok(fv_kf, n_kf) || !featvec_ok(fv_f, n_f))
-        return set_error("orb_search_by_bow_kf_f: malformed FeatureVector CSR", hipSuccess), ORB_ERR_ARG;
+        return arg_error("orb_search_by_bow_kf_f", "malformed FeatureVector CSR");
     const orb_bow_kf K{n_kf, desc_kf, angle_kf, mp_kf, fv_kf, match_f, nmatches_out};
     return bow_kf_f_run(c, nnratio, check_ori, n_f, desc_f, angle_f, fv_f, 1, &K);
 }
@@ -635,11 +646,9 @@ int orb_search_by_bow_kf_f_batch(orb_ctx* h, float nnratio, int check_ori, int n
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     if (n_f < 0 || nkf < 0 || (nkf > 0 && !kfs) || (n_f > 0 && !(desc_f && angle_f))) return ORB_ERR_ARG;
-    if (!featvec_ok(fv_f, n_f))
-        return set_error("orb_search_by_bow_kf_f_batch: malformed FeatureVector CSR", hipSuccess), ORB_ERR_ARG;
+    if (!featvec_ok(fv_f, n_f)) return arg_error("orb_search_by_bow_kf_f_batch", "malformed FeatureVector CSR");
     for (int p = 0; p < nkf; p++)
-        if (!bow_kf_ok(kfs[p]))
-            return set_error("orb_search_by_bow_kf_f_batch: bad keyframe arguments", hipSuccess), ORB_ERR_ARG;
+        if (!bow_kf_ok(kfs[p])) return arg_error("orb_search_by_bow_kf_f_batch", "bad keyframe arguments");
     return nkf ? bow_kf_f_run(c, nnratio, check_ori, n_f, desc_f, angle_f, fv_f, nkf, kfs) : ORB_OK;
 }
 
@@ -652,7 +661,7 @@ int orb_search_by_bow_kf_kf(orb_ctx* h, float nnratio, int check_ori, int n1, co
     CTX_GUARD(c);
     if (n1 < 0 || n2 < 0 || !match12) return ORB_ERR_ARG;
     if (!featvec_ok(fv1, n1) || !featvec_ok(fv2, n2))
-        return set_error("orb_search_by_bow_kf_kf: malformed FeatureVector CSR", hipSuccess), ORB_ERR_ARG;
+        return arg_error("orb_search_by_bow_kf_kf", "malformed FeatureVector CSR");
     const orb_bow_kf K{n2, desc2, angle2, mp2, fv2, match12, nmatches_out};
     return bow_kf_kf_run(c, nnratio, check_ori, n1, desc1, angle1, mp1, fv1, 1, &K);
 }
@@ -663,16 +672,13 @@ int orb_search_by_bow_kf_kf_batch(orb_ctx* h, float nnratio, int check_ori, int 
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     if (n1 < 0 || nkf < 0 || (nkf > 0 && !kf2s) || (n1 > 0 && !(desc1 && angle1 && mp1))) return ORB_ERR_ARG;
-    if (!featvec_ok(fv1, n1))
-        return set_error("orb_search_by_bow_kf_kf_batch: malformed FeatureVector CSR", hipSuccess), ORB_ERR_ARG;
+    if (!featvec_ok(fv1, n1)) return arg_error("orb_search_by_bow_kf_kf_batch", "malformed FeatureVector CSR");
     long long ntot = 0;
     for (int p = 0; p < nkf; p++) {
-        if (!bow_kf_ok(kf2s[p]))
-            return set_error("orb_search_by_bow_kf_kf_batch: bad keyframe arguments", hipSuccess), ORB_ERR_ARG;
+        if (!bow_kf_ok(kf2s[p])) return arg_error("orb_search_by_bow_kf_kf_batch", "bad keyframe arguments");
         ntot += kf2s[p].n;
     }
-    if (ntot > INT_MAX / 64)
-        return set_error("orb_search_by_bow_kf_kf_batch: too many features", hipSuccess), ORB_ERR_ARG;
+    if (ntot > INT_MAX / 64) return arg_error("orb_search_by_bow_kf_kf_batch", "too many features");
     return nkf ? bow_kf_kf_run(c, nnratio, check_ori, n1, desc1, angle1, mp1, fv1, nkf, kf2s) : ORB_OK;
 }
 
@@ -786,14 +792,8 @@ int tri_replay_pair(Ctx* c, int check_ori, int n1, const orb_keypoint* kps1, con
         nmatches++;
         if (check_ori) rotHist[rot_bin(kps1[idx1].angle, kps2[best[i]].angle)].push_back(idx1);
     }
-    if (check_ori) {   // :792-813 (no ">= 0" guard in this function: every culled entry decrements)
-        int i1 = -1, i2 = -1, i3 = -1;
-        three_maxima(rotHist, i1, i2, i3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == i1 || i == i2 || i == i3) continue;
-            for (int q : rotHist[i]) { vMatches12[q] = -1; nmatches--; }
-        }
-    }
+    // :792-813 (no ">= 0" guard in this function: every culled entry decrements)
+    if (check_ori) cull_rotation_all(rotHist, vMatches12, nmatches, -1);
     (void)nmatches;   // == the number of pairs collected below (:815-820)
     int np = 0;
     for (int i = 0; i < n1; i++) {
@@ -818,7 +818,7 @@ int tri_run(Ctx* c, int check_ori, int only_stereo, const TriSide& a, int npairs
         cap_trains += pairs[p].fv2.nnodes > 0 ? (size_t)pairs[p].fv2.offsets[pairs[p].fv2.nnodes] : 0;
     }
     if (cap_items > (size_t)INT_MAX / 2 || cap_trains > (size_t)INT_MAX / 2)
-        return set_error("orb_search_for_triangulation: too many records", hipSuccess), ORB_ERR_ARG;
+        return arg_error("orb_search_for_triangulation", "too many records");
     std::vector<int>& item_q = c->tri_item_q;     // item -> idx1
     std::vector<int>& train_of = c->tri_train_of; // train record -> idx2
     item_q.clear();
@@ -890,7 +890,7 @@ int orb_search_for_triangulation(orb_ctx* h, int check_ori, int only_stereo, int
     CTX_GUARD(c);
     if (n1 < 0 || n2 < 0 || !npairs || nlevels2 < 1 || nlevels2 > ORBGPU_MAX_LEVELS) return ORB_ERR_ARG;
     if (!featvec_ok(fv1, n1) || !featvec_ok(fv2, n2))
-        return set_error("orb_search_for_triangulation: malformed FeatureVector CSR", hipSuccess), ORB_ERR_ARG;
+        return arg_error("orb_search_for_triangulation", "malformed FeatureVector CSR");
     const orb_tri_pair P{n2, desc2, kps2, has_mp2, uright2, fv2, F12, ex, ey, scale2, sigma2_2, nlevels2, pairs_out, cap,
                          npairs};
     return tri_run(c, check_ori, only_stereo, TriSide{n1, desc1, kps1, has_mp1, uright1, fv1}, 1, &P);
@@ -902,11 +902,9 @@ int orb_search_for_triangulation_batch(orb_ctx* h, int check_ori, int only_stere
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     if (n1 < 0 || npairs < 0 || (npairs > 0 && !pairs)) return ORB_ERR_ARG;
-    if (!featvec_ok(fv1, n1))
-        return set_error("orb_search_for_triangulation_batch: malformed FeatureVector CSR", hipSuccess), ORB_ERR_ARG;
+    if (!featvec_ok(fv1, n1)) return arg_error("orb_search_for_triangulation_batch", "malformed FeatureVector CSR");
     for (int p = 0; p < npairs; p++)
-        if (!tri_pair_ok(pairs[p]))
-            return set_error("orb_search_for_triangulation_batch: bad pair arguments", hipSuccess), ORB_ERR_ARG;
+        if (!tri_pair_ok(pairs[p])) return arg_error("orb_search_for_triangulation_batch", "bad pair arguments");
     if (npairs == 0) return ORB_OK;
     return tri_run(c, check_ori, only_stereo, TriSide{n1, desc1, kps1, has_mp1, uright1, fv1}, npairs, pairs);
 }
@@ -915,14 +913,15 @@ int orb_search_for_triangulation_batch(orb_ctx* h, int check_ori, int only_stere
 
 namespace orbgpu {
 namespace {
-// What is wrong with a Frame grid CSR (cell_off and, where it has slots, cell_idx not NULL), or NULL: the grid
-// kernels read cell_idx[cell_off[..]] for every rectangle column and index the trains by cell_idx, so a malformed
-// CSR would be an out-of-bounds device read.
+// What is wrong with a Frame grid CSR over nt trains, or NULL: cell_off missing, or cell_idx missing where the grid
+// has slots; then the CSR itself, since the grid kernels read cell_idx[cell_off[..]] for every rectangle column and
+// index the trains by cell_idx, so a malformed one would be an out-of-bounds device read.
 const char* grid_csr_fault(const orb_frame_grid& g, int nt) {
+    if (!g.cell_off || (g.cell_off[kFrameGridCells] && !g.cell_idx)) return "bad arguments";
     if (g.cell_off[0] != 0) return "grid cell_off[0] != 0";
-    for (int i = 0; i < 64 * 48; i++)   // offsets non-decreasing, so every run lies in [0, cell_off[3072])
+    for (int i = 0; i < kFrameGridCells; i++)   // offsets non-decreasing, so every run lies in [0, cell_off[3072])
         if (g.cell_off[i + 1] < g.cell_off[i]) return "grid cell_off decreases";
-    for (int i = 0, nslots = g.cell_off[64 * 48]; i < nslots; i++)   // the device indexes the trains by these
+    for (int i = 0, nslots = g.cell_off[kFrameGridCells]; i < nslots; i++)   // the device indexes the trains by these
         if (g.cell_idx[i] < 0 || g.cell_idx[i] >= nt) return "grid index out of range";
     return nullptr;
 }
@@ -937,12 +936,11 @@ int window_replay(TopkSession& s, float nnratio, int check_ori, int n1, const or
     std::vector<int> rotHist[HISTO_LENGTH];
     int nmatches = 0;
     auto admit = [&](int t, int d) { return vMatchedDistance[t] > d; };   // if(vMatchedDistance[i2]<=dist) continue;
+    auto fill_thr = [&]() { return vMatchedDistance.data(); };   // the kernel's own rule is thr[t] <= d: skip
+    TopkPick p;
     for (int i = 0; i < s.nitems; i++) {
-        int d1, b2, d2;
-        if (!s.best_two(i, admit, d1, b2, d2, INT_MAX)) {
-            if ((st = s.run(i, vMatchedDistance.data())) != ORB_OK) return st;
-            s.best_two(i, admit, d1, b2, d2, INT_MAX);
-        }
+        if ((st = s.pick(i, 2, admit, kTopkNoStop, fill_thr, -1, p)) != ORB_OK) return st;
+        const int d1 = p.dist(0, INT_MAX), b2 = p.t[0], d2 = p.dist(1, INT_MAX);   // bestDist = bestDist2 = INT_MAX
         const int i1 = s.item_q[i];
         if (d1 <= TH_LOW && d1 < (float)d2 * nnratio) {   // :457-459
             if (vnMatches21[b2] >= 0) {
@@ -975,35 +973,23 @@ int proj_replay(TopkSession& s, int mode, float nnratio, int check_ori, int max_
     std::vector<int> rotHist[HISTO_LENGTH];
     auto fill_thr = [&]() {
         for (int t = 0; t < nt; t++) thr[t] = taken[t] ? -1 : INT_MAX;
+        return thr.data();
     };
     if (t_taken)
         for (int t = 0; t < nt; t++) taken[t] = t_taken[t] != 0;
-    fill_thr();
-    int st = s.run(0, t_taken ? thr.data() : nullptr);
+    int st = s.run(0, t_taken ? fill_thr() : nullptr);
     if (st != ORB_OK) return st;
+    // SearchByProjection(CurrentFrame, LastFrame) keeps one minimum, the other forms two; all of them start at 256
+    // and update on '<' only, so an entry at 256 or beyond ends the entries that can be a minimum
     const int need = mode == ORB_PROJ_BEST ? 1 : 2;
-    int d[2], ti[2], found = 0;
-    // the first `need` admissible entries of query i's list with a distance below 256 (the reference's running
-    // minima start at 256 and update on '<' only); false if the list cannot decide them
-    auto scan = [&](int i) {
-        found = 0;
-        for (int j = 0; j < K && found < need; j++) {
-            const int dj = s.dist[(size_t)i * K + j];
-            if (dj < 0 || dj >= 256) return true;   // the end of the list, or of its entries that can be a minimum
-            const int t = s.idx[(size_t)i * K + j];
-            if (taken[t]) continue;
-            d[found] = dj;
-            ti[found++] = t;
-        }
-        return found == need || s.nvalid[i] <= K;
-    };
+    auto admit = [&](int t, int) { return !taken[t]; };
+    TopkPick p;
     int nmatches = 0;
     for (int i = 0; i < nq; i++) {
-        if (!scan(i)) {
-            fill_thr();
-            if ((st = s.run(i, thr.data())) != ORB_OK) return st;
-            scan(i);
-        }
+        if ((st = s.pick(i, need, admit, 256, fill_thr, -1, p)) != ORB_OK) return st;
+        const int found = p.found;
+        const int* d = p.d;
+        const int* ti = p.t;
         if (found == 0 || d[0] > max_dist) continue;   // :118 / :1426 / :1987
         if (mode == ORB_PROJ_RATIO_SAME_LEVEL) {       // :120-121 / :1989-1990
             const int bestLevel = kps_t[ti[0]].octave, bestLevel2 = found == 2 ? kps_t[ti[1]].octave : -1;
@@ -1015,14 +1001,9 @@ int proj_replay(TopkSession& s, int mode, float nnratio, int check_ori, int max_
         nmatches++;
         if (mode == ORB_PROJ_BEST && check_ori) rotHist[rot_bin(q[i].angle, kps_t[ti[0]].angle)].push_back(ti[0]);
     }
-    if (mode == ORB_PROJ_BEST && check_ori) {   // :1448-1467: every entry of a culled bin resets its train and decrements
-        int i1 = -1, i2 = -1, i3 = -1;          // (no guard: a train entered twice by overwriting queries counts twice)
-        three_maxima(rotHist, i1, i2, i3);
-        for (int b = 0; b < HISTO_LENGTH; b++) {
-            if (b == i1 || b == i2 || b == i3) continue;
-            for (int t : rotHist[b]) { matches[t] = -2; nmatches--; }
-        }
-    }
+    // :1448-1467: every entry of a culled bin resets its train and decrements (no guard: a train entered twice by
+    // overwriting queries counts twice)
+    if (mode == ORB_PROJ_BEST && check_ori) cull_rotation_all(rotHist, matches, nmatches, -2);
     std::memcpy(match_t, matches.data(), (size_t)nt * sizeof(int));
     if (nmatches_out) *nmatches_out = nmatches;
     return ORB_OK;
@@ -1043,28 +1024,15 @@ int match_bird_replay(TopkSession& s, float nnratio, int check_ori, int max_dist
     if (st != ORB_OK) return st;
     std::vector<int> vMatchedDistanceBird(nt, INT_MAX), matches(nt, -1);
     std::vector<int> rotHist[HISTO_LENGTH];
-    int d[2], ti[2], found = 0;
-    auto scan = [&](int i) {
-        found = 0;
-        for (int j = 0; j < K && found < 2; j++) {
-            const int dj = s.dist[(size_t)i * K + j];
-            if (dj < 0) break;
-            const int t = s.idx[(size_t)i * K + j];
-            if (vMatchedDistanceBird[t] <= dj) continue;   // :2051
-            d[found] = dj;
-            ti[found++] = t;
-        }
-        return found == 2 || s.nvalid[i] <= K;
-    };
+    auto admit = [&](int t, int d) { return vMatchedDistanceBird[t] > d; };   // :2051
+    auto fill_thr = [&]() { return vMatchedDistanceBird.data(); };
+    TopkPick p;
     int nmatches = 0;
     for (int i = 0; i < nq; i++) {
-        if (!scan(i)) {
-            if ((st = s.run(i, vMatchedDistanceBird.data())) != ORB_OK) return st;
-            scan(i);
-        }
-        if (found == 0) continue;   // :2025, or every candidate skipped: bestDist stays INT_MAX
-        const int bestDist = d[0], bestIdx = ti[0], bestLevel = kps_t[bestIdx].octave;
-        const int bestDist2 = found == 2 ? d[1] : INT_MAX, bestLevel2 = found == 2 ? kps_t[ti[1]].octave : -1;
+        if ((st = s.pick(i, 2, admit, kTopkNoStop, fill_thr, -1, p)) != ORB_OK) return st;
+        if (p.found == 0) continue;   // :2025, or every candidate skipped: bestDist stays INT_MAX
+        const int bestDist = p.d[0], bestIdx = p.t[0], bestLevel = kps_t[bestIdx].octave;
+        const int bestDist2 = p.dist(1, INT_MAX), bestLevel2 = p.found == 2 ? kps_t[p.t[1]].octave : -1;
         if (bestDist <= max_dist) {                                                      // :2070
             if (bestLevel != bestLevel2 || bestDist < (float)bestDist2 * nnratio) {      // :2072
                 matches[bestIdx] = q_id ? q_id[i] : i;
@@ -1074,14 +1042,7 @@ int match_bird_replay(TopkSession& s, float nnratio, int check_ori, int max_dist
             }
         }
     }
-    if (check_ori) {   // :2093-2111, no guard
-        int i1 = -1, i2 = -1, i3 = -1;
-        three_maxima(rotHist, i1, i2, i3);
-        for (int b = 0; b < HISTO_LENGTH; b++) {
-            if (b == i1 || b == i2 || b == i3) continue;
-            for (int t : rotHist[b]) { matches[t] = -2; nmatches--; }
-        }
-    }
+    if (check_ori) cull_rotation_all(rotHist, matches, nmatches, -2);   // :2093-2111, no guard
     std::memcpy(match_t, matches.data(), (size_t)nt * sizeof(int));
     if (nmatches_out) *nmatches_out = nmatches;
     return ORB_OK;
@@ -1092,15 +1053,13 @@ int match_bird_replay(TopkSession& s, float nnratio, int check_ori, int max_dist
 const char* proj_target_fault(int gate, const orb_proj_target& T, int q0, int q1) {
     if (T.nq < 0 || T.nt < 0) return "negative count";
     if (T.nq > 0 && (!T.best_idx || !T.best_dist)) return "NULL outputs";
-    if ((T.nq > 0 && (!T.q || !T.qdesc)) || (T.nt > 0 && (!T.tdesc || !T.kps_t)) || !T.grid.cell_off ||
-        (T.grid.cell_off[64 * 48] && !T.grid.cell_idx))
-        return "bad arguments";
+    if ((T.nq > 0 && (!T.q || !T.qdesc)) || (T.nt > 0 && (!T.tdesc || !T.kps_t))) return "bad arguments";
+    if (const char* why = grid_csr_fault(T.grid, T.nt)) return why;
     for (int i = q0; i < q1; i++) {
         if (!std::isfinite(T.q[i].u) || !std::isfinite(T.q[i].v) || !std::isfinite(T.q[i].r) || T.q[i].r < 0)
             return "query window not finite or radius negative";
         if (gate == ORB_PROJ_GATE_FUSE && !std::isfinite(T.q[i].ur)) return "query ur not finite";
     }
-    if (const char* why = grid_csr_fault(T.grid, T.nt)) return why;
     if (gate == ORB_PROJ_GATE_FUSE) {
         if (!T.inv_sigma2) return "inv_sigma2 NULL";
         if (T.nlevels < 1 || T.nlevels > ORBGPU_MAX_LEVELS) return "nlevels outside [1, ORBGPU_MAX_LEVELS]";
@@ -1126,7 +1085,7 @@ bool fuse_gate_skips(float u, float v, float ur, const orb_keypoint& kp, float u
 // One query of a (validated) target on the CPU: k_projection_best's walk over the grid CSR, sequentially.
 void proj_best_one(int gate, const orb_proj_target& T, const orb_proj_query& P, const uint8_t* qdesc, int* best_idx,
                    int* best_dist) {
-    const int COLS = 64, ROWS = 48;
+    const int COLS = kFrameGridCols, ROWS = kFrameGridRows;
     const orb_frame_grid& g = T.grid;
     *best_idx = -1;
     *best_dist = -1;
@@ -1194,11 +1153,10 @@ int orb_window_match_grid(orb_ctx* h, float nnratio, int check_ori, int level0_o
                           int* nmatches_out) {
     // the arguments are checked before the context: k_window_topk reads cell_idx[cell_off[..]] for every
     // rectangle column, so a malformed CSR would be an out-of-bounds device read
-    if (n1 < 0 || n2 < 0 || !match12 || (n1 && (!desc1 || !kps1)) || (n2 && (!desc2 || !kps2)) ||
-        !grid2.cell_off || (grid2.cell_off[64 * 48] && !grid2.cell_idx))
-        return set_error("orb_window_match_grid: bad arguments", hipSuccess), ORB_ERR_ARG;
-    if (const char* why = grid_csr_fault(grid2, n2))
-        return set_error((std::string("orb_window_match_grid: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
+    const char* const fn = "orb_window_match_grid";
+    if (n1 < 0 || n2 < 0 || !match12 || (n1 && (!desc1 || !kps1)) || (n2 && (!desc2 || !kps2)))
+        return arg_error(fn, "bad arguments");
+    if (const char* why = grid_csr_fault(grid2, n2)) return arg_error(fn, why);
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     TopkSession s{c};
@@ -1218,19 +1176,15 @@ int orb_search_by_projection(orb_ctx* h, int mode, float nnratio, int check_ori,
                              const orb_keypoint* kps_t, const float* t_uright, const uint8_t* t_taken,
                              orb_frame_grid grid, int* match_t, int* nmatches_out) {
     // as in orb_window_match_grid the arguments are checked before the context: nothing malformed reaches the device
-    if (mode != ORB_PROJ_BEST && mode != ORB_PROJ_RATIO_SAME_LEVEL)
-        return set_error("orb_search_by_projection: unknown mode", hipSuccess), ORB_ERR_ARG;
-    if (max_dist < 0 || max_dist > 256)
-        return set_error("orb_search_by_projection: max_dist outside [0, 256]", hipSuccess), ORB_ERR_ARG;
-    if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q || !qdesc)) || (nt && (!tdesc || !kps_t)) ||
-        !grid.cell_off || (grid.cell_off[64 * 48] && !grid.cell_idx))
-        return set_error("orb_search_by_projection: bad arguments", hipSuccess), ORB_ERR_ARG;
+    const char* const fn = "orb_search_by_projection";
+    if (mode != ORB_PROJ_BEST && mode != ORB_PROJ_RATIO_SAME_LEVEL) return arg_error(fn, "unknown mode");
+    if (max_dist < 0 || max_dist > 256) return arg_error(fn, "max_dist outside [0, 256]");
+    if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q || !qdesc)) || (nt && (!tdesc || !kps_t)))
+        return arg_error(fn, "bad arguments");
+    if (const char* why = grid_csr_fault(grid, nt)) return arg_error(fn, why);
     for (int i = 0; i < nq; i++)
         if (!std::isfinite(q[i].u) || !std::isfinite(q[i].v) || !std::isfinite(q[i].r) || q[i].r < 0)
-            return set_error("orb_search_by_projection: query window not finite or radius negative", hipSuccess),
-                   ORB_ERR_ARG;
-    if (const char* why = grid_csr_fault(grid, nt))
-        return set_error((std::string("orb_search_by_projection: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
+            return arg_error(fn, "query window not finite or radius negative");
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     for (int t = 0; t < nt; t++) match_t[t] = -1;
@@ -1255,21 +1209,19 @@ int orb_search_by_match_bird(orb_ctx* h, float nnratio, int check_ori, int max_d
                              const uint8_t* tdesc, const orb_keypoint* kps_t, orb_frame_grid grid, int* match_t,
                              int* nmatches_out) {
     // the arguments are checked before the context: nothing malformed reaches the device, no output is written
-    if (max_dist < 0 || max_dist > 256)
-        return set_error("orb_search_by_match_bird: max_dist outside [0, 256]", hipSuccess), ORB_ERR_ARG;
-    if (!std::isfinite(r) || r < 0)
-        return set_error("orb_search_by_match_bird: radius not finite or negative", hipSuccess), ORB_ERR_ARG;
+    const char* const fn = "orb_search_by_match_bird";
+    if (max_dist < 0 || max_dist > 256) return arg_error(fn, "max_dist outside [0, 256]");
+    if (!std::isfinite(r) || r < 0) return arg_error(fn, "radius not finite or negative");
     if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q_xy || !qdesc || (check_ori && !q_angle))) ||
-        (nt && (!tdesc || !kps_t)) || !grid.cell_off || (grid.cell_off[64 * 48] && !grid.cell_idx))
-        return set_error("orb_search_by_match_bird: bad arguments", hipSuccess), ORB_ERR_ARG;
+        (nt && (!tdesc || !kps_t)))
+        return arg_error(fn, "bad arguments");
+    if (const char* why = grid_csr_fault(grid, nt)) return arg_error(fn, why);
     for (int i = 0; i < nq; i++) {
         if (!std::isfinite(q_xy[2 * i]) || !std::isfinite(q_xy[2 * i + 1]))
-            return set_error("orb_search_by_match_bird: query centre not finite", hipSuccess), ORB_ERR_ARG;
-        if (q_id && q_id[i] < 0)   // (match_t keeps the negative values for "untouched" and "culled")
-            return set_error("orb_search_by_match_bird: negative query id", hipSuccess), ORB_ERR_ARG;
+            return arg_error(fn, "query centre not finite");
+        // (match_t keeps the negative values for "untouched" and "culled")
+        if (q_id && q_id[i] < 0) return arg_error(fn, "negative query id");
     }
-    if (const char* why = grid_csr_fault(grid, nt))
-        return set_error((std::string("orb_search_by_match_bird: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     for (int t = 0; t < nt; t++) match_t[t] = -1;
@@ -1290,11 +1242,11 @@ int orb_search_by_match_bird_frame(orb_ctx* h, float nnratio, int check_ori, flo
                                    const uint8_t* desc_last, const orb_keypoint* kps_last, const uint8_t* has_mp_last,
                                    int n_cur, const uint8_t* desc_cur, const orb_keypoint* kps_cur,
                                    orb_frame_grid grid_cur, int* match_cur, int* nmatches_out) {
+    const char* const fn = "orb_search_by_match_bird_frame";
     if (n_last < 0 || n_cur < 0 || (n_cur && !match_cur) || (n_last && (!desc_last || !kps_last)) ||
-        (n_cur && (!desc_cur || !kps_cur)) || !grid_cur.cell_off || (grid_cur.cell_off[64 * 48] && !grid_cur.cell_idx))
-        return set_error("orb_search_by_match_bird_frame: bad arguments", hipSuccess), ORB_ERR_ARG;
-    if (const char* why = grid_csr_fault(grid_cur, n_cur))
-        return set_error((std::string("orb_search_by_match_bird_frame: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
+        (n_cur && (!desc_cur || !kps_cur)))
+        return arg_error(fn, "bad arguments");
+    if (const char* why = grid_csr_fault(grid_cur, n_cur)) return arg_error(fn, why);
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     std::vector<int> vnMatches12((size_t)std::max(n_last, 1), -1);
@@ -1321,22 +1273,19 @@ int orb_search_by_match_bird_frame(orb_ctx* h, float nnratio, int check_ori, flo
  * distance over the gated candidates, every target's items in one k_projection_best launch (orbgpu.h). */
 int orb_project_best_batch(orb_ctx* h, int gate, int ntargets, const orb_proj_target* targets) {
     // everything is checked before the context and before any output is written: nothing runs if a target is malformed
-    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE)
-        return set_error("orb_project_best_batch: unknown gate", hipSuccess), ORB_ERR_ARG;
-    if (ntargets < 0 || (ntargets > 0 && !targets))
-        return set_error("orb_project_best_batch: ntargets < 0 or targets NULL", hipSuccess), ORB_ERR_ARG;
+    const char* const fn = "orb_project_best_batch";
+    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE) return arg_error(fn, "unknown gate");
+    if (ntargets < 0 || (ntargets > 0 && !targets)) return arg_error(fn, "ntargets < 0 or targets NULL");
     size_t nitems = 0, nused = 0;
     for (int k = 0; k < ntargets; k++) {
         if (const char* why = proj_target_fault(gate, targets[k], 0, targets[k].nq))
-            return set_error(("orb_project_best_batch: target " + std::to_string(k) + ": " + why).c_str(), hipSuccess),
-                   ORB_ERR_ARG;
+            return arg_error(fn, "target " + std::to_string(k) + ": " + why);
         if (targets[k].nq > 0 && targets[k].nt > 0) {
             nitems += (size_t)targets[k].nq;
             nused++;
         }
     }
-    if (nitems > (size_t)INT_MAX / 2)
-        return set_error("orb_project_best_batch: too many queries", hipSuccess), ORB_ERR_ARG;
+    if (nitems > (size_t)INT_MAX / 2) return arg_error(fn, "too many queries");
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     for (int k = 0; k < ntargets; k++)
@@ -1344,7 +1293,7 @@ int orb_project_best_batch(orb_ctx* h, int gate, int ntargets, const orb_proj_ta
     if (nitems == 0) return ORB_OK;
     // the staging area: [table | item -> table row | queries | query descriptors | per used target: descriptors,
     // keypoints, uright, inv_sigma2, cell_off, cell_idx] in one DMA, then the outputs the kernel writes into the mirror
-    const int ncells = 64 * 48;
+    const int ncells = kFrameGridCells;
     Stage st{c};
     const size_t o_tab = st.add(nused * sizeof(ProjTarget)), o_item = st.add(nitems * 4),
                  o_pq = st.add(nitems * sizeof(orb_proj_query)), o_q = st.add(nitems * 32);
@@ -1408,15 +1357,13 @@ int orb_project_best_batch(orb_ctx* h, int gate, int ntargets, const orb_proj_ta
 }
 
 int orb_project_best_host(int gate, const orb_proj_target* target, int query, int* best_idx, int* best_dist) {
-    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE)
-        return set_error("orb_project_best_host: unknown gate", hipSuccess), ORB_ERR_ARG;
-    if (!target || !best_idx || !best_dist || query < 0 || query >= target->nq)
-        return set_error("orb_project_best_host: bad arguments", hipSuccess), ORB_ERR_ARG;
+    const char* const fn = "orb_project_best_host";
+    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE) return arg_error(fn, "unknown gate");
+    if (!target || !best_idx || !best_dist || query < 0 || query >= target->nq) return arg_error(fn, "bad arguments");
     orb_proj_target T = *target;   // (the target's own outputs are not this call's: not required, not touched)
     T.best_idx = best_idx;
     T.best_dist = best_dist;
-    if (const char* why = proj_target_fault(gate, T, query, query + 1))
-        return set_error((std::string("orb_project_best_host: ") + why).c_str(), hipSuccess), ORB_ERR_ARG;
+    if (const char* why = proj_target_fault(gate, T, query, query + 1)) return arg_error(fn, why);
     proj_best_one(gate, T, T.q[query], T.qdesc + (size_t)query * 32, best_idx, best_dist);
     return ORB_OK;
 }
@@ -1424,7 +1371,7 @@ int orb_project_best_host(int gate, const orb_proj_target* target, int query, in
 /* Frame::GetFeaturesInArea over the Frame grid (Frame.cc:378-392, 494-560) */
 int orb_features_in_area(int n, const orb_keypoint* kps_un, float mnMinX, float mnMaxX, float mnMinY, float mnMaxY,
                          float x, float y, float r, int minLevel, int maxLevel, int* out, int cap) {
-    const int COLS = 64, ROWS = 48;   // Frame.h:39-40
+    const int COLS = kFrameGridCols, ROWS = kFrameGridRows;
     const float gw = static_cast<float>(COLS) / static_cast<float>(mnMaxX - mnMinX);
     const float gh = static_cast<float>(ROWS) / static_cast<float>(mnMaxY - mnMinY);
     std::vector<std::vector<int>> grid((size_t)COLS * ROWS);

@@ -36,6 +36,11 @@ constexpr int kRrTileH = 32;
 constexpr int kRrStrip = 8;
 constexpr int kRrMaxRows = 64;        // source rows of a tile it stages at most (8 per staging pass)
 constexpr int kRrMaxChunks = 32;      // 16-byte chunks of a source row it stages at most (one per staging lane)
+// the Frame grid (FRAME_GRID_COLS / FRAME_GRID_ROWS, Frame.h:39-40): an orb_frame_grid's cell_off has
+// kFrameGridCells + 1 entries, cell (ix, iy) at ix * kFrameGridRows + iy
+constexpr int kFrameGridCols = 64;
+constexpr int kFrameGridRows = 48;
+constexpr int kFrameGridCells = kFrameGridCols * kFrameGridRows;
 
 // Per-level geometry (host-computed once per image size; lives in device memory).
 struct LevelGeom {

@@ -310,6 +310,16 @@ def frame_grid(kps_un, min_x, max_x, min_y, max_y):
     return float(inv_w), float(inv_h), np.cumsum(off).astype(np.int32), order.astype(np.int32)
 
 
+def _frame_grid_arg(grid, min_xy=(0.0, 0.0)):
+    """A frame_grid(...) tuple as the C-ABI's orb_frame_grid, and the arrays it points into, which the caller keeps
+    alive for as long as the struct is in use.  An empty cell_idx goes down as one unused slot, not as a NULL."""
+    inv_w, inv_h, off, idx = grid
+    off = np.ascontiguousarray(off, np.int32)
+    idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
+    g = OrbFrameGrid(float(min_xy[0]), float(min_xy[1]), inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+    return g, (off, idx)
+
+
 def proj_queries(u, v, radius, level, ur=None, level_above=0, angle=None):
     """PROJ_QUERY_DTYPE array of projected map points with predicted levels `level`: the window (u, v, radius), the
     level range (level - 1, level + level_above), ur (Fuse's gate), angle (the rotation check); blocks = 1."""
@@ -334,7 +344,6 @@ class _ProjTargets:
         self.keep, self.out = [], []
         self.arr = (OrbProjTarget * max(len(targets), 1))()
         for k, t in enumerate(targets):
-            inv_w, inv_h, off, idx = t["grid"]
             q = np.ascontiguousarray(t["q"], PROJ_QUERY_DTYPE)
             qd = np.ascontiguousarray(t["qdesc"], np.uint8).reshape(-1, 32)
             td = np.ascontiguousarray(t["tdesc"], np.uint8).reshape(-1, 32)
@@ -343,14 +352,11 @@ class _ProjTargets:
             ur = None if t.get("t_uright") is None else np.ascontiguousarray(t["t_uright"], np.float32)
             inv = None if t.get("inv_sigma2") is None else np.ascontiguousarray(t["inv_sigma2"], np.float32)
             assert ur is None or len(ur) == len(kt)
-            off = np.ascontiguousarray(off, np.int32)
-            idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
-            mx, my = t.get("min_xy", (0.0, 0.0))
+            g, grid_arrays = _frame_grid_arg(t["grid"], t.get("min_xy", (0.0, 0.0)))
             bi, bd = np.full(max(len(q), 1), -1, np.int32), np.full(max(len(q), 1), -1, np.int32)
-            g = OrbFrameGrid(float(mx), float(my), inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
             self.arr[k] = OrbProjTarget(len(q), _p(q), _p(qd), len(kt), _p(td), _p(kt), _p(ur), _p(inv),
                                         0 if inv is None else len(inv), g, _p(bi), _p(bd))
-            self.keep.append((q, qd, td, kt, ur, inv, off, idx))
+            self.keep.append((q, qd, td, kt, ur, inv) + grid_arrays)
             self.out.append((bi[:len(q)], bd[:len(q)]))
 
 
@@ -541,11 +547,9 @@ class ORBmatcher:
     def window_match_grid(self, level0_only, desc1, kps1, desc2, kps2, grid, window, centres=None, min_xy=(0.0, 0.0)):
         """orb_window_match_grid: the window searches with GetFeaturesInArea on the device over F2's grid
         (frame_grid(...)); centres: (n1, 2) float32 window centres or None = kps1 positions."""
-        inv_w, inv_h, off, idx = grid
         a = [np.ascontiguousarray(x) for x in (desc1, np.asarray(kps1, KP_DTYPE), desc2, np.asarray(kps2, KP_DTYPE))]
         cen = None if centres is None else np.ascontiguousarray(centres, np.float32).reshape(-1, 2)
-        idx = idx if len(idx) else np.zeros(1, np.int32)
-        g = OrbFrameGrid(float(min_xy[0]), float(min_xy[1]), inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+        g, _grid_arrays = _frame_grid_arg(grid, min_xy)
         out = np.full(max(len(a[0]), 1), -1, np.int32)
         nm = ctypes.c_int()
         check(lib().orb_window_match_grid(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation), int(level0_only),
@@ -560,7 +564,6 @@ class ORBmatcher:
         t_uright (mvuRight; None = no stereo gate) and t_taken (mvpMapPoints[t] && Observations() > 0; None = none).
         Returns (nmatches, match_t): match_t[t] = the last query assigned to train t, -1 = untouched, -2 = reset
         by the rotation cull."""
-        inv_w, inv_h, off, idx = grid
         qa = np.ascontiguousarray(queries, PROJ_QUERY_DTYPE)
         qd = np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
         td = np.ascontiguousarray(tdesc, np.uint8).reshape(-1, 32)
@@ -569,9 +572,7 @@ class ORBmatcher:
         ur = None if t_uright is None else np.ascontiguousarray(t_uright, np.float32)
         tk = None if t_taken is None else np.ascontiguousarray(t_taken, np.uint8)
         assert (ur is None or len(ur) == len(kt)) and (tk is None or len(tk) == len(kt))
-        off = np.ascontiguousarray(off, np.int32)
-        idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
-        g = OrbFrameGrid(float(min_xy[0]), float(min_xy[1]), inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+        g, _grid_arrays = _frame_grid_arg(grid, min_xy)
         out = np.full(max(len(kt), 1), -1, np.int32)
         nm = ctypes.c_int()
         check(lib().orb_search_by_projection(self._ctx.h, int(mode), self.mfNNratio, int(self.mbCheckOrientation),
@@ -645,7 +646,6 @@ class ORBmatcher:
         pKF->mvKeysBird[k].pt and .angle, the map point's descriptor; the Frame's mDescriptorsBird, mvKeysBird and
         birdview grid.  Returns (nmatches, match_bird): match_bird[t] = the k whose map point feature t now holds,
         -1 = untouched, -2 = reset by the rotation cull; nmatches is the reference's return value."""
-        inv_w, inv_h, off, idx = grid_bird
         ids = np.ascontiguousarray(index, np.int32)
         xy = np.ascontiguousarray(np.stack([np.asarray(pt_x, np.float32), np.asarray(pt_y, np.float32)], 1))
         ang = np.ascontiguousarray(angle, np.float32)
@@ -653,9 +653,7 @@ class ORBmatcher:
         td = np.ascontiguousarray(desc_bird, np.uint8).reshape(-1, 32)
         kt = np.ascontiguousarray(kps_bird, KP_DTYPE)
         assert len(ids) == len(xy) == len(ang) == len(qd) and len(td) == len(kt)
-        off = np.ascontiguousarray(off, np.int32)
-        idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
-        g = OrbFrameGrid(0.0, 0.0, inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+        g, _grid_arrays = _frame_grid_arg(grid_bird)
         out = np.full(max(len(kt), 1), -1, np.int32)
         nm = ctypes.c_int()
         check(lib().orb_search_by_match_bird(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation), int(max_dist),
@@ -668,16 +666,13 @@ class ORBmatcher:
         BirdviewMatch(LastFrame, CurrentFrame) over CurrentFrame's birdview grid, then the carry-over of
         LastFrame.mvpMapPointsBird.  has_mp_last[k] = mvpMapPointsBird[k] != NULL (None: none).  Returns (nmatches,
         match_cur): match_cur[i] = the LastFrame feature whose map point CurrentFrame feature i receives, else -1."""
-        inv_w, inv_h, off, idx = grid_cur
         dl = np.ascontiguousarray(desc_last, np.uint8).reshape(-1, 32)
         kl = np.ascontiguousarray(kps_last, KP_DTYPE)
         dc = np.ascontiguousarray(desc_cur, np.uint8).reshape(-1, 32)
         kc = np.ascontiguousarray(kps_cur, KP_DTYPE)
         mp = None if has_mp_last is None else np.ascontiguousarray(has_mp_last, np.uint8)
         assert len(dl) == len(kl) and len(dc) == len(kc) and (mp is None or len(mp) == len(kl))
-        off = np.ascontiguousarray(off, np.int32)
-        idx = np.ascontiguousarray(idx, np.int32) if len(idx) else np.zeros(1, np.int32)
-        g = OrbFrameGrid(0.0, 0.0, inv_w, inv_h, off.ctypes.data, idx.ctypes.data)
+        g, _grid_arrays = _frame_grid_arg(grid_cur)
         out = np.full(max(len(kc), 1), -1, np.int32)
         nm = ctypes.c_int()
         check(lib().orb_search_by_match_bird_frame(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation),

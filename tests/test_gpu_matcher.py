@@ -269,6 +269,28 @@ def test_exhaustion_rerank_path(orbgpu_mod, oracle_mod):
     assert n2 == on2 and np.array_equal(m2, om2)
 
 
+def test_exhaustion_rerank_path_grid(orbgpu_mod, oracle_mod):
+    # test_exhaustion_rerank_path's data through orb_window_match_grid: every keypoint at (0, 0) on octave 0, so
+    # each query's window holds all 40 trains.  Query i skips trains 0..i-1 (vMatchedDistance <= dist,
+    # ORBmatcher.cc:444-445) and takes train i (i < 0.99 (i + 1), :459-461); queries 8..39 find their 8-entry lists
+    # exhausted and are decided only after a re-rank in grid mode.
+    base = np.random.default_rng(5).integers(0, 256, 32, dtype=np.uint8)
+    bits = np.unpackbits(base)
+    t = np.array([np.packbits(bits ^ (np.arange(256) < d)) for d in range(40)], np.uint8)
+    q = np.repeat(base[None], 40, 0)
+    assert [int(np.unpackbits(base ^ x).sum()) for x in t] == list(range(40))
+    k = np.zeros(40, orbgpu_mod.KP_DTYPE)
+    m = orbgpu_mod.ORBmatcher(0.99, True)
+    n, m12 = m.window_match_grid(True, q, k, t, k, orbgpu_mod.frame_grid(k, 0, 640, 0, 480), 10)
+    assert n == 40 and np.array_equal(m12, np.arange(40))
+    off = np.arange(0, 41 * 40, 40, dtype=np.int32)
+    cand = np.tile(np.arange(40, dtype=np.int32), 40)
+    on, om = oracle_mod.window_match(0.99, True, True, q, k, t, k, off, cand)
+    assert n == on and np.array_equal(m12, om)
+    n2, m2 = m.SearchForInitialization(q, k, t, k, off, cand)
+    assert n == n2 and np.array_equal(m12, m2)
+
+
 @pytest.mark.parametrize("only_stereo,check_ori,far_epipole", [(False, False, True), (False, True, False),
                                                                (True, False, True)])
 def test_search_for_triangulation(orbgpu_mod, oracle_mod, frames, only_stereo, check_ori, far_epipole):

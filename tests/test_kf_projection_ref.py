@@ -160,6 +160,11 @@ def test_project_best_batch_rejects_malformed_targets(orbgpu_mod):
     assert call(0, grid(first)) == (-1, P + "grid cell_off[0] != 0")
     assert call(0, grid(dec)) == (-1, P + "grid cell_off decreases")
     assert call(1, grid(oob)) == (-1, P + "grid index out of range")
+
+    def dec_and_nan(t):   # two faults: the grid is checked with the other pointers, ahead of the query values
+        grid(dec)(t)
+        q_field("u", 5, np.nan)(t)
+    assert call(0, dec_and_nan) == (-1, P + "grid cell_off decreases")
     assert call(1, post(lambda s: setattr(s, "inv_sigma2", None))) == (-1, P + "inv_sigma2 NULL")
     assert call(0, post(lambda s: setattr(s, "inv_sigma2", None))) == (-1, "NULL context")
     for n in (0, 17):

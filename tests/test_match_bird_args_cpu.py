@@ -88,6 +88,17 @@ def test_keyframe_form_refusals(env):
     assert _kf(e, max_dist=0) == (-1, "NULL context") and _kf(e, max_dist=256, r=0.0) == (-1, "NULL context")
 
 
+def test_grid_is_checked_before_the_query_values(env):
+    """The Frame grid is checked with the other pointers, ahead of the per-query values: a call with two faults
+    reports the grid's (a NULL one as "bad arguments")."""
+    e, name = env, "orb_search_by_match_bird: "
+    nan_xy, neg_id = _with(e["xy"], 7, np.nan), _with(e["ids"], 3, -1)
+    assert _kf(e, xy=nan_xy, off=_with(e["off"], 100, 3)) == (-1, name + "grid cell_off decreases")
+    assert _kf(e, ids=neg_id, idx=_with(e["idx"], 7, N)) == (-1, name + "grid index out of range")
+    assert _kf(e, xy=nan_xy, off=None) == (-1, name + "bad arguments")
+    assert _kf(e, r=np.nan, off=_with(e["off"], 0, 1)) == (-1, name + "radius not finite or negative")   # (a scalar)
+
+
 def test_frame_form_refusals(env):
     e = env
     assert _frame(e) == (-1, "NULL context")

@@ -277,3 +277,15 @@ def test_argument_errors_before_any_gpu_work(orbgpu_mod):
     assert _call(orbgpu_mod, idx=idx) == (-1, "orb_search_by_projection: grid index out of range")
     # an index equal to a smaller nt is out of range too
     assert _call(orbgpu_mod, nt=9)[1] == "orb_search_by_projection: grid index out of range"
+
+
+def test_grid_is_checked_before_the_query_values(orbgpu_mod):
+    """The Frame grid is checked with the other pointers, ahead of the per-query values: a call with a malformed CSR
+    and a non-finite query reports the CSR."""
+    q = np.zeros(3, orbgpu_mod.PROJ_QUERY_DTYPE)
+    q["u"][1] = np.nan
+    bad = np.zeros(64 * 48 + 1, np.int32)
+    bad[5:] = 10
+    bad[100] = 3
+    assert _call(orbgpu_mod, q=q, off=bad) == (-1, "orb_search_by_projection: grid cell_off decreases")
+    assert _call(orbgpu_mod, q=q, max_dist=257) == (-1, "orb_search_by_projection: max_dist outside [0, 256]")
