@@ -3,6 +3,8 @@ ORBmatcher.cc — match indices bit-exact."""
 import numpy as np
 import pytest
 
+from top2_cases import top2_numpy as _top2_numpy
+
 pytestmark = pytest.mark.gpu
 
 
@@ -827,23 +829,11 @@ def test_top2_frames_pair_list_changes(orbgpu_mod):
     bx.close()
 
 
-def _top2_numpy(dq, dt):
-    """(best, first argmin, second) of the 256-bit Hamming distances, DescriptorDistance
-    (ORBmatcher.cc:1647-1663) as a popcount of the XOR of four u64 words."""
-    a = np.ascontiguousarray(dq).view(np.uint64)
-    b = np.ascontiguousarray(dt).view(np.uint64)
-    D = np.zeros((len(a), len(b)), np.int32)
-    for w in range(4):
-        D += np.bitwise_count(a[:, w, None] ^ b[None, :, w]).astype(np.int32)
-    srt = np.partition(D, 1, axis=1) if D.shape[1] > 1 else D
-    return D.min(1), D.argmin(1), srt[:, 1] if D.shape[1] > 1 else np.full(len(a), 257)
-
-
 def test_top2_frames_bench_shape(orbgpu_mod):
     """The Hamming half of the headline metric exactly as bench.py times it: B = 256 C3 frames
     (1280x720, 2000 features, bench_frames), the 255 consecutive pairs f -> f+1 in ONE
     orb_hamming_top2_frames_device launch.  At this shape top2_batch_slices gives one train slice, so
-    k_top2_mfma writes best / index / second directly (hamming_kernels.hip, gridDim.y == 1 branch; no
+    k_top2_mfma writes best / index / second directly (hamming_top2.hip, nslices == 1 branch; no
     k_top2b_merge).  Pairs 0, 127 and 254 against numpy on the downloaded descriptors: best distance,
     first index on ties (SearchByBoW's strict '<', ORBmatcher.cc:216-225) and the second distance."""
     from orbgpu import _lib
