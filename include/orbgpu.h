@@ -494,6 +494,10 @@ int orb_features_in_area(int n, const orb_keypoint* kps_un, float min_x, float m
 
 /* ======================= Frame::ComputeStereoMatches ======================= */
 
+/* The descriptor search keeps its running best as dist << 24 | right index: at most this many right keypoints
+ * (nR of orb_compute_stereo_matches, kp_cap of the batch behind orb_stereo_batch_device); more is ORB_ERR_ARG. */
+#define ORB_STEREO_MAX_RIGHT ((1 << 24) - 1)
+
 /* void Frame::ComputeStereoMatches()  Frame.cc:662-836, for one rectified pair.  `left` / `right` are
  * the contexts that extracted the left / right image last (orb_extract; the reference's
  * mpORBextractorLeft/Right, whose mvImagePyramid the window search reads), same image size.  They may sit
@@ -501,14 +505,14 @@ int orb_features_in_area(int n, const orb_keypoint* kps_un, float min_x, float m
  * device with hipMemcpyPeerAsync and the search runs there.  kpsL/descL = mvKeys/mDescriptors (nL),
  * kpsR/descR = mvKeysRight/mDescriptorsRight (nR);
  * mb = baseline, mbf = baseline * fx.  uright / depth (nL each) receive mvuRight / mvDepth
- * (-1 = no match); *nmatched = number of left keypoints with a depth.  Synchronous. */
+ * (-1 = no match); *nmatched = number of left keypoints with a depth.  nR <= ORB_STEREO_MAX_RIGHT.  Synchronous. */
 int orb_compute_stereo_matches(orb_ctx* left, orb_ctx* right, int nL, const orb_keypoint* kpsL, const uint8_t* descL,
                                int nR, const orb_keypoint* kpsR, const uint8_t* descR, float mb, float mbf,
                                float* uright, float* depth, int* nmatched);
 
 /* Device-resident batched form: frames (2p, 2p+1) of the last orb_extract_batch_device on ctx are
  * the (left, right) images of pair p.  Outputs at d_uright/d_depth[p * kp_cap + i] (kp_cap of that
- * batch) and d_nmatched[p].  Asynchronous on the context stream. */
+ * batch) and d_nmatched[p].  kp_cap <= ORB_STEREO_MAX_RIGHT.  Asynchronous on the context stream. */
 int orb_stereo_batch_device(orb_ctx* ctx, int npairs, float mb, float mbf, float* d_uright, float* d_depth,
                             int* d_nmatched);
 

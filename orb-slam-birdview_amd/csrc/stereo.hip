@@ -26,6 +26,8 @@ constexpr int kThHigh = 100;                      // ORBmatcher.cc:37
 constexpr int kThOrbDist = (kThHigh + 50) / 2;    // Frame.cc:667
 constexpr int kWin = 5;                           // :758 w
 constexpr int kRange = 5;                         // :765 L
+constexpr int kStereoMaxRight = (1 << 24) - 1;    // k_stereo packs dist << 24 | iR (ORB_STEREO_MAX_RIGHT)
+static_assert(kStereoMaxRight == ORB_STEREO_MAX_RIGHT, "orbgpu.h states the limit");
 
 __device__ __forceinline__ const uint8_t* level_base(const Geom* __restrict__ g, const StereoSide& s, int f, int l,
                                                      int& stride) {
@@ -68,7 +70,7 @@ __device__ __forceinline__ int block256_scan(int v, int* s_w, int& total) {
 
 // Right keypoints bucketed by image row (counting sort in LDS, one workgroup per pair): the
 // descriptor search of a left keypoint then visits only the rows its band can reach instead of
-// every right keypoint.  Order inside a row is irrelevant (the search minimises dist << 16 | iR).
+// every right keypoint.  Order inside a row is irrelevant (the search minimises dist << 24 | iR).
 __global__ __launch_bounds__(256) void k_stereo_bucket(const Geom* __restrict__ g, StereoSide R,
                                                        int* __restrict__ rows, int* __restrict__ sorted,
                                                        long long row_stride, long long out_stride) {
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(256) void k_stereo(const Geom* __restrict__ g, Ster
     const int levelL = kpL.octave;
 
     // ---- descriptor search over the right keypoints whose row band covers yL (:676-689, :716-745)
-    unsigned best = 0xFFFFFFFFu;   // dist << 16 | iR: the first minimum in iR order
+    unsigned best = 0xFFFFFFFFu;   // dist << 24 | iR (dist < 100, iR <= kStereoMaxRight): the first minimum in iR order
     if (maxU >= 0) {
         // a right keypoint reaches rows [floor(y - r), ceil(y + r)], r = 2 * scale <= 2 * scale_max
         const int reach = (int)ceilf(2.0f * g->L[g->nlevels - 1].scale) + 1;
@@ -146,7 +148,7 @@ __global__ __launch_bounds__(256) void k_stereo(const Geom* __restrict__ g, Ster
             if (kr.octave < levelL - 1 || kr.octave > levelL + 1) continue;
             if (!(kr.x >= minU && kr.x <= maxU)) continue;
             const int dist = hamming256(qa, qb, dR[2 * iR], dR[2 * iR + 1]);
-            if (dist < kThHigh) best = min(best, ((unsigned)dist << 16) | (unsigned)iR);
+            if (dist < kThHigh) best = min(best, ((unsigned)dist << 24) | (unsigned)iR);
         }
     }
 #pragma unroll
@@ -154,9 +156,9 @@ __global__ __launch_bounds__(256) void k_stereo(const Geom* __restrict__ g, Ster
 
     float outU = -1.0f, outD = -1.0f;
     int outS = -1;
-    if (best != 0xFFFFFFFFu && (int)(best >> 16) < kThOrbDist) {
+    if (best != 0xFFFFFFFFu && (int)(best >> 24) < kThOrbDist) {
         // ---- sliding-window search at the keypoint's scale (:750-788)
-        const int bestIdxR = (int)(best & 0xFFFF);
+        const int bestIdxR = (int)(best & 0xFFFFFF);
         const float uR0 = kR[bestIdxR].x;
         const float scaleFactor = 1.0f / g->L[levelL].scale;   // mvInvScaleFactors (ORBextractor.cc:428-429)
         const float scaleduL = roundf(uL * scaleFactor);
@@ -366,6 +368,8 @@ int orb_compute_stereo_matches(orb_ctx* left, orb_ctx* right, int nL, const orb_
         return set_error("orb_compute_stereo_matches: both contexts must have extracted an image of one size",
                          hipSuccess),
                ORB_ERR_ARG;
+    if (nR > kStereoMaxRight)
+        return set_error("orb_compute_stereo_matches: more than 16,777,215 right keypoints", hipSuccess), ORB_ERR_ARG;
     if (nL == 0) {
         if (nmatched) *nmatched = 0;
         return ORB_OK;
@@ -457,6 +461,8 @@ int orb_stereo_batch_device(orb_ctx* h, int npairs, float mb, float mbf, float* 
         return set_error("orb_stereo_batch_device: the last batch holds fewer than 2*npairs frames", hipSuccess),
                ORB_ERR_ARG;
     const int cap = c->last_kp_cap;
+    if (cap > kStereoMaxRight)
+        return set_error("orb_stereo_batch_device: kp_cap above 16,777,215", hipSuccess), ORB_ERR_ARG;
     const size_t need = stereo_scratch_ints(c->geom, npairs, cap) * 4 + 256;
     hipError_t e;
     if (need > c->scratch_cap || !c->d_scratch) {

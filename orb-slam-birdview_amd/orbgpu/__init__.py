@@ -142,7 +142,8 @@ class ORBextractor(_Ctx):
         if img.size == 0:
             return keypoints, descriptors
         assert img.dtype == np.uint8 and img.ndim == 2, "CV_8UC1 expected (ORBextractor.cc:1050)"
-        img = np.ascontiguousarray(img)
+        if not (img.strides[1] == 1 and img.strides[0] >= img.shape[1]):   # rows with padding go down as they are
+            img = np.ascontiguousarray(img)
         h, w = img.shape
         cap = 4 * max(self.params.nfeatures, 1) + 256
         while True:
