@@ -445,7 +445,9 @@ int orb_search_by_match_bird(orb_ctx* ctx, float nnratio, int check_ori, int max
  * NULL and level0_only = 0 over CurrentFrame's birdview grid, one GPU call; then on the host, for each k with
  * vnMatches12[k] >= 0 and has_mp_last[k] != 0 (LastFrame.mvpMapPointsBird[k] != NULL): match_cur[vnMatches12[k]] = k.
  * match_cur: n_cur ints, -1 = untouched; *nmatches = the carried points (not BirdviewMatch's return value).
- * has_mp_last == NULL: no point carries a map point (0, all -1).  Arguments are checked as orb_window_match_grid's. */
+ * has_mp_last == NULL: no point carries a map point (0, all -1).  Arguments are checked as orb_window_match_grid's.
+ * ("_frame" here names the form between two Frames; the keyframe form over a resident orb_frame handle is
+ * orb_search_by_match_bird_resident.) */
 int orb_search_by_match_bird_frame(orb_ctx* ctx, float nnratio, int check_ori, float window,
                                    int n_last, const uint8_t* desc_last, const orb_keypoint* kps_last,
                                    const uint8_t* has_mp_last, int n_cur, const uint8_t* desc_cur,
@@ -491,6 +493,70 @@ int orb_project_best_host(int gate, const orb_proj_target* target, int query, in
  * C++ mirror uses to build window candidate lists. Returns count or -(needed)-1. */
 int orb_features_in_area(int n, const orb_keypoint* kps_un, float min_x, float max_x, float min_y, float max_y,
                          float x, float y, float r, int min_level, int max_level, int* out, int cap);
+
+/* ======================= Resident Frame / KeyFrame handles ======================= */
+
+/* The train side of the grid searches, kept on the device: a Frame is searched several times within a few
+ * milliseconds (SearchByProjection and its 2*th retry, SearchLocalPoints, the birdview searches) and a KeyFrame for as
+ * long as it lives (Fuse from every neighbour, SearchBySim3, relocalisation, loop closing).  A handle is created once
+ * from the frame's descriptors (32 B each), undistorted keypoints and, optionally, mvuRight; the library builds the
+ * Frame grid on the GPU (Frame::AssignFeaturesToGrid with PosInGrid, Frame.cc:378-413, :549-559: cell (ix, iy) =
+ * (round((x - min_x) * inv_w), round((y - min_y) * inv_h)) in float, half away from zero, inside iff 0 <= ix < 64 and
+ * 0 <= iy < 48 compared after the rounding; each cell's indices ascend, the order of the reference's push_back loop).
+ * min_x / min_y / inv_w / inv_h are orb_frame_grid's (mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv);
+ * the birdview grid passes its inverses with origin 0.
+ *   orb_frame_create         arrays in host memory
+ *   orb_frame_create_device  arrays in device memory of the context's GPU (e.g. a slot of orb_extract_batch_device's
+ *                            outputs): copied device-to-device on the context's stream, the keypoints come back to the
+ *                            host once (the searches' host replays read octave and angle)
+ * Both synchronise before they return; the handle is then usable with any context of the same device (another device:
+ * ORB_ERR_ARG from the search), from one thread at a time per context as every call here.  It owns one device
+ * allocation and must be destroyed before the context that created it.
+ * ORB_ERR_ARG before any GPU work: n < 0, NULL desc / kps with n > 0, inv_w / inv_h not finite or <= 0, min_x / min_y
+ * not finite, and for orb_frame_create a keypoint x or y that is not finite.  n == 0 is a valid empty frame.
+ * orb_frame_grid_read copies the grid out (cell_off: 64 * 48 + 1 ints; cell_idx: *nslots <= n ints; ORB_ERR_CAPACITY
+ * with *nslots set when cap is smaller). */
+typedef struct orb_frame orb_frame;
+int  orb_frame_create(orb_ctx* ctx, int n, const uint8_t* desc, const orb_keypoint* kps_un, const float* uright,
+                      float min_x, float min_y, float inv_w, float inv_h, orb_frame** out);
+int  orb_frame_create_device(orb_ctx* ctx, int n, const uint8_t* d_desc, const orb_keypoint* d_kps,
+                             const float* d_uright, float min_x, float min_y, float inv_w, float inv_h,
+                             orb_frame** out);
+void orb_frame_destroy(orb_frame* frame);
+int  orb_frame_count(const orb_frame* frame);
+int  orb_frame_grid_read(const orb_frame* frame, int* cell_off, int* cell_idx, int cap, int* nslots);
+
+/* The grid searches with a handle as their train side: every output is byte for byte that of the host-pointer entry
+ * point given the same train data and a grid equal to the handle's, and every argument check of that entry point
+ * applies (before the context is touched or any output is written); a NULL handle or one of another device is
+ * ORB_ERR_ARG.  Nothing of the train side is staged or uploaded.  nq == 0 (n1 == 0) or an empty frame: ORB_OK, the
+ * outputs -1 and 0, no GPU work.
+ *   orb_search_by_projection_frame  = orb_search_by_projection; use_uright = 0 is t_uright == NULL (mono, birdview,
+ *     the keyframe forms), use_uright = 1 gates on the handle's uright (ORB_ERR_ARG if it was created without).
+ *   orb_window_match_frame          = orb_window_match_grid with F2 as a handle.
+ *   orb_search_by_match_bird_resident = orb_search_by_match_bird, the KEYFRAME form (queries = map points of a
+ *     keyframe, trains = the Frame's birdview features, here a handle over mvKeysBird / mDescriptorsBird and the
+ *     birdview grid).  Not to be confused with orb_search_by_match_bird_frame, the form between two Frames
+ *     (SearchByMatchBird(CurrentFrame, LastFrame, windowSize)), which takes host arrays.
+ *   orb_project_best_frames         = orb_project_best_batch with each target's trains as a handle (gate FUSE reads
+ *     the handle's uright if it has one; inv_sigma2 / nlevels stay per target). */
+int orb_search_by_projection_frame(orb_ctx* ctx, int mode, float nnratio, int check_ori, int max_dist,
+                                   int nq, const orb_proj_query* q, const uint8_t* qdesc, const orb_frame* frame,
+                                   const uint8_t* t_taken, int use_uright, int* match_t, int* nmatches);
+int orb_window_match_frame(orb_ctx* ctx, float nnratio, int check_ori, int level0_only,
+                           int n1, const uint8_t* desc1, const orb_keypoint* kps1, const float* centres,
+                           float window, const orb_frame* frame2, int* match12, int* nmatches);
+int orb_search_by_match_bird_resident(orb_ctx* ctx, float nnratio, int check_ori, int max_dist, float r,
+                                      int nq, const int* q_id, const float* q_xy, const float* q_angle,
+                                      const uint8_t* qdesc, const orb_frame* frame, int* match_t, int* nmatches);
+typedef struct orb_proj_frame_target {
+    int nq; const orb_proj_query* q; const uint8_t* qdesc;   /* as orb_proj_target's */
+    const orb_frame* frame;     /* the keyframe */
+    const float* inv_sigma2;    /* mvInvLevelSigma2, nlevels entries (gate FUSE only) */
+    int nlevels;
+    int* best_idx; int* best_dist;
+} orb_proj_frame_target;
+int orb_project_best_frames(orb_ctx* ctx, int gate, int ntargets, const orb_proj_frame_target* targets);
 
 /* ======================= Frame::ComputeStereoMatches ======================= */
 

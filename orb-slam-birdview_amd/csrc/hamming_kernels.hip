@@ -290,16 +290,16 @@ __global__ __launch_bounds__(256) void k_projection_topk(const orb_proj_query* _
 // The searches that decide every projected point on its own: Fuse(KeyFrame*, vector<MapPoint*>, th) (:892-949,
 // GATE 1), Fuse(KeyFrame*, Scw, ...) (:1051-1079) and both directions of SearchBySim3 (:1191-1219, :1271-1299)
 // (GATE 0).  One wavefront per (target, query) item, the items of all targets in one launch; the item's target row
-// gives where its keyframe's descriptors, keypoints, mvuRight, mvInvLevelSigma2 and grid CSR lie in the staging
-// area.  The walk is k_projection_topk's (KeyFrame::GetFeaturesInArea is Frame::GetFeaturesInArea without levels;
-// the level filter of the callers is the query's (min_level, max_level)); a lane keeps one key dist << 32 | slot
-// (a slot is the candidate's rank in vIndices), so the wave minimum is the reference's first minimum.
+// gives where its keyframe's descriptors, keypoints, mvuRight, mvInvLevelSigma2 and grid CSR lie (device pointers:
+// the call's staging area, or a resident frame).  The walk is k_projection_topk's (KeyFrame::GetFeaturesInArea is
+// Frame::GetFeaturesInArea without levels; the level filter of the callers is the query's (min_level, max_level));
+// a lane keeps one key dist << 32 | slot (a slot is the candidate's rank in vIndices), so the wave minimum is the
+// reference's first minimum.
 // GATE 1: the chi-square reprojection test of :914-938 in the reference build's contracted forms
 // (tools/fuse_flags_probe.cpp; this file builds -ffp-contract=off, so the fmaf below are the only fused operations);
 // the octave indexes inv_sigma2, which the host validated.  Waves past the last item stay in with an empty window.
 template <int GATE>
-__global__ __launch_bounds__(256) void k_projection_best(const uint8_t* __restrict__ base,
-                                                         const ProjTarget* __restrict__ tab,
+__global__ __launch_bounds__(256) void k_projection_best(const ProjTarget* __restrict__ tab,
                                                          const int* __restrict__ item_tgt,
                                                          const orb_proj_query* __restrict__ pq,
                                                          const uint8_t* __restrict__ q, int nitems,
@@ -313,12 +313,12 @@ __global__ __launch_bounds__(256) void k_projection_best(const uint8_t* __restri
     const ProjTarget T = tab[item_tgt[ic]];
     const uint4* qp = reinterpret_cast<const uint4*>(q + (long long)ic * 32);
     const uint4 qa = qp[0], qb = qp[1];
-    const uint8_t* t = base + T.o_t;
-    const orb_keypoint* kps = reinterpret_cast<const orb_keypoint*>(base + T.o_kps);
-    const float* uright = T.o_ur >= 0 ? reinterpret_cast<const float*>(base + T.o_ur) : nullptr;
-    const float* inv_sigma2 = reinterpret_cast<const float*>(base + T.o_inv);
-    const int* cell_off = reinterpret_cast<const int*>(base + T.o_coff);
-    const int* cell_idx = reinterpret_cast<const int*>(base + T.o_cidx);
+    const uint8_t* t = T.t;
+    const orb_keypoint* kps = T.kps;
+    const float* uright = T.ur;
+    const float* inv_sigma2 = T.inv_sigma2;
+    const int* cell_off = T.cell_off;
+    const int* cell_idx = T.cell_idx;
     const ProjGrid g = T.g;
     const float x = P.u, y = P.v, r = P.r;
     const int nMinCellX = max(0, (int)floorf((x - g.min_x - r) * g.inv_w));
@@ -449,15 +449,14 @@ hipError_t launch_projection_topk(const orb_proj_query* d_pq, const uint8_t* d_q
     return hipGetLastError();
 }
 
-hipError_t launch_projection_best(int gate, const uint8_t* d_base, const ProjTarget* d_tab, const int* d_item_tgt,
-                                  const orb_proj_query* d_pq, const uint8_t* d_q, int nitems, int* d_idx, int* d_dist,
-                                  hipStream_t stream) {
+hipError_t launch_projection_best(int gate, const ProjTarget* d_tab, const int* d_item_tgt, const orb_proj_query* d_pq,
+                                  const uint8_t* d_q, int nitems, int* d_idx, int* d_dist, hipStream_t stream) {
     if (nitems <= 0) return hipSuccess;
     if (gate == ORB_PROJ_GATE_FUSE)
-        hipLaunchKernelGGL(k_projection_best<ORB_PROJ_GATE_FUSE>, dim3((nitems + 3) / 4), dim3(256), 0, stream, d_base,
+        hipLaunchKernelGGL(k_projection_best<ORB_PROJ_GATE_FUSE>, dim3((nitems + 3) / 4), dim3(256), 0, stream,
                            d_tab, d_item_tgt, d_pq, d_q, nitems, d_idx, d_dist);
     else if (gate == ORB_PROJ_GATE_NONE)
-        hipLaunchKernelGGL(k_projection_best<ORB_PROJ_GATE_NONE>, dim3((nitems + 3) / 4), dim3(256), 0, stream, d_base,
+        hipLaunchKernelGGL(k_projection_best<ORB_PROJ_GATE_NONE>, dim3((nitems + 3) / 4), dim3(256), 0, stream,
                            d_tab, d_item_tgt, d_pq, d_q, nitems, d_idx, d_dist);
     else
         return hipErrorInvalidValue;

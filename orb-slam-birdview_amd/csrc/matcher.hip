@@ -135,6 +135,9 @@ struct TopkSession {
     ProjGrid pg{};
     bool cen = false;      // GRID: window centres given (else kps1)
     bool has_ur = false;   // PROJ: stereo gate
+    // GRID / PROJ: the train side as a resident frame (else NULL: staged in the arena).  Its descriptors, keypoints,
+    // uright and grid are not laid out or uploaded; the launch takes the handle's device pointers
+    const orb_frame* ext = nullptr;
     int lanes = 64;        // PROJ: lanes per query
     // host results (indexed by item), in the pinned mirror
     const int* dist = nullptr;
@@ -202,9 +205,11 @@ struct TopkSession {
 
     // Grid mode: queries = desc1 rows item_q[i] (uploaded whole, indexed on the device), candidates from
     // the window around centres[item_q[i]] (NULL: kps1) in F2's grid.
+    // F2 given: the train side is that frame (desc2, kps2 and g's CSR are not read; g carries the geometry).
     int setup_grid(const uint8_t* desc1, int n1, const orb_keypoint* kps1, const float* centres, const uint8_t* desc2,
-                   int n2, const orb_keypoint* kps2, const orb_frame_grid& g, float r) {
+                   int n2, const orb_keypoint* kps2, const orb_frame_grid& g, float r, const orb_frame* F2 = nullptr) {
         if (!begin(GRID, (int)item_q.size(), n2)) return ORB_OK;
+        ext = F2;
         wg = WinGrid{g.min_x, g.min_y, g.inv_w, g.inv_h, r};
         cen = centres != nullptr;
         const size_t kp1 = (size_t)n1 * sizeof(orb_keypoint), kp2 = (size_t)n2 * sizeof(orb_keypoint);
@@ -212,18 +217,22 @@ struct TopkSession {
         o_item = st.add((size_t)nitems * 4);
         o_cen = st.add(cen ? (size_t)n1 * 8 : 0);
         o_k1 = st.add(kp1);
-        o_t = st.add((size_t)n2 * 32);
-        o_k2 = st.add(kp2);
-        add_grid(g);
+        if (!ext) {
+            o_t = st.add((size_t)n2 * 32);
+            o_k2 = st.add(kp2);
+            add_grid(g);
+        }
         const int rr = finish_layout();
         if (rr != ORB_OK) return rr;
         put(o_q, desc1, (size_t)n1 * 32);
         put(o_item, item_q.data(), (size_t)nitems * 4);
         if (cen) put(o_cen, centres, (size_t)n1 * 8);
         put(o_k1, kps1, kp1);
-        put(o_t, desc2, (size_t)n2 * 32);
-        put(o_k2, kps2, kp2);
-        put_grid(g);
+        if (!ext) {
+            put(o_t, desc2, (size_t)n2 * 32);
+            put(o_k2, kps2, kp2);
+            put_grid(g);
+        }
         return ORB_OK;
     }
 
@@ -252,6 +261,23 @@ struct TopkSession {
         put_grid(g);
         return ORB_OK;
     }
+    // The same with the train frame resident: only the queries are staged.
+    int setup_proj(int nq, const orb_proj_query* q, const uint8_t* qdesc, const orb_frame* F, bool use_uright,
+                   int nlanes) {
+        if (!begin(PROJ, nq, F->n)) return ORB_OK;
+        ext = F;
+        pg = ProjGrid{F->min_x, F->min_y, F->inv_w, F->inv_h};
+        has_ur = use_uright;
+        lanes = nlanes;
+        const size_t pq = (size_t)nq * sizeof(orb_proj_query);
+        o_pq = st.add(pq);
+        o_q = st.add((size_t)nq * 32);
+        const int rr = finish_layout();
+        if (rr != ORB_OK) return rr;
+        put(o_pq, q, pq);
+        put(o_q, qdesc, (size_t)nq * 32);
+        return ORB_OK;
+    }
 
     // Rank items [from, to) (to < 0: nitems) with train thresholds thr (NULL = admit all).
     int run(int from, const int* thr, int to = -1) {
@@ -269,19 +295,23 @@ struct TopkSession {
         int* const out_dist = st.h<int>(o_dist) + (size_t)from * K;
         int* const out_idx = st.h<int>(o_idx) + (size_t)from * K;
         int* const out_nv = st.h<int>(o_nv) + from;
+        // GRID / PROJ: the train side, staged or resident
+        const uint8_t* const d_t = ext ? ext->d_desc : st.di<uint8_t>(o_t);
+        const orb_keypoint* const d_k2 = ext ? ext->d_kps : st.di<orb_keypoint>(o_k2);
+        const float* const d_ur = !has_ur ? nullptr : ext ? ext->d_ur : st.di<float>(o_ur);
+        const int* const d_coff = ext ? ext->d_coff : st.di<int>(o_coff);
+        const int* const d_cidx = ext ? ext->d_cidx : st.di<int>(o_cidx);
         if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
         switch (mode) {
         case PROJ:
             e = launch_projection_topk(st.di<orb_proj_query>(o_pq) + from, st.di<uint8_t>(o_q) + (size_t)from * 32, n,
-                                       st.di<uint8_t>(o_t), st.di<orb_keypoint>(o_k2),
-                                       has_ur ? st.di<float>(o_ur) : nullptr, st.di<int>(o_coff), st.di<int>(o_cidx), pg,
-                                       d_thr, K, lanes, out_dist, out_idx, out_nv, c->stream);
+                                       d_t, d_k2, d_ur, d_coff, d_cidx, pg, d_thr, K, lanes, out_dist, out_idx, out_nv,
+                                       c->stream);
             break;
         case GRID:
             e = launch_window_topk(st.di<uint8_t>(o_q), st.di<int>(o_item) + from, cen ? st.di<float2>(o_cen) : nullptr, n,
-                                   st.di<orb_keypoint>(o_k1), st.di<uint8_t>(o_t), st.di<orb_keypoint>(o_k2),
-                                   st.di<int>(o_coff), st.di<int>(o_cidx), wg, d_thr, K, out_dist, out_idx, out_nv,
-                                   c->stream);
+                                   st.di<orb_keypoint>(o_k1), d_t, d_k2, d_coff, d_cidx, wg, d_thr, K, out_dist, out_idx,
+                                   out_nv, c->stream);
             break;
         case LIST:
             e = launch_hamming_topk(st.di<uint8_t>(o_q) + (size_t)from * 32, n, st.di<uint8_t>(o_t), nt,
@@ -1048,13 +1078,44 @@ int match_bird_replay(TopkSession& s, float nnratio, int check_ori, int max_dist
     return ORB_OK;
 }
 
-// What is wrong with a target of orb_project_best_batch for its queries [q0, q1), or NULL.  The kernel indexes
-// inv_sigma2 by the train's octave and the trains by the grid's cell_idx, so both are checked here.
-const char* proj_target_fault(int gate, const orb_proj_target& T, int q0, int q1) {
+// A target of the per-query searches as both entry points give it: orb_proj_target's fields, and the resident frame
+// when the trains are one (orb_project_best_frames: nt and kps_t are the frame's count and host keypoints, tdesc,
+// t_uright and the grid's CSR are not read).
+struct ProjView {
+    orb_proj_target T;
+    const orb_frame* F;
+};
+ProjView proj_view(const orb_proj_target& T) { return ProjView{T, nullptr}; }
+ProjView proj_view(const orb_proj_frame_target& R) {
+    const orb_frame* F = R.frame;
+    orb_proj_target T{};
+    T.nq = R.nq;
+    T.q = R.q;
+    T.qdesc = R.qdesc;
+    T.inv_sigma2 = R.inv_sigma2;
+    T.nlevels = R.nlevels;
+    T.best_idx = R.best_idx;
+    T.best_dist = R.best_dist;
+    if (F) {
+        T.nt = F->n;
+        T.kps_t = F->kps.data();
+        T.grid = orb_frame_grid{F->min_x, F->min_y, F->inv_w, F->inv_h, nullptr, nullptr};
+    }
+    return ProjView{T, F};
+}
+
+// What is wrong with a target of orb_project_best_batch / orb_project_best_frames for its queries [q0, q1), or NULL.
+// The kernel indexes inv_sigma2 by the train's octave and the trains by the grid's cell_idx, so both are checked here
+// (a resident frame's CSR is the library's own).
+const char* proj_target_fault(int gate, const ProjView& V, int q0, int q1) {
+    const orb_proj_target& T = V.T;
     if (T.nq < 0 || T.nt < 0) return "negative count";
     if (T.nq > 0 && (!T.best_idx || !T.best_dist)) return "NULL outputs";
-    if ((T.nq > 0 && (!T.q || !T.qdesc)) || (T.nt > 0 && (!T.tdesc || !T.kps_t))) return "bad arguments";
-    if (const char* why = grid_csr_fault(T.grid, T.nt)) return why;
+    if (T.nq > 0 && (!T.q || !T.qdesc)) return "bad arguments";
+    if (!V.F) {
+        if (T.nt > 0 && (!T.tdesc || !T.kps_t)) return "bad arguments";
+        if (const char* why = grid_csr_fault(T.grid, T.nt)) return why;
+    }
     for (int i = q0; i < q1; i++) {
         if (!std::isfinite(T.q[i].u) || !std::isfinite(T.q[i].v) || !std::isfinite(T.q[i].r) || T.q[i].r < 0)
             return "query window not finite or radius negative";
@@ -1269,91 +1330,236 @@ int orb_search_by_match_bird_frame(orb_ctx* h, float nnratio, int check_ori, flo
     return ORB_OK;
 }
 
-/* Fuse (both overloads) and SearchBySim3's two directions: per (target, query) the first minimum of the descriptor
- * distance over the gated candidates, every target's items in one k_projection_best launch (orbgpu.h). */
-int orb_project_best_batch(orb_ctx* h, int gate, int ntargets, const orb_proj_target* targets) {
+}  // extern "C"
+
+namespace orbgpu {
+namespace {
+// orb_project_best_batch and orb_project_best_frames over their common view of the targets (fn: the entry point's
+// name for messages).
+int project_best_run(const char* fn, orb_ctx* h, int gate, const std::vector<ProjView>& targets) {
     // everything is checked before the context and before any output is written: nothing runs if a target is malformed
-    const char* const fn = "orb_project_best_batch";
-    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE) return arg_error(fn, "unknown gate");
-    if (ntargets < 0 || (ntargets > 0 && !targets)) return arg_error(fn, "ntargets < 0 or targets NULL");
+    const int ntargets = (int)targets.size();
     size_t nitems = 0, nused = 0;
     for (int k = 0; k < ntargets; k++) {
-        if (const char* why = proj_target_fault(gate, targets[k], 0, targets[k].nq))
+        const orb_proj_target& T = targets[k].T;
+        if (const char* why = proj_target_fault(gate, targets[k], 0, T.nq))
             return arg_error(fn, "target " + std::to_string(k) + ": " + why);
-        if (targets[k].nq > 0 && targets[k].nt > 0) {
-            nitems += (size_t)targets[k].nq;
+        if (T.nq > 0 && T.nt > 0) {
+            nitems += (size_t)T.nq;
             nused++;
         }
     }
     if (nitems > (size_t)INT_MAX / 2) return arg_error(fn, "too many queries");
     Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
+    for (int k = 0; k < ntargets; k++)
+        if (targets[k].F && targets[k].F->device != c->device)
+            return arg_error(fn, "target " + std::to_string(k) + ": the frame lives on another device");
     CTX_GUARD(c);
     for (int k = 0; k < ntargets; k++)
-        for (int i = 0; i < targets[k].nq; i++) targets[k].best_idx[i] = targets[k].best_dist[i] = -1;
+        for (int i = 0; i < targets[k].T.nq; i++) targets[k].T.best_idx[i] = targets[k].T.best_dist[i] = -1;
     if (nitems == 0) return ORB_OK;
     // the staging area: [table | item -> table row | queries | query descriptors | per used target: descriptors,
-    // keypoints, uright, inv_sigma2, cell_off, cell_idx] in one DMA, then the outputs the kernel writes into the mirror
+    // keypoints, uright, inv_sigma2, cell_off, cell_idx (a resident frame: inv_sigma2 only)] in one DMA, then the
+    // outputs the kernel writes into the mirror
     const int ncells = kFrameGridCells;
     Stage st{c};
     const size_t o_tab = st.add(nused * sizeof(ProjTarget)), o_item = st.add(nitems * 4),
                  o_pq = st.add(nitems * sizeof(orb_proj_query)), o_q = st.add(nitems * 32);
-    std::vector<ProjTarget> tab;
+    struct Offsets {   // (-1: the region is not staged)
+        long long o_t, o_kps, o_ur, o_inv, o_coff, o_cidx;
+    };
+    std::vector<Offsets> tab;
     tab.reserve(nused);
     for (int k = 0; k < ntargets; k++) {
-        const orb_proj_target& T = targets[k];
+        const orb_proj_target& T = targets[k].T;
         if (T.nq == 0 || T.nt == 0) continue;
-        ProjTarget R;
-        R.o_t = (long long)st.add((size_t)T.nt * 32);
-        R.o_kps = (long long)st.add((size_t)T.nt * sizeof(orb_keypoint));
-        R.o_ur = gate == ORB_PROJ_GATE_FUSE && T.t_uright ? (long long)st.add((size_t)T.nt * 4) : -1;
+        Offsets R{-1, -1, -1, -1, -1, -1};
+        if (!targets[k].F) {
+            R.o_t = (long long)st.add((size_t)T.nt * 32);
+            R.o_kps = (long long)st.add((size_t)T.nt * sizeof(orb_keypoint));
+            R.o_ur = gate == ORB_PROJ_GATE_FUSE && T.t_uright ? (long long)st.add((size_t)T.nt * 4) : -1;
+        }
         R.o_inv = gate == ORB_PROJ_GATE_FUSE ? (long long)st.add((size_t)T.nlevels * 4) : 0;
-        R.o_coff = (long long)st.add((size_t)(ncells + 1) * 4);
-        R.o_cidx = (long long)st.add((size_t)T.grid.cell_off[ncells] * 4);
-        R.g = ProjGrid{T.grid.min_x, T.grid.min_y, T.grid.inv_w, T.grid.inv_h};
+        if (!targets[k].F) {
+            R.o_coff = (long long)st.add((size_t)(ncells + 1) * 4);
+            R.o_cidx = (long long)st.add((size_t)T.grid.cell_off[ncells] * 4);
+        }
         tab.push_back(R);
     }
     const size_t o_in_end = st.off;
     const size_t o_idx = st.add(nitems * 4), o_dist = st.add(nitems * 4);
     const int rr = st.alloc();
     if (rr != ORB_OK) return rr;
-    std::memcpy(st.hi<ProjTarget>(o_tab), tab.data(), nused * sizeof(ProjTarget));
     size_t item = 0, row = 0;
     for (int k = 0; k < ntargets; k++) {
-        const orb_proj_target& T = targets[k];
+        const orb_proj_target& T = targets[k].T;
+        const orb_frame* F = targets[k].F;
         if (T.nq == 0 || T.nt == 0) continue;
-        const ProjTarget& R = tab[row];
+        const Offsets& R = tab[row];
+        ProjTarget& D = st.hi<ProjTarget>(o_tab)[row];
+        D.inv_sigma2 = st.di<float>((size_t)R.o_inv);
+        D.g = ProjGrid{T.grid.min_x, T.grid.min_y, T.grid.inv_w, T.grid.inv_h};
         for (int i = 0; i < T.nq; i++) st.hi<int>(o_item)[item + i] = (int)row;
         std::memcpy(st.hi<orb_proj_query>(o_pq) + item, T.q, (size_t)T.nq * sizeof(orb_proj_query));
         std::memcpy(st.hi<uint8_t>(o_q) + item * 32, T.qdesc, (size_t)T.nq * 32);
-        std::memcpy(st.hi<uint8_t>(R.o_t), T.tdesc, (size_t)T.nt * 32);
-        std::memcpy(st.hi<uint8_t>(R.o_kps), T.kps_t, (size_t)T.nt * sizeof(orb_keypoint));
-        if (R.o_ur >= 0) std::memcpy(st.hi<uint8_t>(R.o_ur), T.t_uright, (size_t)T.nt * 4);
         if (gate == ORB_PROJ_GATE_FUSE) std::memcpy(st.hi<uint8_t>(R.o_inv), T.inv_sigma2, (size_t)T.nlevels * 4);
-        std::memcpy(st.hi<uint8_t>(R.o_coff), T.grid.cell_off, (size_t)(ncells + 1) * 4);
-        if (T.grid.cell_off[ncells])
-            std::memcpy(st.hi<uint8_t>(R.o_cidx), T.grid.cell_idx, (size_t)T.grid.cell_off[ncells] * 4);
+        if (F) {
+            D.t = F->d_desc;
+            D.kps = F->d_kps;
+            D.ur = gate == ORB_PROJ_GATE_FUSE ? F->d_ur : nullptr;
+            D.cell_off = F->d_coff;
+            D.cell_idx = F->d_cidx;
+        } else {
+            D.t = st.di<uint8_t>((size_t)R.o_t);
+            D.kps = st.di<orb_keypoint>((size_t)R.o_kps);
+            D.ur = R.o_ur >= 0 ? st.di<float>((size_t)R.o_ur) : nullptr;
+            D.cell_off = st.di<int>((size_t)R.o_coff);
+            D.cell_idx = st.di<int>((size_t)R.o_cidx);
+            std::memcpy(st.hi<uint8_t>(R.o_t), T.tdesc, (size_t)T.nt * 32);
+            std::memcpy(st.hi<uint8_t>(R.o_kps), T.kps_t, (size_t)T.nt * sizeof(orb_keypoint));
+            if (R.o_ur >= 0) std::memcpy(st.hi<uint8_t>(R.o_ur), T.t_uright, (size_t)T.nt * 4);
+            std::memcpy(st.hi<uint8_t>(R.o_coff), T.grid.cell_off, (size_t)(ncells + 1) * 4);
+            if (T.grid.cell_off[ncells])
+                std::memcpy(st.hi<uint8_t>(R.o_cidx), T.grid.cell_idx, (size_t)T.grid.cell_off[ncells] * 4);
+        }
         item += (size_t)T.nq;
         row++;
     }
     hipError_t e;
     if ((e = st.up(0, o_in_end)) != hipSuccess) return set_error("upload", e), ORB_ERR_HIP;
     if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
-    e = launch_projection_best(gate, st.di<uint8_t>(0), st.di<ProjTarget>(o_tab), st.di<int>(o_item),
-                               st.di<orb_proj_query>(o_pq), st.di<uint8_t>(o_q), (int)nitems, st.h<int>(o_idx),
-                               st.h<int>(o_dist), c->stream);
+    e = launch_projection_best(gate, st.di<ProjTarget>(o_tab), st.di<int>(o_item), st.di<orb_proj_query>(o_pq),
+                               st.di<uint8_t>(o_q), (int)nitems, st.h<int>(o_idx), st.h<int>(o_dist), c->stream);
     if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 0, c->stream);
     if (e != hipSuccess) return set_error("projection kernel", e), ORB_ERR_HIP;
     // the kernel writes (idx, dist) straight into the pinned mirror (host-coherent memory): no D2H command
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("download", e), ORB_ERR_HIP;
     item = 0;
     for (int k = 0; k < ntargets; k++) {
-        const orb_proj_target& T = targets[k];
+        const orb_proj_target& T = targets[k].T;
         if (T.nq == 0 || T.nt == 0) continue;
         std::memcpy(T.best_idx, st.h<int>(o_idx) + item, (size_t)T.nq * 4);
         std::memcpy(T.best_dist, st.h<int>(o_dist) + item, (size_t)T.nq * 4);
         item += (size_t)T.nq;
     }
     return ORB_OK;
+}
+}  // namespace
+}  // namespace orbgpu
+
+extern "C" {
+
+/* Fuse (both overloads) and SearchBySim3's two directions: per (target, query) the first minimum of the descriptor
+ * distance over the gated candidates, every target's items in one k_projection_best launch (orbgpu.h). */
+int orb_project_best_batch(orb_ctx* h, int gate, int ntargets, const orb_proj_target* targets) {
+    const char* const fn = "orb_project_best_batch";
+    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE) return arg_error(fn, "unknown gate");
+    if (ntargets < 0 || (ntargets > 0 && !targets)) return arg_error(fn, "ntargets < 0 or targets NULL");
+    std::vector<ProjView> v;
+    v.reserve(ntargets);
+    for (int k = 0; k < ntargets; k++) v.push_back(proj_view(targets[k]));
+    return project_best_run(fn, h, gate, v);
+}
+
+/* The same with every target's trains as a resident frame. */
+int orb_project_best_frames(orb_ctx* h, int gate, int ntargets, const orb_proj_frame_target* targets) {
+    const char* const fn = "orb_project_best_frames";
+    if (gate != ORB_PROJ_GATE_NONE && gate != ORB_PROJ_GATE_FUSE) return arg_error(fn, "unknown gate");
+    if (ntargets < 0 || (ntargets > 0 && !targets)) return arg_error(fn, "ntargets < 0 or targets NULL");
+    std::vector<ProjView> v;
+    v.reserve(ntargets);
+    for (int k = 0; k < ntargets; k++) {
+        if (!targets[k].frame) return arg_error(fn, "target " + std::to_string(k) + ": NULL frame");
+        v.push_back(proj_view(targets[k]));
+    }
+    return project_best_run(fn, h, gate, v);
+}
+
+/* The grid searches with the train side as a resident frame (orbgpu.h): the counterpart's checks, then the same
+ * session with the handle's device pointers and the same replay over the handle's host keypoints. */
+#define FRAME_GUARD(fn, c, F)                                                                        \
+    if (!(c)) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;                             \
+    if ((F)->device != (c)->device) return arg_error(fn, "the frame lives on another device");       \
+    CTX_GUARD(c)
+
+int orb_search_by_projection_frame(orb_ctx* h, int mode, float nnratio, int check_ori, int max_dist, int nq,
+                                   const orb_proj_query* q, const uint8_t* qdesc, const orb_frame* F,
+                                   const uint8_t* t_taken, int use_uright, int* match_t, int* nmatches_out) {
+    const char* const fn = "orb_search_by_projection_frame";
+    if (mode != ORB_PROJ_BEST && mode != ORB_PROJ_RATIO_SAME_LEVEL) return arg_error(fn, "unknown mode");
+    if (max_dist < 0 || max_dist > 256) return arg_error(fn, "max_dist outside [0, 256]");
+    if (!F) return arg_error(fn, "NULL frame");
+    const int nt = F->n;
+    if (nq < 0 || (nt && !match_t) || (nq && (!q || !qdesc))) return arg_error(fn, "bad arguments");
+    if (use_uright && !F->has_ur) return arg_error(fn, "use_uright with a frame created without uright");
+    for (int i = 0; i < nq; i++)
+        if (!std::isfinite(q[i].u) || !std::isfinite(q[i].v) || !std::isfinite(q[i].r) || q[i].r < 0)
+            return arg_error(fn, "query window not finite or radius negative");
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    FRAME_GUARD(fn, c, F);
+    for (int t = 0; t < nt; t++) match_t[t] = -1;
+    if (nmatches_out) *nmatches_out = 0;
+    if (nq == 0 || nt == 0) return ORB_OK;
+    const char* e = getenv("ORBGPU_PROJ_LANES");   // (as orb_search_by_projection)
+    const int lanes = (e && atoi(e) == 16) ? 16 : 64;
+    TopkSession s{c};
+    const int st = s.setup_proj(nq, q, qdesc, F, use_uright != 0, lanes);
+    if (st != ORB_OK) return st;
+    return proj_replay(s, mode, nnratio, check_ori, max_dist, q, F->kps.data(), t_taken, match_t, nmatches_out);
+}
+
+int orb_window_match_frame(orb_ctx* h, float nnratio, int check_ori, int level0_only, int n1, const uint8_t* desc1,
+                           const orb_keypoint* kps1, const float* centres, float window, const orb_frame* F2,
+                           int* match12, int* nmatches_out) {
+    const char* const fn = "orb_window_match_frame";
+    if (!F2) return arg_error(fn, "NULL frame");
+    if (n1 < 0 || !match12 || (n1 && (!desc1 || !kps1))) return arg_error(fn, "bad arguments");
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    FRAME_GUARD(fn, c, F2);
+    if (n1 == 0 || F2->n == 0) {
+        for (int i = 0; i < n1; i++) match12[i] = -1;
+        if (nmatches_out) *nmatches_out = 0;
+        return ORB_OK;
+    }
+    TopkSession s{c};
+    for (int i1 = 0; i1 < n1; i1++) {
+        if (level0_only && kps1[i1].octave > 0) continue;   // :420-423
+        s.item_q.push_back(i1);
+    }
+    const orb_frame_grid g{F2->min_x, F2->min_y, F2->inv_w, F2->inv_h, nullptr, nullptr};
+    const int st = s.setup_grid(desc1, n1, kps1, centres, nullptr, F2->n, nullptr, g, window, F2);
+    if (st != ORB_OK) return st;
+    return window_replay(s, nnratio, check_ori, n1, kps1, F2->n, F2->kps.data(), match12, nmatches_out);
+}
+
+int orb_search_by_match_bird_resident(orb_ctx* h, float nnratio, int check_ori, int max_dist, float r, int nq,
+                                      const int* q_id, const float* q_xy, const float* q_angle, const uint8_t* qdesc,
+                                      const orb_frame* F, int* match_t, int* nmatches_out) {
+    const char* const fn = "orb_search_by_match_bird_resident";
+    if (max_dist < 0 || max_dist > 256) return arg_error(fn, "max_dist outside [0, 256]");
+    if (!std::isfinite(r) || r < 0) return arg_error(fn, "radius not finite or negative");
+    if (!F) return arg_error(fn, "NULL frame");
+    const int nt = F->n;
+    if (nq < 0 || (nt && !match_t) || (nq && (!q_xy || !qdesc || (check_ori && !q_angle))))
+        return arg_error(fn, "bad arguments");
+    for (int i = 0; i < nq; i++) {
+        if (!std::isfinite(q_xy[2 * i]) || !std::isfinite(q_xy[2 * i + 1]))
+            return arg_error(fn, "query centre not finite");
+        if (q_id && q_id[i] < 0) return arg_error(fn, "negative query id");
+    }
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    FRAME_GUARD(fn, c, F);
+    for (int t = 0; t < nt; t++) match_t[t] = -1;
+    if (nmatches_out) *nmatches_out = 0;
+    if (nq == 0 || nt == 0) return ORB_OK;
+    std::vector<orb_proj_query> q(nq);
+    for (int i = 0; i < nq; i++)   // GetFeaturesInAreaBirdview(pt.x, pt.y, r): the default levels (:2023)
+        q[i] = orb_proj_query{q_xy[2 * i], q_xy[2 * i + 1], r, -1, -1, 0.0f, 0.0f, 0.0f, 0};
+    TopkSession s{c};
+    const int st = s.setup_proj(nq, q.data(), qdesc, F, false, 64);
+    if (st != ORB_OK) return st;
+    return match_bird_replay(s, nnratio, check_ori, max_dist, q_id, q_angle, F->kps.data(), match_t, nmatches_out);
 }
 
 int orb_project_best_host(int gate, const orb_proj_target* target, int query, int* best_idx, int* best_dist) {
@@ -1363,7 +1569,7 @@ int orb_project_best_host(int gate, const orb_proj_target* target, int query, in
     orb_proj_target T = *target;   // (the target's own outputs are not this call's: not required, not touched)
     T.best_idx = best_idx;
     T.best_dist = best_dist;
-    if (const char* why = proj_target_fault(gate, T, query, query + 1)) return arg_error(fn, why);
+    if (const char* why = proj_target_fault(gate, proj_view(T), query, query + 1)) return arg_error(fn, why);
     proj_best_one(gate, T, T.q[query], T.qdesc + (size_t)query * 32, best_idx, best_dist);
     return ORB_OK;
 }

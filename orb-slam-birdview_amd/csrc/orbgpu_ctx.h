@@ -260,3 +260,21 @@ struct Stage {
 };
 
 }  // namespace orbgpu
+
+// A device-resident Frame / KeyFrame (the object behind the opaque orb_frame*, frame.hip): the train side of the grid
+// searches, uploaded once.  One device allocation holds [desc | kps | uright | cell_off | cell_idx], each region
+// 256-byte aligned; cell_off / cell_idx are the Frame grid k_frame_grid built from the keypoints.  The host keeps the
+// keypoints: the searches' replays read their octave and angle.
+struct orb_frame {
+    int device = 0;
+    int n = 0;
+    bool has_ur = false;
+    float min_x = 0, min_y = 0, inv_w = 0, inv_h = 0;
+    uint8_t* d_base = nullptr;
+    const uint8_t* d_desc = nullptr;
+    const orb_keypoint* d_kps = nullptr;
+    const float* d_ur = nullptr;   // NULL: created without uright
+    const int* d_coff = nullptr;   // kFrameGridCells + 1
+    const int* d_cidx = nullptr;   // n slots (cell_off[kFrameGridCells] of them used)
+    std::vector<orb_keypoint> kps;
+};

@@ -344,15 +344,25 @@ hipError_t launch_projection_topk(const orb_proj_query* d_pq, const uint8_t* d_q
 
 // The per-query searches over many targets (orb_project_best_batch: Fuse, SearchBySim3): the items (target, query)
 // of every target flattened into one launch.  Item i has its orb_proj_query d_pq[i], its descriptor d_q + 32 i and its
-// target's row d_item_tgt[i] of this table; a row's offsets are bytes from d_base (the call's staging area, each
-// region 256-byte aligned).  o_ur < 0: every train is monocular; o_inv is read with gate FUSE only.
+// target's row d_item_tgt[i] of this table; a row holds device pointers, into the call's staging area (a target given
+// as host arrays) or into a resident frame's allocation (orb_project_best_frames).  ur == NULL: every train is
+// monocular; inv_sigma2 is read with gate FUSE only.
 struct ProjTarget {
-    long long o_t, o_kps, o_ur, o_inv, o_coff, o_cidx;
+    const uint8_t* t;
+    const orb_keypoint* kps;
+    const float* ur;
+    const float* inv_sigma2;
+    const int* cell_off;
+    const int* cell_idx;
     ProjGrid g;
 };
-hipError_t launch_projection_best(int gate, const uint8_t* d_base, const ProjTarget* d_tab, const int* d_item_tgt,
-                                  const orb_proj_query* d_pq, const uint8_t* d_q, int nitems, int* d_idx, int* d_dist,
-                                  hipStream_t stream);
+hipError_t launch_projection_best(int gate, const ProjTarget* d_tab, const int* d_item_tgt, const orb_proj_query* d_pq,
+                                  const uint8_t* d_q, int nitems, int* d_idx, int* d_dist, hipStream_t stream);
+
+// The Frame grid of n keypoints on the device (k_frame_grid, frame.hip): d_cell_off (kFrameGridCells + 1) and
+// d_cell_idx (n slots), every cell's indices ascending.  d_work: 2 n ints of working space.
+hipError_t launch_frame_grid(const orb_keypoint* d_kps, int n, const ProjGrid& g, int* d_cell_off, int* d_cell_idx,
+                             int* d_work, hipStream_t stream);
 
 // SearchForTriangulation's staged inputs, read by k_triangulation straight from the pinned mirror (over PCIe):
 // one record per query (item) holding everything its wave needs, and the candidate trains' records in

@@ -79,6 +79,9 @@ std::vector<float> angles(const FeatureSet& s) {
     return a;
 }
 
+// mvuRight gates the search: the FeatureSet's array, or the resident frame's
+bool has_uright(const FeatureSet& s) { return s.resident ? s.resident->hasURight() : s.uRight != nullptr; }
+
 const uint8_t* desc_ptr(const FeatureSet& s) {
     static const uint8_t dummy[32] = {0};
     return (s.descriptors && s.N()) ? s.descriptors : dummy;
@@ -178,6 +181,74 @@ orb_frame_grid FrameGrid::Csr(std::vector<int>& off, std::vector<int>& idx) cons
     g.cell_idx = idx.data();
     return g;
 }
+
+/* ---------------- ResidentFrame (orb_frame) ---------------- */
+ResidentFrame::ResidentFrame(const KeyPoint* keysUn, int n, const uint8_t* descriptors, const float* uRight, float minX,
+                             float maxX, float minY, float maxY) {
+    const float invW = static_cast<float>(ORBGPU_FRAME_GRID_COLS) / static_cast<float>(maxX - minX);   // as FrameGrid
+    const float invH = static_cast<float>(ORBGPU_FRAME_GRID_ROWS) / static_cast<float>(maxY - minY);
+    check(orb_frame_create(matcher_ctx(), n, descriptors, keysUn, uRight, minX, minY, invW, invH, &h_), "ResidentFrame");
+    n_ = n;
+    hasURight_ = uRight != nullptr;
+}
+
+ResidentFrame ResidentFrame::Birdview(const KeyPoint* keysBird, int n, const uint8_t* descriptors, float widthInv,
+                                      float heightInv) {
+    ResidentFrame f;
+    check(orb_frame_create(matcher_ctx(), n, descriptors, keysBird, nullptr, 0.f, 0.f, widthInv, heightInv, &f.h_),
+          "ResidentFrame::Birdview");
+    f.n_ = n;
+    return f;
+}
+
+ResidentFrame ResidentFrame::FromDevice(orb_ctx* ctx, int n, const uint8_t* d_descriptors, const KeyPoint* d_keysUn,
+                                        const float* d_uRight, float minX, float minY, float widthInv, float heightInv) {
+    ResidentFrame f;
+    check(orb_frame_create_device(ctx, n, d_descriptors, d_keysUn, d_uRight, minX, minY, widthInv, heightInv, &f.h_),
+          "ResidentFrame::FromDevice");
+    f.n_ = n;
+    f.hasURight_ = d_uRight != nullptr;
+    return f;
+}
+
+ResidentFrame::~ResidentFrame() { orb_frame_destroy(h_); }
+
+ResidentFrame::ResidentFrame(ResidentFrame&& o) noexcept : h_(o.h_), n_(o.n_), hasURight_(o.hasURight_) {
+    o.h_ = nullptr;
+    o.n_ = 0;
+    o.hasURight_ = false;
+}
+
+ResidentFrame& ResidentFrame::operator=(ResidentFrame&& o) noexcept {
+    if (this != &o) {
+        orb_frame_destroy(h_);
+        h_ = o.h_;
+        n_ = o.n_;
+        hasURight_ = o.hasURight_;
+        o.h_ = nullptr;
+        o.n_ = 0;
+        o.hasURight_ = false;
+    }
+    return *this;
+}
+
+void ResidentFrame::Grid(std::vector<int>& off, std::vector<int>& idx) const {
+    require(h_ != nullptr, "ResidentFrame::Grid: empty handle");
+    off.assign((size_t)ORBGPU_FRAME_GRID_COLS * ORBGPU_FRAME_GRID_ROWS + 1, 0);
+    idx.assign(std::max(n_, 1), 0);
+    int nslots = 0;
+    check(orb_frame_grid_read(h_, off.data(), idx.data(), n_, &nslots), "ResidentFrame::Grid");
+    idx.resize(nslots);
+}
+
+namespace {
+// the train side's handle, checked against the FeatureSet it stands for (NULL: the FrameGrid form)
+const orb_frame* resident_of(const FeatureSet& F, const char* what) {
+    if (!F.resident) return nullptr;
+    require(F.resident->handle() != nullptr && F.resident->N() == F.N(), what);
+    return F.resident->handle();
+}
+}  // namespace
 
 /* ---------------- ORBmatcher ---------------- */
 ORBmatcher::ORBmatcher(float nnratio, bool checkOri) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
@@ -295,8 +366,28 @@ int ORBmatcher::window_match(bool level0_only, const FeatureSet& F1, const Featu
                              const std::vector<Point2f>* centres, int windowSize, std::vector<int>& vnMatches12) {
     const int n1 = F1.N(), n2 = F2.N();
     vnMatches12.assign(n1, -1);
-    require(F2.grid != nullptr, "window match: F2 grid");
     require(n1 == 0 || (F1.keys && F1.descriptors), "window match: F1 keys/descriptors");
+    if (const orb_frame* R = resident_of(F2, "window match: F2 resident frame")) {
+        // GetFeaturesInArea on the device over the handle's grid: the same candidates in the same order
+        std::vector<float> cen;
+        if (centres) {
+            require((int)centres->size() >= n1, "window match: one centre per F1 feature");
+            cen.resize(2 * (size_t)std::max(n1, 1));
+            for (int i = 0; i < n1; i++) {
+                cen[2 * i] = (*centres)[i].x;
+                cen[2 * i + 1] = (*centres)[i].y;
+            }
+        }
+        std::vector<int> out(std::max(n1, 1), -1);
+        int nmatches = 0;
+        check(orb_window_match_frame(matcher_ctx(), mfNNratio, mbCheckOrientation, level0_only, n1, desc_ptr(F1),
+                                     keys_ptr(F1), centres ? cen.data() : nullptr, (float)windowSize, R, out.data(),
+                                     &nmatches),
+              "window match (resident)");
+        std::copy(out.begin(), out.begin() + n1, vnMatches12.begin());
+        return nmatches;
+    }
+    require(F2.grid != nullptr, "window match: F2 grid");
     require(n2 == 0 || (F2.keys && F2.descriptors), "window match: F2 keys/descriptors");
     // candidate lists: F2.GetFeaturesInArea(centre, windowSize, level1, level1) per query (:425, :1686, :1806)
     std::vector<int> off(n1 + 1, 0), idx;
@@ -354,6 +445,19 @@ int ORBmatcher::projection_search(int mode, const FeatureSet& F, bool stereo, co
                                   int max_dist, int check_ori, const uint8_t* taken) {
     const int n = F.N(), nq = (int)q.size();
     matches.assign(n, -1);
+    if (const orb_frame* R = resident_of(F, "projection search: resident frame")) {
+        require(!stereo || F.resident->hasURight(), "projection search: resident frame without uRight");
+        std::vector<int> out(std::max(n, 1), -1);
+        int nmatches = 0;
+        check(orb_search_by_projection_frame(matcher_ctx(), mode, mfNNratio,
+                                             check_ori < 0 ? (int)mbCheckOrientation : check_ori,
+                                             max_dist < 0 ? TH_HIGH : max_dist, nq, nq ? q.data() : nullptr,
+                                             nq ? qdesc.data() : nullptr, R, taken ? taken : F.hasMapPoint, stereo ? 1 : 0,
+                                             out.data(), &nmatches),
+              what);
+        std::copy(out.begin(), out.begin() + n, matches.begin());
+        return nmatches;
+    }
     require(F.grid != nullptr, "projection search: Frame grid");
     require(n == 0 || (F.keys && F.descriptors), "projection search: Frame keys/descriptors");
     std::vector<int> off, idx;
@@ -400,7 +504,7 @@ int ORBmatcher::SearchByProjection(FrameData& CurrentFrame, const ProjectedLastF
         q[i].blocks = p.observed ? 1 : 0;
         memcpy(&qdesc[i * 32], p.descriptor, 32);
     }
-    return projection_search(ORB_PROJ_BEST, CurrentFrame, CurrentFrame.uRight != nullptr, q, qdesc, vpMapPointMatches,
+    return projection_search(ORB_PROJ_BEST, CurrentFrame, has_uright(CurrentFrame), q, qdesc, vpMapPointMatches,
                              "SearchByProjection(CurrentFrame, LastFrame)");
 }
 
@@ -428,7 +532,7 @@ int ORBmatcher::SearchByProjection(FrameData& F, const ProjectedMapPoints& vpMap
         q[i].blocks = 1;
         memcpy(&qdesc[i * 32], p.descriptor, 32);
     }
-    return projection_search(ORB_PROJ_RATIO_SAME_LEVEL, F, F.uRight != nullptr, q, qdesc, vpMapPointMatches,
+    return projection_search(ORB_PROJ_RATIO_SAME_LEVEL, F, has_uright(F), q, qdesc, vpMapPointMatches,
                              "SearchByProjection(F, MapPoints)");
 }
 
@@ -460,8 +564,9 @@ int ORBmatcher::SearchByMatchBird(const KeyFrameBirdPoints& KF, FrameData& F, st
                                   const float r) {
     const int n = F.N(), nq = (int)KF.points.size();
     vpMapPointMatchesBird.assign(n, -1);   // :2004 vector<MapPointBird*>(F.mvKeysBird.size(), NULL)
-    require(F.grid != nullptr, "SearchByMatchBird: Frame grid");
-    require(n == 0 || (F.keys && F.descriptors), "SearchByMatchBird: Frame keys/descriptors");
+    const orb_frame* R = resident_of(F, "SearchByMatchBird: resident frame");
+    require(R || F.grid != nullptr, "SearchByMatchBird: Frame grid");
+    require(R || n == 0 || (F.keys && F.descriptors), "SearchByMatchBird: Frame keys/descriptors");
     std::vector<int> id(nq);
     std::vector<float> xy(2 * (size_t)nq), angle(nq);
     std::vector<uint8_t> qdesc((size_t)nq * 32);
@@ -474,10 +579,19 @@ int ORBmatcher::SearchByMatchBird(const KeyFrameBirdPoints& KF, FrameData& F, st
         angle[i] = p.angle;
         memcpy(&qdesc[(size_t)i * 32], p.descriptor, 32);
     }
-    std::vector<int> off, idx;
-    const orb_frame_grid g = F.grid->Csr(off, idx);
     std::vector<int> out(std::max(n, 1), -1);
     int nmatches = 0;
+    if (R) {
+        check(orb_search_by_match_bird_resident(matcher_ctx(), mfNNratio, mbCheckOrientation, TH_HIGH, r, nq,
+                                                nq ? id.data() : nullptr, nq ? xy.data() : nullptr,
+                                                nq ? angle.data() : nullptr, nq ? qdesc.data() : nullptr, R, out.data(),
+                                                &nmatches),
+              "SearchByMatchBird(KF, F) (resident)");
+        std::copy(out.begin(), out.begin() + n, vpMapPointMatchesBird.begin());
+        return nmatches;
+    }
+    std::vector<int> off, idx;
+    const orb_frame_grid g = F.grid->Csr(off, idx);
     check(orb_search_by_match_bird(matcher_ctx(), mfNNratio, mbCheckOrientation, TH_HIGH, r, nq, nq ? id.data() : nullptr,
                                    nq ? xy.data() : nullptr, nq ? angle.data() : nullptr, nq ? qdesc.data() : nullptr, n,
                                    desc_ptr(F), keys_ptr(F), g, out.data(), &nmatches),
@@ -526,23 +640,15 @@ orb_proj_query kf_query(const ProjectedKFPoint& p, float radius, int level_above
     q.blocks = 1;
     return q;
 }
+// the queries and outputs of a target (both forms of the train side)
+void fill_queries(const KeyFrameData& kf, const std::vector<ProjectedKFPoint>& points, bool chi2Gate, TargetArrays& a);
 orb_proj_target make_target(const KeyFrameData& kf, const std::vector<ProjectedKFPoint>& points, bool chi2Gate,
                             TargetArrays& a) {
-    const size_t nq = points.size();
     require(kf.grid != nullptr, "keyframe search: KeyFrame grid");
     require(kf.n == 0 || (kf.keys && kf.descriptors), "keyframe search: KeyFrame keys/descriptors");
-    require(!chi2Gate || (kf.invLevelSigma2 && kf.nlevels > 0), "Fuse: mvInvLevelSigma2");
-    a.q.resize(nq);
-    a.qdesc.resize(nq * 32);
-    for (size_t i = 0; i < nq; i++) {
-        require(points[i].descriptor != nullptr, "keyframe search: map point descriptor");
-        a.q[i] = kf_query(points[i], points[i].radius, 0, 0);
-        memcpy(&a.qdesc[i * 32], points[i].descriptor, 32);
-    }
-    a.best_idx.assign(std::max<size_t>(nq, 1), -1);
-    a.best_dist.assign(std::max<size_t>(nq, 1), -1);
+    fill_queries(kf, points, chi2Gate, a);
     orb_proj_target t;
-    t.nq = (int)nq;
+    t.nq = (int)points.size();
     t.q = a.q.data();
     t.qdesc = a.qdesc.data();
     t.nt = kf.n;
@@ -556,17 +662,66 @@ orb_proj_target make_target(const KeyFrameData& kf, const std::vector<ProjectedK
     t.best_dist = a.best_dist.data();
     return t;
 }
+// the same target with the keyframe as a ResidentFrame (kf.resident)
+orb_proj_frame_target make_frame_target(const KeyFrameData& kf, const std::vector<ProjectedKFPoint>& points,
+                                        bool chi2Gate, TargetArrays& a) {
+    fill_queries(kf, points, chi2Gate, a);
+    orb_proj_frame_target t;
+    t.nq = (int)points.size();
+    t.q = a.q.data();
+    t.qdesc = a.qdesc.data();
+    t.frame = resident_of(kf, "keyframe search: resident frame");
+    t.inv_sigma2 = chi2Gate ? kf.invLevelSigma2 : nullptr;
+    t.nlevels = chi2Gate ? kf.nlevels : 0;
+    t.best_idx = a.best_idx.data();
+    t.best_dist = a.best_dist.data();
+    return t;
+}
+void fill_queries(const KeyFrameData& kf, const std::vector<ProjectedKFPoint>& points, bool chi2Gate, TargetArrays& a) {
+    const size_t nq = points.size();
+    require(!chi2Gate || (kf.invLevelSigma2 && kf.nlevels > 0), "Fuse: mvInvLevelSigma2");
+    a.q.resize(nq);
+    a.qdesc.resize(nq * 32);
+    for (size_t i = 0; i < nq; i++) {
+        require(points[i].descriptor != nullptr, "keyframe search: map point descriptor");
+        a.q[i] = kf_query(points[i], points[i].radius, 0, 0);
+        memcpy(&a.qdesc[i * 32], points[i].descriptor, 32);
+    }
+    a.best_idx.assign(std::max<size_t>(nq, 1), -1);
+    a.best_dist.assign(std::max<size_t>(nq, 1), -1);
+}
+// One call over targets that are all resident or all given as arrays (the C-ABI has one entry point per form).
+void project_best(const std::vector<const KeyFrameData*>& kf, const std::vector<const std::vector<ProjectedKFPoint>*>& pts,
+                  bool chi2Gate, std::vector<TargetArrays>& arrays, const char* what) {
+    const size_t nt = kf.size();
+    arrays.assign(nt, TargetArrays());
+    size_t nres = 0;
+    for (size_t t = 0; t < nt; t++) nres += kf[t]->resident != nullptr;
+    require(nres == 0 || nres == nt, "keyframe search: every target resident, or none");
+    const int gate = chi2Gate ? ORB_PROJ_GATE_FUSE : ORB_PROJ_GATE_NONE;
+    if (nres) {
+        std::vector<orb_proj_frame_target> T(nt);
+        for (size_t t = 0; t < nt; t++) T[t] = make_frame_target(*kf[t], *pts[t], chi2Gate, arrays[t]);
+        check(orb_project_best_frames(matcher_ctx(), gate, (int)nt, T.data()), what);
+    } else {
+        std::vector<orb_proj_target> T(nt);
+        for (size_t t = 0; t < nt; t++) T[t] = make_target(*kf[t], *pts[t], chi2Gate, arrays[t]);
+        check(orb_project_best_batch(matcher_ctx(), gate, (int)nt, nt ? T.data() : nullptr), what);
+    }
+}
 }  // namespace
 
 void ORBmatcher::FuseSearch(const std::vector<FuseTarget>& targets, bool chi2Gate,
                             std::vector<std::vector<FuseBest> >& best) {
     const size_t nt = targets.size();
-    std::vector<TargetArrays> arrays(nt);
-    std::vector<orb_proj_target> T(nt);
-    for (size_t t = 0; t < nt; t++) T[t] = make_target(targets[t].kf, targets[t].points, chi2Gate, arrays[t]);
-    check(orb_project_best_batch(matcher_ctx(), chi2Gate ? ORB_PROJ_GATE_FUSE : ORB_PROJ_GATE_NONE, (int)nt,
-                                 nt ? T.data() : nullptr),
-          "FuseSearch");
+    std::vector<TargetArrays> arrays;
+    std::vector<const KeyFrameData*> kf(nt);
+    std::vector<const std::vector<ProjectedKFPoint>*> pts(nt);
+    for (size_t t = 0; t < nt; t++) {
+        kf[t] = &targets[t].kf;
+        pts[t] = &targets[t].points;
+    }
+    project_best(kf, pts, chi2Gate, arrays, "FuseSearch");
     best.assign(nt, std::vector<FuseBest>());
     for (size_t t = 0; t < nt; t++) {
         best[t].resize(targets[t].points.size());
@@ -590,10 +745,8 @@ int ORBmatcher::SearchBySim3(const KeyFrameData& KF1, const KeyFrameData& KF2, c
                              const ProjectedSim3Points& points2in1, std::vector<int>& vnMatch12) {
     require(points1in2.index.size() == points1in2.points.size() && points2in1.index.size() == points2in1.points.size(),
             "SearchBySim3: one index per point");
-    TargetArrays a[2];
-    orb_proj_target T[2] = {make_target(KF2, points1in2.points, false, a[0]),
-                            make_target(KF1, points2in1.points, false, a[1])};
-    check(orb_project_best_batch(matcher_ctx(), ORB_PROJ_GATE_NONE, 2, T), "SearchBySim3");
+    std::vector<TargetArrays> a;
+    project_best({&KF2, &KF1}, {&points1in2.points, &points2in1.points}, false, a, "SearchBySim3");
     const int N1 = KF1.N(), N2 = KF2.N();
     std::vector<int> vnMatch1(N1, -1), vnMatch2(N2, -1);                     // :1144-1145
     for (size_t k = 0; k < points1in2.points.size(); k++) {
@@ -660,6 +813,47 @@ int ORBmatcher::SearchByProjection(FrameData& CurrentFrame, const ProjectedKeyFr
     // the rotation cull of :1577-1596 is statement for statement that of :1448-1467, which BEST mode replays
     return projection_search(ORB_PROJ_BEST, CurrentFrame, false, q, qdesc, vpMapPointMatches, "SearchByProjection(F, KF)",
                              ORBdist);
+}
+
+/* ---------------- the ResidentFrame overloads: the FeatureSet forms with `resident` set ---------------- */
+namespace {
+FrameData with_resident(const FrameData& members, const ResidentFrame& R) {
+    FrameData F = members;
+    F.n = R.N();
+    F.resident = &R;
+    return F;
+}
+}  // namespace
+
+int ORBmatcher::SearchByProjection(const ResidentFrame& CurrentFrame, FrameData& members,
+                                   const ProjectedLastFrame& LastFrame, const float th, const bool bMono,
+                                   std::vector<int>& vpMapPointMatches) {
+    FrameData F = with_resident(members, CurrentFrame);
+    return SearchByProjection(F, LastFrame, th, bMono, vpMapPointMatches);
+}
+
+int ORBmatcher::SearchByProjection(const ResidentFrame& Fr, FrameData& members, const ProjectedMapPoints& vpMapPoints,
+                                   const float th, std::vector<int>& vpMapPointMatches) {
+    FrameData F = with_resident(members, Fr);
+    return SearchByProjection(F, vpMapPoints, th, vpMapPointMatches);
+}
+
+int ORBmatcher::SearchByProjectionBird(const ResidentFrame& Fr, FrameData& members,
+                                       const ProjectedBirdPoints& vpMapPointsBird, const float r,
+                                       std::vector<int>& vpMapPointMatchesBird) {
+    FrameData F = with_resident(members, Fr);
+    return SearchByProjectionBird(F, vpMapPointsBird, r, vpMapPointMatchesBird);
+}
+
+int ORBmatcher::SearchByMatchBird(const KeyFrameBirdPoints& KF, const ResidentFrame& Fr,
+                                  std::vector<int>& vpMapPointMatchesBird, const float r) {
+    FrameData F = with_resident(FrameData(), Fr);
+    return SearchByMatchBird(KF, F, vpMapPointMatchesBird, r);
+}
+
+int ORBmatcher::BirdviewMatch(const FrameData& F1, const ResidentFrame& F2, std::vector<int>& vnMatches12,
+                              int windowSize) {
+    return window_match(false, F1, with_resident(FrameData(), F2), nullptr, windowSize, vnMatches12);
 }
 
 std::vector<int> ComputeDistinctiveDescriptors(const std::vector<std::vector<const uint8_t*> >& observations) {

@@ -62,6 +62,44 @@ private:
     std::vector<std::vector<size_t> > cells_;   // [ix * ROWS + iy]
 };
 
+// A Frame's or KeyFrame's train side kept on the device (the C-ABI's orb_frame): descriptors, undistorted keypoints
+// and optionally mvuRight are uploaded once and the library builds the grid on the GPU, so a frame that is searched
+// several times is not staged again.  Constructed like a FrameGrid, plus the arrays the searches read; the arrays
+// may be freed once the constructor returns.  Move-only; the destructor frees the device memory.  Failures throw
+// OrbGpuError.  It lives on the GPU of the calling thread's matcher context (ORBGPU_DEVICE, default 0) and serves any
+// thread's searches on that GPU; create it in the Frame / KeyFrame constructor and let it die with its owner
+// (INTEGRATION.md).
+class ResidentFrame {
+public:
+    ResidentFrame() = default;
+    // Frame grid: cells of (maxX-minX)/64 x (maxY-minY)/48 over mvKeysUn; uRight may be NULL (monocular)
+    ResidentFrame(const KeyPoint* keysUn, int n, const uint8_t* descriptors, const float* uRight, float minX, float maxX,
+                  float minY, float maxY);
+    // birdview grid: GridElementWidthInv/HeightInv given directly, origin (0, 0), no uRight
+    static ResidentFrame Birdview(const KeyPoint* keysBird, int n, const uint8_t* descriptors, float widthInv,
+                                  float heightInv);
+    // from arrays already in the memory of ctx's GPU (e.g. a slot of orb_extract_batch_device's outputs)
+    static ResidentFrame FromDevice(orb_ctx* ctx, int n, const uint8_t* d_descriptors, const KeyPoint* d_keysUn,
+                                    const float* d_uRight, float minX, float minY, float widthInv, float heightInv);
+    ~ResidentFrame();
+    ResidentFrame(ResidentFrame&& o) noexcept;
+    ResidentFrame& operator=(ResidentFrame&& o) noexcept;
+    ResidentFrame(const ResidentFrame&) = delete;
+    ResidentFrame& operator=(const ResidentFrame&) = delete;
+
+    int N() const { return n_; }
+    bool hasURight() const { return hasURight_; }
+    explicit operator bool() const { return h_ != nullptr; }
+    const orb_frame* handle() const { return h_; }
+    // the grid the GPU built, as FrameGrid::Csr gives the host one (cell_off: 64 * 48 + 1 entries)
+    void Grid(std::vector<int>& off, std::vector<int>& idx) const;
+
+private:
+    orb_frame* h_ = nullptr;
+    int n_ = 0;
+    bool hasURight_ = false;
+};
+
 // The members of a Frame / KeyFrame that ORBmatcher reads, as zero-copy views (cv::KeyPoint and
 // orb_keypoint share one 28-byte layout; a continuous n x 32 CV_8U Mat is n*32 bytes).  Pointers
 // may be NULL where a method does not read the member (see each method).
@@ -77,6 +115,11 @@ struct FeatureSet {
     int nlevels = 0;                                  // mnScaleLevels (length of the two tables above)
     const FrameGrid* grid = nullptr;                  // mGrid / mGridBirdview
     const float* invLevelSigma2 = nullptr;            // mvInvLevelSigma2 (Fuse's reprojection gate)
+    // The frame as a ResidentFrame: where a search reads grid, descriptors and uRight of its TRAIN side (the
+    // projection searches' Frame, the window matches' F2, SearchByMatchBird's Frame / CurrentFrame... see below), it
+    // takes them from the handle instead and does not read those three members; n must equal resident->N().  The
+    // other members (hasMapPoint, the scale tables, keys where a method reads them on the host) are read as before.
+    const ResidentFrame* resident = nullptr;
     int N() const { return n; }
 };
 // Tags standing for the reference's Frame& and KeyFrame* arguments (so the overloads keep the
@@ -194,6 +237,22 @@ public:
     int BirdviewMatch(const FrameData& F1, const FrameData& F2, std::vector<int>& vnMatches12,
                       std::vector<Point2f>& vPrevMatched, int windowSize = 10);
     int BirdviewMatch(const FrameData& F1, const FrameData& F2, std::vector<int>& vnMatches12, int windowSize = 10);
+
+    // Every method that takes a FrameGrid plus arrays as its train side also accepts that side as a ResidentFrame:
+    // set FeatureSet::resident (or use the overloads below, which do so) and the call goes to the handle form of the
+    // C-ABI with results equal to the FrameGrid form's.  That covers SearchForInitialization / BirdviewMatch (F2;
+    // F2.keys are still read on the host to update vbPrevMatched), the three Frame forms and the two keyframe forms of
+    // SearchByProjection, SearchByProjectionBird, SearchByMatchBird(KF, F), FuseSearch and SearchBySim3 (each
+    // target's kf).  SearchByMatchBird(CurrentFrame, LastFrame) has no handle form in the C-ABI and ignores it.
+    int SearchByProjection(const ResidentFrame& CurrentFrame, FrameData& members, const ProjectedLastFrame& LastFrame,
+                           const float th, const bool bMono, std::vector<int>& vpMapPointMatches);
+    int SearchByProjection(const ResidentFrame& F, FrameData& members, const ProjectedMapPoints& vpMapPoints,
+                           const float th, std::vector<int>& vpMapPointMatches);
+    int SearchByProjectionBird(const ResidentFrame& F, FrameData& members, const ProjectedBirdPoints& vpMapPointsBird,
+                               const float r, std::vector<int>& vpMapPointMatchesBird);
+    int SearchByMatchBird(const KeyFrameBirdPoints& KF, const ResidentFrame& F, std::vector<int>& vpMapPointMatchesBird,
+                          const float r);
+    int BirdviewMatch(const FrameData& F1, const ResidentFrame& F2, std::vector<int>& vnMatches12, int windowSize = 10);
 
     // ORBmatcher.cc:1328-1470.  CurrentFrame: keys (mvKeysUn), descriptors, grid, uRight (NULL: monocular, all -1),
     // hasMapPoint (mvpMapPoints[i] && Observations() > 0; NULL: none), scaleFactors, nlevels.

@@ -11,11 +11,11 @@ import ctypes
 import numpy as np
 
 from ._lib import (VARIANT_BLUR_HALFUP, VARIANT_DEFAULT, VARIANT_NO_FMA, VARIANT_RESIZE_GENERIC,
-                   VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, OrbProjTarget, check,
-                   lib)
+                   VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, OrbProjFrameTarget,
+                   OrbProjTarget, check, lib)
 
 __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError", "device_count",
-           "features_in_area", "frame_grid", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
+           "features_in_area", "frame_grid", "Frame", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
            "PROJ_GATE_NONE", "PROJ_GATE_FUSE", "proj_queries", "project_best_host",
            "compute_stereo_matches", "ORBVocabulary", "BirdORB", "cornerSubPix",
            "bird_footprint_mask", "VARIANT_DEFAULT", "VARIANT_TIE_REVERSE", "VARIANT_RESIZE_GENERIC",
@@ -221,6 +221,12 @@ class BatchExtractor(_Ctx):
         check(lib().orb_memcpy_d2h(self.h, _p(desc), self.d_desc + frame * self.kp_cap * 32, desc.nbytes), "d2h")
         return kps[:n], desc[:n]
 
+    def frame_slots(self, frame):
+        """(n, d_desc, d_kps): the keypoint count and the device pointers of frame `frame`'s output slots of the last
+        launch, as Frame.from_device takes them: a resident Frame without a host copy of the descriptors."""
+        n = int(self.counts()[frame])
+        return n, self.d_desc + frame * self.kp_cap * 32, self.d_kps + frame * self.kp_cap * 28
+
     def profile(self, on=True):
         check(lib().orb_profile_enable(self.h, int(on)), "orb_profile_enable")
 
@@ -321,6 +327,94 @@ def _frame_grid_arg(grid, min_xy=(0.0, 0.0)):
     return g, (off, idx)
 
 
+def _ctx_handle(ctx_or_matcher):
+    c = getattr(ctx_or_matcher, "_ctx", ctx_or_matcher)
+    return c.h
+
+
+class Frame:
+    """A device-resident Frame / KeyFrame (orb_frame): descriptors, undistorted keypoints and optionally mvuRight,
+    uploaded once, with the Frame grid built on the GPU (Frame::AssignFeaturesToGrid).  The grid searches of ORBmatcher
+    take it as their train side (frame=...), so a frame searched several times is staged once.
+
+    Frame(ctx_or_matcher, desc, kps_un, bounds=(mnMinX, mnMaxX, mnMinY, mnMaxY), uright=None) derives the inverse cell
+    sizes as frame_grid() does; Frame(..., inv=(inv_w, inv_h)) gives them directly with origin min_xy (default (0, 0):
+    the birdview grid).  ctx_or_matcher: an ORBmatcher, or any object of this module that owns a context (its GPU is
+    the frame's).  close() frees it; close every Frame before its context."""
+
+    def __init__(self, ctx_or_matcher, desc, kps_un, bounds=None, inv=None, uright=None, min_xy=(0.0, 0.0)):
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        k = np.ascontiguousarray(kps_un, KP_DTYPE)
+        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        assert len(d) == len(k) and (ur is None or len(ur) == len(k))
+        self._create("orb_frame_create", ctx_or_matcher, len(k), _p(d), _p(k), _p(ur), bounds, inv, min_xy)
+
+    @classmethod
+    def from_device(cls, ctx_or_matcher, n, d_desc, d_kps, bounds=None, inv=None, d_uright=None, min_xy=(0.0, 0.0)):
+        """A Frame from n descriptors / keypoints (and optionally uright) already in device memory of the context's
+        GPU (ints: e.g. BatchExtractor.frame_slots(f)); copied device-to-device."""
+        self = cls.__new__(cls)
+        vp = ctypes.c_void_p
+        self._create("orb_frame_create_device", ctx_or_matcher, int(n), vp(d_desc), vp(d_kps),
+                     None if d_uright is None else vp(d_uright), bounds, inv, min_xy)
+        return self
+
+    def _create(self, fn, ctx_or_matcher, n, desc, kps, ur, bounds, inv, min_xy):
+        self.h = None
+        assert (bounds is None) != (inv is None), "give bounds=(min_x, max_x, min_y, max_y) or inv=(inv_w, inv_h)"
+        f32 = np.float32
+        if bounds is not None:
+            min_x, max_x, min_y, max_y = bounds
+            inv_w = f32(64) / (f32(max_x) - f32(min_x))   # Frame.cc:102-103, as frame_grid()
+            inv_h = f32(48) / (f32(max_y) - f32(min_y))
+        else:
+            (min_x, min_y), (inv_w, inv_h) = min_xy, inv
+        self.min_xy, self.inv = (float(f32(min_x)), float(f32(min_y))), (float(inv_w), float(inv_h))
+        self.has_uright = ur is not None
+        out = ctypes.c_void_p()
+        check(getattr(lib(), fn)(_ctx_handle(ctx_or_matcher), n, desc, kps, ur, self.min_xy[0], self.min_xy[1],
+                                 self.inv[0], self.inv[1], ctypes.byref(out)), fn)
+        self.h = out
+        self.n = lib().orb_frame_count(self.h)
+
+    def __len__(self):
+        return self.n
+
+    def grid(self):
+        """(cell_off, cell_idx) of the grid the GPU built, as frame_grid() returns them."""
+        off = np.zeros(64 * 48 + 1, np.int32)
+        idx = np.zeros(max(self.n, 1), np.int32)
+        ns = ctypes.c_int()
+        check(lib().orb_frame_grid_read(self.h, _p(off), _p(idx), self.n, ctypes.byref(ns)), "orb_frame_grid_read")
+        return off, idx[:ns.value]
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().orb_frame_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class _ProjFrameTargets:
+    """orb_proj_frame_target array over target dicts: q, qdesc, frame (a Frame) and optionally inv_sigma2."""
+
+    def __init__(self, targets):
+        self.keep, self.out = [], []
+        self.arr = (OrbProjFrameTarget * max(len(targets), 1))()
+        for k, t in enumerate(targets):
+            q = np.ascontiguousarray(t["q"], PROJ_QUERY_DTYPE)
+            qd = np.ascontiguousarray(t["qdesc"], np.uint8).reshape(-1, 32)
+            assert len(q) == len(qd)
+            inv = None if t.get("inv_sigma2") is None else np.ascontiguousarray(t["inv_sigma2"], np.float32)
+            bi, bd = np.full(max(len(q), 1), -1, np.int32), np.full(max(len(q), 1), -1, np.int32)
+            self.arr[k] = OrbProjFrameTarget(len(q), _p(q), _p(qd), t["frame"].h, _p(inv),
+                                             0 if inv is None else len(inv), _p(bi), _p(bd))
+            self.keep.append((q, qd, inv, t["frame"]))
+            self.out.append((bi[:len(q)], bd[:len(q)]))
+
+
 def proj_queries(u, v, radius, level, ur=None, level_above=0, angle=None):
     """PROJ_QUERY_DTYPE array of projected map points with predicted levels `level`: the window (u, v, radius), the
     level range (level - 1, level + level_above), ur (Fuse's gate), angle (the rotation check); blocks = 1."""
@@ -372,8 +466,11 @@ def project_best_host(gate, target, query):
 
 
 def _kf_target(kf, pts, level_above=0):
-    """A target dict from a keyframe dict (desc, kps, grid, and optionally min_xy, uright, inv_sigma2) and its
-    projected points (u, v, radius, level, desc, and optionally ur)."""
+    """A target dict from a keyframe dict (desc, kps, grid, and optionally min_xy, uright, inv_sigma2; or frame (a
+    Frame) and optionally inv_sigma2) and its projected points (u, v, radius, level, desc, and optionally ur)."""
+    if kf.get("frame") is not None:
+        return dict(q=proj_queries(pts["u"], pts["v"], pts["radius"], pts["level"], pts.get("ur"), level_above),
+                    qdesc=pts["desc"], frame=kf["frame"], inv_sigma2=kf.get("inv_sigma2"))
     return dict(q=proj_queries(pts["u"], pts["v"], pts["radius"], pts["level"], pts.get("ur"), level_above),
                 qdesc=pts["desc"], tdesc=kf["desc"], kps_t=kf["kps"], grid=kf["grid"],
                 min_xy=kf.get("min_xy", (0.0, 0.0)), t_uright=kf.get("uright"), inv_sigma2=kf.get("inv_sigma2"))
@@ -545,11 +642,24 @@ class ORBmatcher:
                                      _p(a[5]), _p(out), ctypes.byref(nm)), "window match")
         return nm.value, out
 
-    def window_match_grid(self, level0_only, desc1, kps1, desc2, kps2, grid, window, centres=None, min_xy=(0.0, 0.0)):
+    def window_match_grid(self, level0_only, desc1, kps1, desc2=None, kps2=None, grid=None, window=None, centres=None,
+                          min_xy=(0.0, 0.0), frame=None):
         """orb_window_match_grid: the window searches with GetFeaturesInArea on the device over F2's grid
-        (frame_grid(...)); centres: (n1, 2) float32 window centres or None = kps1 positions."""
-        a = [np.ascontiguousarray(x) for x in (desc1, np.asarray(kps1, KP_DTYPE), desc2, np.asarray(kps2, KP_DTYPE))]
+        (frame_grid(...)); centres: (n1, 2) float32 window centres or None = kps1 positions.  frame: F2 as a
+        resident Frame (orb_window_match_frame; desc2, kps2 and grid are then not read)."""
         cen = None if centres is None else np.ascontiguousarray(centres, np.float32).reshape(-1, 2)
+        assert window is not None, "window_match_grid: window"
+        assert (frame is None) != (desc2 is None and kps2 is None and grid is None), \
+            "window_match_grid: give F2 as desc2, kps2 and grid, or as frame=, not both"
+        if frame is not None:
+            d1, k1 = np.ascontiguousarray(desc1), np.ascontiguousarray(np.asarray(kps1, KP_DTYPE))
+            out = np.full(max(len(d1), 1), -1, np.int32)
+            nm = ctypes.c_int()
+            check(lib().orb_window_match_frame(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation),
+                                               int(level0_only), len(d1), _p(d1), _p(k1), _p(cen), float(window),
+                                               frame.h, _p(out), ctypes.byref(nm)), "window match (frame)")
+            return nm.value, out[:len(d1)]
+        a = [np.ascontiguousarray(x) for x in (desc1, np.asarray(kps1, KP_DTYPE), desc2, np.asarray(kps2, KP_DTYPE))]
         g, _grid_arrays = _frame_grid_arg(grid, min_xy)
         out = np.full(max(len(a[0]), 1), -1, np.int32)
         nm = ctypes.c_int()
@@ -558,15 +668,31 @@ class ORBmatcher:
                                           _p(a[3]), g, _p(out), ctypes.byref(nm)), "window match (grid)")
         return nm.value, out[:len(a[0])]
 
-    def search_by_projection(self, mode, queries, qdesc, tdesc, kps_t, grid, t_uright=None, t_taken=None,
-                             min_xy=(0.0, 0.0), max_dist=TH_HIGH):
+    def search_by_projection(self, mode, queries, qdesc, tdesc=None, kps_t=None, grid=None, t_uright=None,
+                             t_taken=None, min_xy=(0.0, 0.0), max_dist=TH_HIGH, frame=None, use_uright=False):
         """orb_search_by_projection: the projection-gated searches' core.  queries: PROJ_QUERY_DTYPE array (one per
         projected map point) with descriptors qdesc; trains tdesc / kps_t with their grid (frame_grid(...)),
         t_uright (mvuRight; None = no stereo gate) and t_taken (mvpMapPoints[t] && Observations() > 0; None = none).
         Returns (nmatches, match_t): match_t[t] = the last query assigned to train t, -1 = untouched, -2 = reset
-        by the rotation cull."""
+        by the rotation cull.  frame: the trains as a resident Frame (orb_search_by_projection_frame) in place of
+        tdesc, kps_t, grid, min_xy and t_uright; use_uright then says whether the stereo gate reads the Frame's own
+        uright (it is not read without frame=)."""
+        assert (frame is None) != (tdesc is None and kps_t is None and grid is None and t_uright is None), \
+            "search_by_projection: give the trains as tdesc, kps_t, grid (and t_uright), or as frame=, not both"
         qa = np.ascontiguousarray(queries, PROJ_QUERY_DTYPE)
         qd = np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
+        if frame is not None:
+            assert len(qa) == len(qd)
+            tk = None if t_taken is None else np.ascontiguousarray(t_taken, np.uint8)
+            assert tk is None or len(tk) == len(frame)
+            out = np.full(max(len(frame), 1), -1, np.int32)
+            nm = ctypes.c_int()
+            check(lib().orb_search_by_projection_frame(self._ctx.h, int(mode), self.mfNNratio,
+                                                       int(self.mbCheckOrientation), int(max_dist), len(qa), _p(qa),
+                                                       _p(qd), frame.h, _p(tk),
+                                                       int(bool(use_uright)), _p(out),
+                                                       ctypes.byref(nm)), "orb_search_by_projection_frame")
+            return nm.value, out[:len(frame)]
         td = np.ascontiguousarray(tdesc, np.uint8).reshape(-1, 32)
         kt = np.ascontiguousarray(kps_t, KP_DTYPE)
         assert len(qa) == len(qd) and len(td) == len(kt)
@@ -582,8 +708,8 @@ class ORBmatcher:
         return nm.value, out[:len(kt)]
 
     def SearchByProjection_CF_LF(self, u, v, invzc, octave, angle, observed, desc_mp, scale_factors, mbf, th, bMono,
-                                 desc_cf, kps_cf, grid_cf, uright_cf=None, taken_cf=None, min_xy=(0.0, 0.0),
-                                 bForward=False, bBackward=False):
+                                 desc_cf=None, kps_cf=None, grid_cf=None, uright_cf=None, taken_cf=None,
+                                 min_xy=(0.0, 0.0), bForward=False, bBackward=False, frame=None):
         """SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono) (ORBmatcher.cc:1328-1470).
         Per LastFrame map point the search keeps (the caller drops outliers, invzc < 0 and projections out of
         bounds, :1355-1376): its projection (u, v) and invzc, LastFrame.mvKeys[i].octave, mvKeysUn[i].angle,
@@ -606,10 +732,12 @@ class ORBmatcher:
         q["ur_tol"] = q["r"]
         q["angle"] = np.asarray(angle, f32)
         q["blocks"] = np.asarray(observed, bool)
-        return self.search_by_projection(PROJ_BEST, q, desc_mp, desc_cf, kps_cf, grid_cf, uright_cf, taken_cf, min_xy)
+        return self.search_by_projection(PROJ_BEST, q, desc_mp, desc_cf, kps_cf, grid_cf, uright_cf, taken_cf, min_xy,
+                                         frame=frame, use_uright=frame is not None and frame.has_uright)
 
     def SearchByProjection_F_MapPoints(self, proj_x, proj_y, proj_xr, level, view_cos, desc_mp, scale_factors, th,
-                                       desc_f, kps_f, grid_f, uright_f=None, taken_f=None, min_xy=(0.0, 0.0)):
+                                       desc_f=None, kps_f=None, grid_f=None, uright_f=None, taken_f=None,
+                                       min_xy=(0.0, 0.0), frame=None):
         """SearchByProjection(Frame& F, const vector<MapPoint*>&, th) (ORBmatcher.cc:45-129).  Per map point with
         mbTrackInView && !isBad() (:54-58, filtered by the caller): mTrackProjX / Y / XR, mnTrackScaleLevel,
         mTrackViewCos and its descriptor.  Returns (nmatches, match_f)."""
@@ -626,9 +754,10 @@ class ORBmatcher:
         q["ur_tol"] = q["r"]                                               # :94
         q["blocks"] = 1
         return self.search_by_projection(PROJ_RATIO_SAME_LEVEL, q, desc_mp, desc_f, kps_f, grid_f, uright_f, taken_f,
-                                         min_xy)
+                                         min_xy, frame=frame, use_uright=frame is not None and frame.has_uright)
 
-    def SearchByProjectionBird(self, pt_x, pt_y, desc_mp, r, desc_bird, kps_bird, grid_bird, taken_bird=None):
+    def SearchByProjectionBird(self, pt_x, pt_y, desc_mp, r, desc_bird=None, kps_bird=None, grid_bird=None,
+                               taken_bird=None, frame=None):
         """SearchByProjectionBird(Frame& F, const vector<MapPointBird*>&, r) (ORBmatcher.cc:1923-1998).  Per birdview
         map point the search keeps (:1933-1943, filtered by the caller): its birdview projection pt and descriptor;
         the Frame's mDescriptorsBird, mvKeysBird, birdview grid.  Returns (nmatches, match_bird)."""
@@ -638,10 +767,10 @@ class ORBmatcher:
         q["min_level"], q["max_level"] = -1, -1                            # GetFeaturesInAreaBirdview's defaults
         q["blocks"] = 1
         return self.search_by_projection(PROJ_RATIO_SAME_LEVEL, q, desc_mp, desc_bird, kps_bird, grid_bird, None,
-                                         taken_bird)
+                                         taken_bird, frame=frame)
 
-    def SearchByMatchBird(self, index, pt_x, pt_y, angle, desc_mp, r, desc_bird, kps_bird, grid_bird,
-                          max_dist=TH_HIGH):
+    def SearchByMatchBird(self, index, pt_x, pt_y, angle, desc_mp, r, desc_bird=None, kps_bird=None, grid_bird=None,
+                          max_dist=TH_HIGH, frame=None):
         """SearchByMatchBird(KeyFrame* pKF, Frame& F, vector<MapPointBird*>&, r) (ORBmatcher.cc:2000-2114).  Per
         birdview keypoint k of the keyframe with a MapPointBird (the caller leaves the others out): index = k,
         pKF->mvKeysBird[k].pt and .angle, the map point's descriptor; the Frame's mDescriptorsBird, mvKeysBird and
@@ -651,6 +780,15 @@ class ORBmatcher:
         xy = np.ascontiguousarray(np.stack([np.asarray(pt_x, np.float32), np.asarray(pt_y, np.float32)], 1))
         ang = np.ascontiguousarray(angle, np.float32)
         qd = np.ascontiguousarray(desc_mp, np.uint8).reshape(-1, 32)
+        if frame is not None:   # the Frame's birdview side as a resident Frame (orb_search_by_match_bird_resident)
+            assert len(ids) == len(xy) == len(ang) == len(qd)
+            out = np.full(max(len(frame), 1), -1, np.int32)
+            nm = ctypes.c_int()
+            check(lib().orb_search_by_match_bird_resident(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation),
+                                                          int(max_dist), float(r), len(qd), _p(ids), _p(xy), _p(ang),
+                                                          _p(qd), frame.h, _p(out), ctypes.byref(nm)),
+                  "orb_search_by_match_bird_resident")
+            return nm.value, out[:len(frame)]
         td = np.ascontiguousarray(desc_bird, np.uint8).reshape(-1, 32)
         kt = np.ascontiguousarray(kps_bird, KP_DTYPE)
         assert len(ids) == len(xy) == len(ang) == len(qd) and len(td) == len(kt)
@@ -687,9 +825,15 @@ class ORBmatcher:
     def project_best_batch(self, gate, targets):
         """orb_project_best_batch: the per-query searches (Fuse, SearchBySim3) of many targets in one GPU call.
         targets: dicts with q (PROJ_QUERY_DTYPE; proj_queries(...)), qdesc, tdesc, kps_t, grid (frame_grid(...)) and
-        optionally min_xy, t_uright, inv_sigma2 (gate PROJ_GATE_FUSE needs inv_sigma2).  Returns per target
+        optionally min_xy, t_uright, inv_sigma2 (gate PROJ_GATE_FUSE needs inv_sigma2); or, for every target, frame (a
+        resident Frame) in place of tdesc, kps_t, grid, min_xy and t_uright (orb_project_best_frames).  Returns per target
         (best_idx, best_dist): the train with the smallest distance (first in GetFeaturesInArea order on ties) among
         the candidates that pass the level filter and the gate, -1 / -1 where none does."""
+        if targets and all(t.get("frame") is not None for t in targets):   # every target's trains resident
+            T = _ProjFrameTargets(targets)
+            check(lib().orb_project_best_frames(self._ctx.h, int(gate), len(targets), ctypes.addressof(T.arr)),
+                  "orb_project_best_frames")
+            return T.out
         T = _ProjTargets(targets)
         check(lib().orb_project_best_batch(self._ctx.h, int(gate), len(targets), ctypes.addressof(T.arr)),
               "orb_project_best_batch")
@@ -716,7 +860,7 @@ class ORBmatcher:
         index = i2.  Both directions are one GPU call.  Returns (nFound, vnMatch12): vnMatch12[i1] = the KF2
         feature both directions agree on, else -1."""
         (b1, d1), (b2, d2) = self.project_best_batch(PROJ_GATE_NONE, [_kf_target(kf2, pts1in2), _kf_target(kf1, pts2in1)])
-        n1, n2 = len(kf1["kps"]), len(kf2["kps"])
+        n1, n2 = (len(k["frame"]) if k.get("frame") is not None else len(k["kps"]) for k in (kf1, kf2))
         vn1, vn2 = np.full(n1, -1, np.int32), np.full(n2, -1, np.int32)
         ok1, ok2 = (b1 >= 0) & (d1 <= TH_HIGH), (b2 >= 0) & (d2 <= TH_HIGH)      # :1221, :1301
         vn1[np.asarray(pts1in2["index"], np.int64)[ok1]] = b1[ok1]
@@ -735,8 +879,8 @@ class ORBmatcher:
         point now matched to feature idx, -1 where the call matched none."""
         q = proj_queries(pts["u"], pts["v"], pts["radius"], pts["level"])
         m = ORBmatcher(self.mfNNratio, False)
-        return m.search_by_projection(PROJ_BEST, q, pts["desc"], kf["desc"], kf["kps"], kf["grid"], None, matched,
-                                      kf.get("min_xy", (0.0, 0.0)), max_dist=TH_LOW)
+        return m.search_by_projection(PROJ_BEST, q, pts["desc"], kf.get("desc"), kf.get("kps"), kf.get("grid"), None,
+                                      matched, kf.get("min_xy", (0.0, 0.0)), max_dist=TH_LOW, frame=kf.get("frame"))
 
     def SearchByProjection_F_KF(self, pts, frame, has_mp, orb_dist):
         """SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th, ORBdist)
@@ -744,8 +888,9 @@ class ORBmatcher:
         angle (pKF->mvKeysUn[i].angle), desc); frame: dict(desc, kps, grid, min_xy); has_mp[i2] =
         CurrentFrame.mvpMapPoints[i2] != NULL.  Returns (nmatches, match_f) as search_by_projection does."""
         q = proj_queries(pts["u"], pts["v"], pts["radius"], pts["level"], None, 1, pts["angle"])
-        return self.search_by_projection(PROJ_BEST, q, pts["desc"], frame["desc"], frame["kps"], frame["grid"], None,
-                                         has_mp, frame.get("min_xy", (0.0, 0.0)), max_dist=int(orb_dist))
+        return self.search_by_projection(PROJ_BEST, q, pts["desc"], frame.get("desc"), frame.get("kps"),
+                                         frame.get("grid"), None, has_mp, frame.get("min_xy", (0.0, 0.0)),
+                                         max_dist=int(orb_dist), frame=frame.get("frame"))
 
     def SearchForInitialization(self, desc1, kps1, desc2, kps2, cand_off, cand_idx):
         """SearchForInitialization (ORBmatcher.cc:405-520); candidates = F2.GetFeaturesInArea per query.

@@ -56,6 +56,11 @@ class OrbProjTarget(ctypes.Structure):   # orb_proj_target
                 ("inv_sigma2", vp), ("nlevels", ci), ("grid", OrbFrameGrid), ("best_idx", vp), ("best_dist", vp)]
 
 
+class OrbProjFrameTarget(ctypes.Structure):   # orb_proj_frame_target
+    _fields_ = [("nq", ci), ("q", vp), ("qdesc", vp), ("frame", vp), ("inv_sigma2", vp), ("nlevels", ci),
+                ("best_idx", vp), ("best_dist", vp)]
+
+
 # name -> (restype, argtypes); mirrors include/orbgpu.h
 SIGNATURES = {
     "orb_abi_version": (ci, []),
@@ -108,6 +113,15 @@ SIGNATURES = {
                                             ctypes.POINTER(ci)]),
     "orb_project_best_batch": (ci, [vp, ci, ci, vp]),
     "orb_project_best_host": (ci, [ci, vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "orb_frame_create": (ci, [vp, ci, vp, vp, vp, cf, cf, cf, cf, ctypes.POINTER(vp)]),
+    "orb_frame_create_device": (ci, [vp, ci, vp, vp, vp, cf, cf, cf, cf, ctypes.POINTER(vp)]),
+    "orb_frame_destroy": (None, [vp]),
+    "orb_frame_count": (ci, [vp]),
+    "orb_frame_grid_read": (ci, [vp, vp, vp, ci, ctypes.POINTER(ci)]),
+    "orb_search_by_projection_frame": (ci, [vp, ci, cf, ci, ci, ci, vp, vp, vp, vp, ci, vp, ctypes.POINTER(ci)]),
+    "orb_window_match_frame": (ci, [vp, cf, ci, ci, ci, vp, vp, vp, cf, vp, vp, ctypes.POINTER(ci)]),
+    "orb_search_by_match_bird_resident": (ci, [vp, cf, ci, ci, cf, ci, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ci)]),
+    "orb_project_best_frames": (ci, [vp, ci, ci, vp]),
     "orb_features_in_area": (ci, [ci, vp, cf, cf, cf, cf, cf, cf, cf, ci, ci, vp, ci]),
     "orb_compute_stereo_matches": (ci, [vp, vp, ci, vp, vp, ci, vp, vp, cf, cf, vp, vp, ctypes.POINTER(ci)]),
     "orb_stereo_batch_device": (ci, [vp, ci, cf, cf, vp, vp, vp]),
