@@ -122,24 +122,20 @@ hipError_t launch_frame_grid(const orb_keypoint* d_kps, int n, const ProjGrid& g
 
 namespace {
 
-int frame_arg_error(const char* fn, const char* why) {
-    return set_error((std::string(fn) + ": " + why).c_str(), hipSuccess), ORB_ERR_ARG;
-}
-
 // Both creators: src_kind says where desc / kps / uright live.  The keypoints come to the host copy (from the host
 // array, or once from the device), the grid is built on the context's stream, and the call returns synchronised.
 int frame_create(const char* fn, Ctx* c, int n, const uint8_t* desc, const orb_keypoint* kps, const float* uright,
                  float min_x, float min_y, float inv_w, float inv_h, hipMemcpyKind src_kind, orb_frame** out) {
-    if (!out) return frame_arg_error(fn, "out NULL");
-    if (n < 0) return frame_arg_error(fn, "n < 0");
-    if (n > 0 && (!desc || !kps)) return frame_arg_error(fn, "NULL arrays with n > 0");
+    if (!out) return arg_error(fn, "out NULL");
+    if (n < 0) return arg_error(fn, "n < 0");
+    if (n > 0 && (!desc || !kps)) return arg_error(fn, "NULL arrays with n > 0");
     if (!std::isfinite(inv_w) || !std::isfinite(inv_h) || inv_w <= 0 || inv_h <= 0)
-        return frame_arg_error(fn, "inverse cell size not finite or not positive");
-    if (!std::isfinite(min_x) || !std::isfinite(min_y)) return frame_arg_error(fn, "grid origin not finite");
+        return arg_error(fn, "inverse cell size not finite or not positive");
+    if (!std::isfinite(min_x) || !std::isfinite(min_y)) return arg_error(fn, "grid origin not finite");
     if (src_kind == hipMemcpyHostToDevice)
         for (int i = 0; i < n; i++)
             if (!std::isfinite(kps[i].x) || !std::isfinite(kps[i].y))
-                return frame_arg_error(fn, "keypoint position not finite");
+                return arg_error(fn, "keypoint position not finite");
     if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return set_error("hipSetDevice", e), ORB_ERR_HIP;
@@ -235,7 +231,7 @@ int orb_frame_count(const orb_frame* F) { return F ? F->n : 0; }
 
 int orb_frame_grid_read(const orb_frame* F, int* cell_off, int* cell_idx, int cap, int* nslots) {
     const char* const fn = "orb_frame_grid_read";
-    if (!F || !cell_off || cap < 0 || (cap > 0 && !cell_idx)) return frame_arg_error(fn, "bad arguments");
+    if (!F || !cell_off || cap < 0 || (cap > 0 && !cell_idx)) return arg_error(fn, "bad arguments");
     hipError_t e = hipSetDevice(F->device);
     if (e != hipSuccess) return set_error("hipSetDevice", e), ORB_ERR_HIP;
     if ((e = hipMemcpy(cell_off, F->d_coff, (size_t)(kFrameGridCells + 1) * 4, hipMemcpyDeviceToHost)) != hipSuccess)

@@ -23,11 +23,6 @@ constexpr int TH_LOW = 50;          // ORBmatcher.cc:38
 constexpr int HISTO_LENGTH = 30;    // :39
 constexpr int K = 8;
 
-// A refused argument: the message "<fn>: <why>" for orb_last_error(), and the status.
-int arg_error(const char* fn, const std::string& why) {
-    return set_error((std::string(fn) + ": " + why).c_str(), hipSuccess), ORB_ERR_ARG;
-}
-
 int rot_bin(float a1, float a2) {   // ORBmatcher.cc:236-243 (round(rot*(1/30)): bins 0..12, upstream quirk)
     const float factor = 1.0f / HISTO_LENGTH;
     float rot = a1 - a2;
@@ -105,6 +100,90 @@ void for_common_nodes(const orb_featvec& a, const orb_featvec& b, F f) {   // st
     }
 }
 
+// What is wrong with a Frame grid CSR over nt trains, or NULL: cell_off missing, or cell_idx missing where the grid
+// has slots; then the CSR itself, since the grid kernels read cell_idx[cell_off[..]] for every rectangle column and
+// index the trains by cell_idx, so a malformed one would be an out-of-bounds device read.
+const char* grid_csr_fault(const orb_frame_grid& g, int nt) {
+    if (!g.cell_off || (g.cell_off[kFrameGridCells] && !g.cell_idx)) return "bad arguments";
+    if (g.cell_off[0] != 0) return "grid cell_off[0] != 0";
+    for (int i = 0; i < kFrameGridCells; i++)   // offsets non-decreasing, so every run lies in [0, cell_off[3072])
+        if (g.cell_off[i + 1] < g.cell_off[i]) return "grid cell_off decreases";
+    for (int i = 0, nslots = g.cell_off[kFrameGridCells]; i < nslots; i++)   // the device indexes the trains by these
+        if (g.cell_idx[i] < 0 || g.cell_idx[i] >= nt) return "grid index out of range";
+    return nullptr;
+}
+
+// The train side of a grid search: host arrays with their Frame grid CSR, staged and uploaded by the call, or a
+// resident frame, whose arrays and grid are on the device already.  Either way n trains, the host keypoints the
+// replays read, and the grid's geometry.
+struct TrainSide {
+    int n = 0;
+    const orb_keypoint* kps = nullptr;
+    float min_x = 0, min_y = 0, inv_w = 0, inv_h = 0;
+    const uint8_t* desc = nullptr;   // the host form: descriptors, uright (NULL: no stereo gate), the grid's CSR
+    const float* uright = nullptr;
+    const int* cell_off = nullptr;
+    const int* cell_idx = nullptr;
+    const orb_frame* F = nullptr;    // the resident form (use_ur: gate on its uright)
+    bool use_ur = false;
+
+    TrainSide() = default;
+    TrainSide(int nt, const uint8_t* tdesc, const orb_keypoint* kps_t, const float* t_uright, const orb_frame_grid& g)
+        : n(nt), kps(kps_t), min_x(g.min_x), min_y(g.min_y), inv_w(g.inv_w), inv_h(g.inv_h), desc(tdesc),
+          uright(t_uright), cell_off(g.cell_off), cell_idx(g.cell_idx) {}
+    TrainSide(const orb_frame* frame, bool use_uright)   // (frame != NULL)
+        : n(frame->n), kps(frame->kps.data()), min_x(frame->min_x), min_y(frame->min_y), inv_w(frame->inv_w),
+          inv_h(frame->inv_h), F(frame), use_ur(use_uright) {}
+
+    bool has_ur() const { return F ? use_ur : uright != nullptr; }
+    // What is wrong with the host form (n >= 0), or NULL: an array missing, then the grid.  A resident frame's arrays
+    // and CSR are the library's own
+    const char* fault() const {
+        if (F) return nullptr;
+        if (n > 0 && (!desc || !kps)) return "bad arguments";
+        return grid_csr_fault(orb_frame_grid{min_x, min_y, inv_w, inv_h, cell_off, cell_idx}, n);
+    }
+    bool on_other_device(const Ctx* c) const { return F && F->device != c->device; }
+};
+
+// A train side's place in a call's staging area.  The host form's regions are laid out in the kernels' order, [t | k2
+// | ur] with add_arrays() and [cell_off | cell_idx] with add_grid(), and written with put(); a resident side has no
+// regions and all three do nothing.  row() gives the device pointers the kernels take, into the staging area or into
+// the frame's allocation, as a row of k_projection_best's table (inv_sigma2 left to the caller).
+struct TrainStage {
+    TrainSide s;
+    bool ur = false;   // the kernel gates on uright
+    size_t o_t = 0, o_k2 = 0, o_ur = 0, o_coff = 0, o_cidx = 0;
+    size_t nslots() const { return (size_t)s.cell_off[kFrameGridCells]; }
+    // ur_region: the layout has a uright region even without the gate (an empty one)
+    void add_arrays(Stage& st, bool ur_region) {
+        if (s.F) return;
+        o_t = st.add((size_t)s.n * 32);
+        o_k2 = st.add((size_t)s.n * sizeof(orb_keypoint));
+        if (ur || ur_region) o_ur = st.add(ur ? (size_t)s.n * 4 : 0);
+    }
+    void add_grid(Stage& st) {
+        if (s.F) return;
+        o_coff = st.add((size_t)(kFrameGridCells + 1) * 4);
+        o_cidx = st.add(nslots() * 4);
+    }
+    void put(const Stage& st) const {
+        if (s.F) return;
+        st.put(o_t, s.desc, (size_t)s.n * 32);
+        st.put(o_k2, s.kps, (size_t)s.n * sizeof(orb_keypoint));
+        if (ur) st.put(o_ur, s.uright, (size_t)s.n * 4);
+        st.put(o_coff, s.cell_off, (size_t)(kFrameGridCells + 1) * 4);
+        st.put(o_cidx, s.cell_idx, nslots() * 4);
+    }
+    ProjTarget row(const Stage& st) const {
+        const ProjGrid g{s.min_x, s.min_y, s.inv_w, s.inv_h};
+        if (const orb_frame* F = s.F)
+            return ProjTarget{F->d_desc, F->d_kps, ur ? F->d_ur : nullptr, nullptr, F->d_coff, F->d_cidx, g};
+        return ProjTarget{st.di<uint8_t>(o_t), st.di<orb_keypoint>(o_k2), ur ? st.di<float>(o_ur) : nullptr, nullptr,
+                          st.di<int>(o_coff), st.di<int>(o_cidx), g};
+    }
+};
+
 // One matcher call: static data on the device, re-rankable from any item with fresh thresholds.
 struct TopkSession {
     // which ranking kernel the session drives, and so which input regions its arena holds before the common tail
@@ -127,26 +206,24 @@ struct TopkSession {
     Mode mode = LIST;
     // arena offsets: the mode's inputs, then the tail every mode shares: [thr] (o_in_end: the end of the uploaded
     // span) and the outputs [dist | idx | nvalid]
-    size_t o_q = 0, o_t = 0, o_rng = 0, o_cand = 0, o_item = 0, o_cen = 0, o_k1 = 0, o_k2 = 0, o_pq = 0, o_ur = 0,
-           o_coff = 0, o_cidx = 0;
+    size_t o_q = 0, o_t = 0, o_rng = 0, o_cand = 0, o_item = 0, o_cen = 0, o_k1 = 0, o_pq = 0;
     size_t o_thr = 0, o_in_end = 0, o_dist = 0, o_idx = 0, o_nv = 0;
     bool uploaded = false;
-    WinGrid wg{};          // GRID / PROJ: the train frame's grid geometry as the kernel takes it
-    ProjGrid pg{};
+    // GRID / PROJ: the train side and its regions [t | k2 | ur | cell_off | cell_idx] (ur in PROJ only; none of them
+    // for a resident frame, whose device pointers the launch takes)
+    TrainStage train;
+    float win_r = 0;       // GRID: the window's radius
     bool cen = false;      // GRID: window centres given (else kps1)
-    bool has_ur = false;   // PROJ: stereo gate
-    // GRID / PROJ: the train side as a resident frame (else NULL: staged in the arena).  Its descriptors, keypoints,
-    // uright and grid are not laid out or uploaded; the launch takes the handle's device pointers
-    const orb_frame* ext = nullptr;
     int lanes = 64;        // PROJ: lanes per query
     // host results (indexed by item), in the pinned mirror
     const int* dist = nullptr;
     const int* idx = nullptr;
     const int* nvalid = nullptr;
 
-    // The layout of a call: begin(), the mode's input regions in the kernel's order with st.add() (and add_grid()),
-    // finish_layout(), which appends the shared tail and allocates, then the inputs with put() in that same order:
-    // the upload starts at offset 0, with the lines written first.
+    // The layout of a call: begin(), the mode's input regions in the kernel's order with st.add() (the train side's
+    // with train.add_arrays() and train.add_grid()), finish_layout(), which appends the shared tail and allocates,
+    // then the inputs with st.put() (train.put()) in that same order: the upload starts at offset 0, with the lines
+    // written first.
     // begin() returns false when there is nothing to rank: no GPU work at all
     bool begin(Mode m, int n_items, int ntrain) {
         mode = m;
@@ -154,10 +231,6 @@ struct TopkSession {
         nt = ntrain;
         st.c = c;
         return nitems > 0;
-    }
-    void add_grid(const orb_frame_grid& g) {
-        o_coff = st.add((size_t)(kFrameGridCells + 1) * 4);
-        o_cidx = st.add((size_t)g.cell_off[kFrameGridCells] * 4);
     }
     int finish_layout() {
         o_thr = st.add((size_t)nt * 4);
@@ -172,13 +245,6 @@ struct TopkSession {
         nvalid = st.h<int>(o_nv);
         return ORB_OK;
     }
-    void put(size_t o, const void* src, size_t bytes) {
-        if (bytes) std::memcpy(st.hi<uint8_t>(o), src, bytes);
-    }
-    void put_grid(const orb_frame_grid& g) {
-        put(o_coff, g.cell_off, (size_t)(kFrameGridCells + 1) * 4);
-        put(o_cidx, g.cell_idx, (size_t)g.cell_off[kFrameGridCells] * 4);
-    }
 
     // List mode: item i = query item_q[i] (or the row item_src[i]) against the candidates cand[item_rng[i]].
     int setup(const uint8_t* qdesc, const uint8_t* tdesc, int ntrain) {
@@ -192,90 +258,58 @@ struct TopkSession {
         uint8_t* hq = st.hi<uint8_t>(o_q);
         for (int i = 0; i < nitems; i++)
             std::memcpy(hq + (size_t)i * 32, item_src.empty() ? qdesc + (size_t)item_q[i] * 32 : item_src[i], 32);
-        if (tparts.empty()) put(o_t, tdesc, (size_t)nt * 32);
+        if (tparts.empty()) st.put(o_t, tdesc, (size_t)nt * 32);
         size_t o = o_t;
         for (const auto& tp : tparts) {
-            put(o, tp.first, (size_t)tp.second * 32);
+            st.put(o, tp.first, (size_t)tp.second * 32);
             o += (size_t)tp.second * 32;
         }
-        put(o_rng, item_rng.data(), (size_t)nitems * 8);
-        put(o_cand, cand, (size_t)ncand * 4);
+        st.put(o_rng, item_rng.data(), (size_t)nitems * 8);
+        st.put(o_cand, cand, (size_t)ncand * 4);
         return ORB_OK;
     }
 
     // Grid mode: queries = desc1 rows item_q[i] (uploaded whole, indexed on the device), candidates from
-    // the window around centres[item_q[i]] (NULL: kps1) in F2's grid.
-    // F2 given: the train side is that frame (desc2, kps2 and g's CSR are not read; g carries the geometry).
-    int setup_grid(const uint8_t* desc1, int n1, const orb_keypoint* kps1, const float* centres, const uint8_t* desc2,
-                   int n2, const orb_keypoint* kps2, const orb_frame_grid& g, float r, const orb_frame* F2 = nullptr) {
-        if (!begin(GRID, (int)item_q.size(), n2)) return ORB_OK;
-        ext = F2;
-        wg = WinGrid{g.min_x, g.min_y, g.inv_w, g.inv_h, r};
+    // the window of radius r around centres[item_q[i]] (NULL: kps1) in the train side's grid.
+    int setup_grid(const uint8_t* desc1, int n1, const orb_keypoint* kps1, const float* centres, float r,
+                   const TrainSide& side) {
+        if (!begin(GRID, (int)item_q.size(), side.n)) return ORB_OK;
+        train = TrainStage{side, false};
+        win_r = r;
         cen = centres != nullptr;
-        const size_t kp1 = (size_t)n1 * sizeof(orb_keypoint), kp2 = (size_t)n2 * sizeof(orb_keypoint);
+        const size_t kp1 = (size_t)n1 * sizeof(orb_keypoint);
         o_q = st.add((size_t)n1 * 32);
         o_item = st.add((size_t)nitems * 4);
         o_cen = st.add(cen ? (size_t)n1 * 8 : 0);
         o_k1 = st.add(kp1);
-        if (!ext) {
-            o_t = st.add((size_t)n2 * 32);
-            o_k2 = st.add(kp2);
-            add_grid(g);
-        }
+        train.add_arrays(st, false);
+        train.add_grid(st);
         const int rr = finish_layout();
         if (rr != ORB_OK) return rr;
-        put(o_q, desc1, (size_t)n1 * 32);
-        put(o_item, item_q.data(), (size_t)nitems * 4);
-        if (cen) put(o_cen, centres, (size_t)n1 * 8);
-        put(o_k1, kps1, kp1);
-        if (!ext) {
-            put(o_t, desc2, (size_t)n2 * 32);
-            put(o_k2, kps2, kp2);
-            put_grid(g);
-        }
+        st.put(o_q, desc1, (size_t)n1 * 32);
+        st.put(o_item, item_q.data(), (size_t)nitems * 4);
+        if (cen) st.put(o_cen, centres, (size_t)n1 * 8);
+        st.put(o_k1, kps1, kp1);
+        train.put(st);
         return ORB_OK;
     }
 
     // Projection mode (orb_search_by_projection): item i = query i with its own window (orb_proj_query) in the
-    // train frame's grid; uright == NULL: no stereo gate.
-    int setup_proj(int nq, const orb_proj_query* q, const uint8_t* qdesc, int ntrain, const uint8_t* tdesc,
-                   const orb_keypoint* kps_t, const float* uright, const orb_frame_grid& g, int nlanes) {
-        if (!begin(PROJ, nq, ntrain)) return ORB_OK;
-        pg = ProjGrid{g.min_x, g.min_y, g.inv_w, g.inv_h};
-        has_ur = uright != nullptr;
-        lanes = nlanes;
-        const size_t pq = (size_t)nq * sizeof(orb_proj_query), kp = (size_t)nt * sizeof(orb_keypoint);
-        o_pq = st.add(pq);
-        o_q = st.add((size_t)nq * 32);
-        o_t = st.add((size_t)nt * 32);
-        o_k2 = st.add(kp);
-        o_ur = st.add(has_ur ? (size_t)nt * 4 : 0);
-        add_grid(g);
-        const int rr = finish_layout();
-        if (rr != ORB_OK) return rr;
-        put(o_pq, q, pq);
-        put(o_q, qdesc, (size_t)nq * 32);
-        put(o_t, tdesc, (size_t)nt * 32);
-        put(o_k2, kps_t, kp);
-        if (has_ur) put(o_ur, uright, (size_t)nt * 4);
-        put_grid(g);
-        return ORB_OK;
-    }
-    // The same with the train frame resident: only the queries are staged.
-    int setup_proj(int nq, const orb_proj_query* q, const uint8_t* qdesc, const orb_frame* F, bool use_uright,
-                   int nlanes) {
-        if (!begin(PROJ, nq, F->n)) return ORB_OK;
-        ext = F;
-        pg = ProjGrid{F->min_x, F->min_y, F->inv_w, F->inv_h};
-        has_ur = use_uright;
+    // train side's grid, with the stereo gate if the side has uright.
+    int setup_proj(int nq, const orb_proj_query* q, const uint8_t* qdesc, const TrainSide& side, int nlanes) {
+        if (!begin(PROJ, nq, side.n)) return ORB_OK;
+        train = TrainStage{side, side.has_ur()};
         lanes = nlanes;
         const size_t pq = (size_t)nq * sizeof(orb_proj_query);
         o_pq = st.add(pq);
         o_q = st.add((size_t)nq * 32);
+        train.add_arrays(st, true);
+        train.add_grid(st);
         const int rr = finish_layout();
         if (rr != ORB_OK) return rr;
-        put(o_pq, q, pq);
-        put(o_q, qdesc, (size_t)nq * 32);
+        st.put(o_pq, q, pq);
+        st.put(o_q, qdesc, (size_t)nq * 32);
+        train.put(st);
         return ORB_OK;
     }
 
@@ -295,22 +329,18 @@ struct TopkSession {
         int* const out_dist = st.h<int>(o_dist) + (size_t)from * K;
         int* const out_idx = st.h<int>(o_idx) + (size_t)from * K;
         int* const out_nv = st.h<int>(o_nv) + from;
-        // GRID / PROJ: the train side, staged or resident
-        const uint8_t* const d_t = ext ? ext->d_desc : st.di<uint8_t>(o_t);
-        const orb_keypoint* const d_k2 = ext ? ext->d_kps : st.di<orb_keypoint>(o_k2);
-        const float* const d_ur = !has_ur ? nullptr : ext ? ext->d_ur : st.di<float>(o_ur);
-        const int* const d_coff = ext ? ext->d_coff : st.di<int>(o_coff);
-        const int* const d_cidx = ext ? ext->d_cidx : st.di<int>(o_cidx);
+        const ProjTarget T = train.row(st);   // GRID / PROJ: the train side, staged or resident
         if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
         switch (mode) {
         case PROJ:
             e = launch_projection_topk(st.di<orb_proj_query>(o_pq) + from, st.di<uint8_t>(o_q) + (size_t)from * 32, n,
-                                       d_t, d_k2, d_ur, d_coff, d_cidx, pg, d_thr, K, lanes, out_dist, out_idx, out_nv,
-                                       c->stream);
+                                       T.t, T.kps, T.ur, T.cell_off, T.cell_idx, T.g, d_thr, K, lanes, out_dist, out_idx,
+                                       out_nv, c->stream);
             break;
         case GRID:
             e = launch_window_topk(st.di<uint8_t>(o_q), st.di<int>(o_item) + from, cen ? st.di<float2>(o_cen) : nullptr, n,
-                                   st.di<orb_keypoint>(o_k1), d_t, d_k2, d_coff, d_cidx, wg, d_thr, K, out_dist, out_idx,
+                                   st.di<orb_keypoint>(o_k1), T.t, T.kps, T.cell_off, T.cell_idx,
+                                   WinGrid{T.g.min_x, T.g.min_y, T.g.inv_w, T.g.inv_h, win_r}, d_thr, K, out_dist, out_idx,
                                    out_nv, c->stream);
             break;
         case LIST:
@@ -480,16 +510,6 @@ int bow_kf_kf_run(Ctx* c, float nnratio, int check_ori, int n1, const uint8_t* d
 }  // namespace orbgpu
 
 using namespace orbgpu;
-
-#define CTX_GUARD(ctx)                                                              \
-    if (!(ctx)) {                                                                   \
-        set_error("NULL context", hipSuccess);                                      \
-        return ORB_ERR_ARG;                                                         \
-    }                                                                               \
-    {                                                                               \
-        hipError_t _e = hipSetDevice((ctx)->device);                                \
-        if (_e != hipSuccess) return set_error("hipSetDevice", _e), ORB_ERR_HIP;    \
-    }
 
 extern "C" {
 
@@ -943,19 +963,6 @@ int orb_search_for_triangulation_batch(orb_ctx* h, int check_ori, int only_stere
 
 namespace orbgpu {
 namespace {
-// What is wrong with a Frame grid CSR over nt trains, or NULL: cell_off missing, or cell_idx missing where the grid
-// has slots; then the CSR itself, since the grid kernels read cell_idx[cell_off[..]] for every rectangle column and
-// index the trains by cell_idx, so a malformed one would be an out-of-bounds device read.
-const char* grid_csr_fault(const orb_frame_grid& g, int nt) {
-    if (!g.cell_off || (g.cell_off[kFrameGridCells] && !g.cell_idx)) return "bad arguments";
-    if (g.cell_off[0] != 0) return "grid cell_off[0] != 0";
-    for (int i = 0; i < kFrameGridCells; i++)   // offsets non-decreasing, so every run lies in [0, cell_off[3072])
-        if (g.cell_off[i + 1] < g.cell_off[i]) return "grid cell_off decreases";
-    for (int i = 0, nslots = g.cell_off[kFrameGridCells]; i < nslots; i++)   // the device indexes the trains by these
-        if (g.cell_idx[i] < 0 || g.cell_idx[i] >= nt) return "grid index out of range";
-    return nullptr;
-}
-
 // The window searches' acceptance, replayed in the reference's query order (:440-498): first / second
 // admissible candidate, vMatchedDistance stealing, rotation histogram.
 int window_replay(TopkSession& s, float nnratio, int check_ori, int n1, const orb_keypoint* kps1, int n2,
@@ -1078,54 +1085,89 @@ int match_bird_replay(TopkSession& s, float nnratio, int check_ori, int max_dist
     return ORB_OK;
 }
 
-// A target of the per-query searches as both entry points give it: orb_proj_target's fields, and the resident frame
-// when the trains are one (orb_project_best_frames: nt and kps_t are the frame's count and host keypoints, tdesc,
-// t_uright and the grid's CSR are not read).
-struct ProjView {
-    orb_proj_target T;
-    const orb_frame* F;
-};
-ProjView proj_view(const orb_proj_target& T) { return ProjView{T, nullptr}; }
-ProjView proj_view(const orb_proj_frame_target& R) {
-    const orb_frame* F = R.frame;
-    orb_proj_target T{};
-    T.nq = R.nq;
-    T.q = R.q;
-    T.qdesc = R.qdesc;
-    T.inv_sigma2 = R.inv_sigma2;
-    T.nlevels = R.nlevels;
-    T.best_idx = R.best_idx;
-    T.best_dist = R.best_dist;
-    if (F) {
-        T.nt = F->n;
-        T.kps_t = F->kps.data();
-        T.grid = orb_frame_grid{F->min_x, F->min_y, F->inv_w, F->inv_h, nullptr, nullptr};
+// The per-query validators of the grid searches (nothing malformed may reach the device): each returns what is wrong,
+// or NULL.  Queries [q0, q1) of the projection searches: a finite window with a radius >= 0, and with gate FUSE a
+// finite ur.
+const char* proj_queries_fault(const orb_proj_query* q, int q0, int q1, bool fuse = false) {
+    for (int i = q0; i < q1; i++) {
+        if (!std::isfinite(q[i].u) || !std::isfinite(q[i].v) || !std::isfinite(q[i].r) || q[i].r < 0)
+            return "query window not finite or radius negative";
+        if (fuse && !std::isfinite(q[i].ur)) return "query ur not finite";
     }
-    return ProjView{T, F};
+    return nullptr;
+}
+// SearchByMatchBird's queries: finite centres, and ids >= 0 (match_t keeps the negative values for "untouched" and
+// "culled").
+const char* bird_queries_fault(int nq, const float* q_xy, const int* q_id) {
+    for (int i = 0; i < nq; i++) {
+        if (!std::isfinite(q_xy[2 * i]) || !std::isfinite(q_xy[2 * i + 1])) return "query centre not finite";
+        if (q_id && q_id[i] < 0) return "negative query id";
+    }
+    return nullptr;
+}
+// The scalars the projection searches and SearchByMatchBird check first, ahead of a NULL frame.
+const char* max_dist_fault(int max_dist) {
+    return max_dist < 0 || max_dist > 256 ? "max_dist outside [0, 256]" : nullptr;
+}
+const char* proj_scalars_fault(int mode, int max_dist) {
+    if (mode != ORB_PROJ_BEST && mode != ORB_PROJ_RATIO_SAME_LEVEL) return "unknown mode";
+    return max_dist_fault(max_dist);
+}
+const char* bird_scalars_fault(int max_dist, float r) {
+    if (const char* why = max_dist_fault(max_dist)) return why;
+    return !std::isfinite(r) || r < 0 ? "radius not finite or negative" : nullptr;
+}
+
+// k_projection_topk's lanes per query: a wavefront per query measured 3-4 us per call faster than a query per 16-lane
+// row at 640x480 / 1,000 queries and level with it at 1280x720 / 2,000, so it is the form in use;
+// ORBGPU_PROJ_LANES=16 selects the row form (diagnostic: profiles/time_projection.py times both)
+int proj_lanes() {
+    const char* e = getenv("ORBGPU_PROJ_LANES");
+    return (e && atoi(e) == 16) ? 16 : 64;
+}
+
+// The context of a grid search (after the argument checks, before anything is written): not NULL, the device a
+// resident train side lives on, and that device made current.
+int side_guard(const char* fn, const Ctx* c, const TrainSide& side) {
+    if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
+    if (side.on_other_device(c)) return arg_error(fn, "the frame lives on another device");
+    CTX_GUARD(c);
+    return ORB_OK;
+}
+
+// A target of the per-query searches as both entry points give it: its queries and outputs, and its train side.
+struct ProjView {
+    int nq;
+    const orb_proj_query* q;
+    const uint8_t* qdesc;
+    const float* inv_sigma2;
+    int nlevels;
+    int* best_idx;
+    int* best_dist;
+    TrainSide side;
+};
+ProjView proj_view(const orb_proj_target& T) {
+    return ProjView{T.nq, T.q, T.qdesc, T.inv_sigma2, T.nlevels, T.best_idx, T.best_dist,
+                    TrainSide(T.nt, T.tdesc, T.kps_t, T.t_uright, T.grid)};
+}
+ProjView proj_view(const orb_proj_frame_target& R) {   // (R.frame != NULL; its uright gates as a host target's does)
+    return ProjView{R.nq, R.q, R.qdesc, R.inv_sigma2, R.nlevels, R.best_idx, R.best_dist, TrainSide(R.frame, true)};
 }
 
 // What is wrong with a target of orb_project_best_batch / orb_project_best_frames for its queries [q0, q1), or NULL.
-// The kernel indexes inv_sigma2 by the train's octave and the trains by the grid's cell_idx, so both are checked here
-// (a resident frame's CSR is the library's own).
+// The kernel indexes inv_sigma2 by the train's octave and the trains by the grid's cell_idx, so both are checked here.
 const char* proj_target_fault(int gate, const ProjView& V, int q0, int q1) {
-    const orb_proj_target& T = V.T;
-    if (T.nq < 0 || T.nt < 0) return "negative count";
-    if (T.nq > 0 && (!T.best_idx || !T.best_dist)) return "NULL outputs";
-    if (T.nq > 0 && (!T.q || !T.qdesc)) return "bad arguments";
-    if (!V.F) {
-        if (T.nt > 0 && (!T.tdesc || !T.kps_t)) return "bad arguments";
-        if (const char* why = grid_csr_fault(T.grid, T.nt)) return why;
-    }
-    for (int i = q0; i < q1; i++) {
-        if (!std::isfinite(T.q[i].u) || !std::isfinite(T.q[i].v) || !std::isfinite(T.q[i].r) || T.q[i].r < 0)
-            return "query window not finite or radius negative";
-        if (gate == ORB_PROJ_GATE_FUSE && !std::isfinite(T.q[i].ur)) return "query ur not finite";
-    }
+    const TrainSide& S = V.side;
+    if (V.nq < 0 || S.n < 0) return "negative count";
+    if (V.nq > 0 && (!V.best_idx || !V.best_dist)) return "NULL outputs";
+    if (V.nq > 0 && (!V.q || !V.qdesc)) return "bad arguments";
+    if (const char* why = S.fault()) return why;
+    if (const char* why = proj_queries_fault(V.q, q0, q1, gate == ORB_PROJ_GATE_FUSE)) return why;
     if (gate == ORB_PROJ_GATE_FUSE) {
-        if (!T.inv_sigma2) return "inv_sigma2 NULL";
-        if (T.nlevels < 1 || T.nlevels > ORBGPU_MAX_LEVELS) return "nlevels outside [1, ORBGPU_MAX_LEVELS]";
-        for (int t = 0; t < T.nt; t++)
-            if (T.kps_t[t].octave < 0 || T.kps_t[t].octave >= T.nlevels) return "train octave outside [0, nlevels)";
+        if (!V.inv_sigma2) return "inv_sigma2 NULL";
+        if (V.nlevels < 1 || V.nlevels > ORBGPU_MAX_LEVELS) return "nlevels outside [1, ORBGPU_MAX_LEVELS]";
+        for (int t = 0; t < S.n; t++)
+            if (S.kps[t].octave < 0 || S.kps[t].octave >= V.nlevels) return "train octave outside [0, nlevels)";
     }
     return nullptr;
 }
@@ -1181,6 +1223,68 @@ void proj_best_one(int gate, const orb_proj_target& T, const orb_proj_query& P, 
         *best_dist = bestDist;
     }
 }
+
+// The bodies of the grid searches, one per search for both forms of the train side.  An entry point checks what only
+// its form has (the host arrays and their grid, or the frame) and calls its body under its own name fn; the arguments
+// are checked before the context, so nothing malformed reaches the device and no output is written: k_window_topk and
+// k_projection_topk read cell_idx[cell_off[..]] for every rectangle column.
+
+// orb_window_match_grid / orb_window_match_frame (and orb_search_by_match_bird_frame's matching)
+int window_grid_run(const char* fn, orb_ctx* h, float nnratio, int check_ori, int level0_only, int n1,
+                    const uint8_t* desc1, const orb_keypoint* kps1, const float* centres, float window,
+                    const TrainSide& side, int* match12, int* nmatches_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (const int st = side_guard(fn, c, side)) return st;
+    if (n1 == 0 || side.n == 0) {
+        for (int i = 0; i < n1; i++) match12[i] = -1;
+        if (nmatches_out) *nmatches_out = 0;
+        return ORB_OK;
+    }
+    TopkSession s{c};
+    for (int i1 = 0; i1 < n1; i1++) {
+        if (level0_only && kps1[i1].octave > 0) continue;   // :420-423 (a query without candidates ranks nothing)
+        s.item_q.push_back(i1);
+    }
+    const int st = s.setup_grid(desc1, n1, kps1, centres, window, side);
+    if (st != ORB_OK) return st;
+    return window_replay(s, nnratio, check_ori, n1, kps1, side.n, side.kps, match12, nmatches_out);
+}
+
+// orb_search_by_projection / orb_search_by_projection_frame, after mode and max_dist
+int projection_search_run(const char* fn, orb_ctx* h, int mode, float nnratio, int check_ori, int max_dist, int nq,
+                          const orb_proj_query* q, const uint8_t* qdesc, const TrainSide& side, const uint8_t* t_taken,
+                          int* match_t, int* nmatches_out) {
+    if (const char* why = proj_queries_fault(q, 0, nq)) return arg_error(fn, why);
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (const int st = side_guard(fn, c, side)) return st;
+    for (int t = 0; t < side.n; t++) match_t[t] = -1;
+    if (nmatches_out) *nmatches_out = 0;
+    if (nq == 0 || side.n == 0) return ORB_OK;
+    TopkSession s{c};
+    const int st = s.setup_proj(nq, q, qdesc, side, proj_lanes());
+    if (st != ORB_OK) return st;
+    return proj_replay(s, mode, nnratio, check_ori, max_dist, q, side.kps, t_taken, match_t, nmatches_out);
+}
+
+// orb_search_by_match_bird / orb_search_by_match_bird_resident, after max_dist and r: k_projection_topk over the
+// birdview grid (a wavefront per query, no stereo gate), the acceptance is match_bird_replay
+int match_bird_run(const char* fn, orb_ctx* h, float nnratio, int check_ori, int max_dist, float r, int nq,
+                   const int* q_id, const float* q_xy, const float* q_angle, const uint8_t* qdesc, const TrainSide& side,
+                   int* match_t, int* nmatches_out) {
+    if (const char* why = bird_queries_fault(nq, q_xy, q_id)) return arg_error(fn, why);
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (const int st = side_guard(fn, c, side)) return st;
+    for (int t = 0; t < side.n; t++) match_t[t] = -1;
+    if (nmatches_out) *nmatches_out = 0;
+    if (nq == 0 || side.n == 0) return ORB_OK;
+    std::vector<orb_proj_query> q(nq);
+    for (int i = 0; i < nq; i++)   // GetFeaturesInAreaBirdview(pt.x, pt.y, r): the default levels (:2023)
+        q[i] = orb_proj_query{q_xy[2 * i], q_xy[2 * i + 1], r, -1, -1, 0.0f, 0.0f, 0.0f, 0};
+    TopkSession s{c};
+    const int st = s.setup_proj(nq, q.data(), qdesc, side, 64);
+    if (st != ORB_OK) return st;
+    return match_bird_replay(s, nnratio, check_ori, max_dist, q_id, q_angle, side.kps, match_t, nmatches_out);
+}
 }  // namespace
 }  // namespace orbgpu
 
@@ -1212,22 +1316,12 @@ int orb_window_match_grid(orb_ctx* h, float nnratio, int check_ori, int level0_o
                           const orb_keypoint* kps1, const float* centres, float window, int n2,
                           const uint8_t* desc2, const orb_keypoint* kps2, orb_frame_grid grid2, int* match12,
                           int* nmatches_out) {
-    // the arguments are checked before the context: k_window_topk reads cell_idx[cell_off[..]] for every
-    // rectangle column, so a malformed CSR would be an out-of-bounds device read
     const char* const fn = "orb_window_match_grid";
-    if (n1 < 0 || n2 < 0 || !match12 || (n1 && (!desc1 || !kps1)) || (n2 && (!desc2 || !kps2)))
-        return arg_error(fn, "bad arguments");
-    if (const char* why = grid_csr_fault(grid2, n2)) return arg_error(fn, why);
-    Ctx* c = reinterpret_cast<Ctx*>(h);
-    CTX_GUARD(c);
-    TopkSession s{c};
-    for (int i1 = 0; i1 < n1; i1++) {
-        if (level0_only && kps1[i1].octave > 0) continue;   // :420-423 (a query without candidates ranks nothing)
-        s.item_q.push_back(i1);
-    }
-    const int st = s.setup_grid(desc1, n1, kps1, centres, desc2, n2, kps2, grid2, window);
-    if (st != ORB_OK) return st;
-    return window_replay(s, nnratio, check_ori, n1, kps1, n2, kps2, match12, nmatches_out);
+    if (n1 < 0 || n2 < 0 || !match12 || (n1 && (!desc1 || !kps1))) return arg_error(fn, "bad arguments");
+    const TrainSide side(n2, desc2, kps2, nullptr, grid2);
+    if (const char* why = side.fault()) return arg_error(fn, why);
+    return window_grid_run(fn, h, nnratio, check_ori, level0_only, n1, desc1, kps1, centres, window, side, match12,
+                           nmatches_out);
 }
 
 /* SearchByProjection(Frame&, const Frame&, th, bMono) (:1328-1470), SearchByProjection(Frame&, vector<MapPoint*>, th)
@@ -1236,30 +1330,13 @@ int orb_search_by_projection(orb_ctx* h, int mode, float nnratio, int check_ori,
                              const orb_proj_query* q, const uint8_t* qdesc, int nt, const uint8_t* tdesc,
                              const orb_keypoint* kps_t, const float* t_uright, const uint8_t* t_taken,
                              orb_frame_grid grid, int* match_t, int* nmatches_out) {
-    // as in orb_window_match_grid the arguments are checked before the context: nothing malformed reaches the device
     const char* const fn = "orb_search_by_projection";
-    if (mode != ORB_PROJ_BEST && mode != ORB_PROJ_RATIO_SAME_LEVEL) return arg_error(fn, "unknown mode");
-    if (max_dist < 0 || max_dist > 256) return arg_error(fn, "max_dist outside [0, 256]");
-    if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q || !qdesc)) || (nt && (!tdesc || !kps_t)))
-        return arg_error(fn, "bad arguments");
-    if (const char* why = grid_csr_fault(grid, nt)) return arg_error(fn, why);
-    for (int i = 0; i < nq; i++)
-        if (!std::isfinite(q[i].u) || !std::isfinite(q[i].v) || !std::isfinite(q[i].r) || q[i].r < 0)
-            return arg_error(fn, "query window not finite or radius negative");
-    Ctx* c = reinterpret_cast<Ctx*>(h);
-    CTX_GUARD(c);
-    for (int t = 0; t < nt; t++) match_t[t] = -1;
-    if (nmatches_out) *nmatches_out = 0;
-    if (nq == 0 || nt == 0) return ORB_OK;
-    // lanes per query: a wavefront per query measured 3-4 us per call faster than a query per 16-lane row at
-    // 640x480 / 1,000 queries and level with it at 1280x720 / 2,000, so it is the form in use;
-    // ORBGPU_PROJ_LANES=16 selects the row form (diagnostic: profiles/time_projection.py times both)
-    const char* e = getenv("ORBGPU_PROJ_LANES");
-    const int lanes = (e && atoi(e) == 16) ? 16 : 64;
-    TopkSession s{c};
-    const int st = s.setup_proj(nq, q, qdesc, nt, tdesc, kps_t, t_uright, grid, lanes);
-    if (st != ORB_OK) return st;
-    return proj_replay(s, mode, nnratio, check_ori, max_dist, q, kps_t, t_taken, match_t, nmatches_out);
+    if (const char* why = proj_scalars_fault(mode, max_dist)) return arg_error(fn, why);
+    if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q || !qdesc))) return arg_error(fn, "bad arguments");
+    const TrainSide side(nt, tdesc, kps_t, t_uright, grid);
+    if (const char* why = side.fault()) return arg_error(fn, why);
+    return projection_search_run(fn, h, mode, nnratio, check_ori, max_dist, nq, q, qdesc, side, t_taken, match_t,
+                                 nmatches_out);
 }
 
 /* SearchByMatchBird(KeyFrame*, Frame&, vector<MapPointBird*>&, r) (:2000-2114): the grid walk and the ranking are
@@ -1269,32 +1346,14 @@ int orb_search_by_match_bird(orb_ctx* h, float nnratio, int check_ori, int max_d
                              const float* q_xy, const float* q_angle, const uint8_t* qdesc, int nt,
                              const uint8_t* tdesc, const orb_keypoint* kps_t, orb_frame_grid grid, int* match_t,
                              int* nmatches_out) {
-    // the arguments are checked before the context: nothing malformed reaches the device, no output is written
     const char* const fn = "orb_search_by_match_bird";
-    if (max_dist < 0 || max_dist > 256) return arg_error(fn, "max_dist outside [0, 256]");
-    if (!std::isfinite(r) || r < 0) return arg_error(fn, "radius not finite or negative");
-    if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q_xy || !qdesc || (check_ori && !q_angle))) ||
-        (nt && (!tdesc || !kps_t)))
+    if (const char* why = bird_scalars_fault(max_dist, r)) return arg_error(fn, why);
+    if (nq < 0 || nt < 0 || (nt && !match_t) || (nq && (!q_xy || !qdesc || (check_ori && !q_angle))))
         return arg_error(fn, "bad arguments");
-    if (const char* why = grid_csr_fault(grid, nt)) return arg_error(fn, why);
-    for (int i = 0; i < nq; i++) {
-        if (!std::isfinite(q_xy[2 * i]) || !std::isfinite(q_xy[2 * i + 1]))
-            return arg_error(fn, "query centre not finite");
-        // (match_t keeps the negative values for "untouched" and "culled")
-        if (q_id && q_id[i] < 0) return arg_error(fn, "negative query id");
-    }
-    Ctx* c = reinterpret_cast<Ctx*>(h);
-    CTX_GUARD(c);
-    for (int t = 0; t < nt; t++) match_t[t] = -1;
-    if (nmatches_out) *nmatches_out = 0;
-    if (nq == 0 || nt == 0) return ORB_OK;
-    std::vector<orb_proj_query> q(nq);
-    for (int i = 0; i < nq; i++)   // GetFeaturesInAreaBirdview(pt.x, pt.y, r): the default levels (:2023)
-        q[i] = orb_proj_query{q_xy[2 * i], q_xy[2 * i + 1], r, -1, -1, 0.0f, 0.0f, 0.0f, 0};
-    TopkSession s{c};
-    const int st = s.setup_proj(nq, q.data(), qdesc, nt, tdesc, kps_t, nullptr, grid, 64);
-    if (st != ORB_OK) return st;
-    return match_bird_replay(s, nnratio, check_ori, max_dist, q_id, q_angle, kps_t, match_t, nmatches_out);
+    const TrainSide side(nt, tdesc, kps_t, nullptr, grid);
+    if (const char* why = side.fault()) return arg_error(fn, why);
+    return match_bird_run(fn, h, nnratio, check_ori, max_dist, r, nq, q_id, q_xy, q_angle, qdesc, side, match_t,
+                          nmatches_out);
 }
 
 /* SearchByMatchBird(Frame& CurrentFrame, const Frame& LastFrame, windowSize) (:1901-1921): BirdviewMatch(LastFrame,
@@ -1304,16 +1363,16 @@ int orb_search_by_match_bird_frame(orb_ctx* h, float nnratio, int check_ori, flo
                                    int n_cur, const uint8_t* desc_cur, const orb_keypoint* kps_cur,
                                    orb_frame_grid grid_cur, int* match_cur, int* nmatches_out) {
     const char* const fn = "orb_search_by_match_bird_frame";
-    if (n_last < 0 || n_cur < 0 || (n_cur && !match_cur) || (n_last && (!desc_last || !kps_last)) ||
-        (n_cur && (!desc_cur || !kps_cur)))
+    if (n_last < 0 || n_cur < 0 || (n_cur && !match_cur) || (n_last && (!desc_last || !kps_last)))
         return arg_error(fn, "bad arguments");
-    if (const char* why = grid_csr_fault(grid_cur, n_cur)) return arg_error(fn, why);
+    const TrainSide side(n_cur, desc_cur, kps_cur, nullptr, grid_cur);
+    if (const char* why = side.fault()) return arg_error(fn, why);
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     std::vector<int> vnMatches12((size_t)std::max(n_last, 1), -1);
     if (has_mp_last && n_last > 0 && n_cur > 0) {   // (without map points nothing is carried whatever matches)
-        const int st = orb_window_match_grid(h, nnratio, check_ori, 0, n_last, desc_last, kps_last, nullptr, window,
-                                             n_cur, desc_cur, kps_cur, grid_cur, vnMatches12.data(), nullptr);
+        const int st = window_grid_run(fn, h, nnratio, check_ori, 0, n_last, desc_last, kps_last, nullptr, window, side,
+                                       vnMatches12.data(), nullptr);
         if (st != ORB_OK) return st;
     }
     int nmatches = 0;
@@ -1341,11 +1400,11 @@ int project_best_run(const char* fn, orb_ctx* h, int gate, const std::vector<Pro
     const int ntargets = (int)targets.size();
     size_t nitems = 0, nused = 0;
     for (int k = 0; k < ntargets; k++) {
-        const orb_proj_target& T = targets[k].T;
-        if (const char* why = proj_target_fault(gate, targets[k], 0, T.nq))
+        const ProjView& V = targets[k];
+        if (const char* why = proj_target_fault(gate, V, 0, V.nq))
             return arg_error(fn, "target " + std::to_string(k) + ": " + why);
-        if (T.nq > 0 && T.nt > 0) {
-            nitems += (size_t)T.nq;
+        if (V.nq > 0 && V.side.n > 0) {
+            nitems += (size_t)V.nq;
             nused++;
         }
     }
@@ -1353,38 +1412,32 @@ int project_best_run(const char* fn, orb_ctx* h, int gate, const std::vector<Pro
     Ctx* c = reinterpret_cast<Ctx*>(h);
     if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
     for (int k = 0; k < ntargets; k++)
-        if (targets[k].F && targets[k].F->device != c->device)
+        if (targets[k].side.on_other_device(c))
             return arg_error(fn, "target " + std::to_string(k) + ": the frame lives on another device");
     CTX_GUARD(c);
     for (int k = 0; k < ntargets; k++)
-        for (int i = 0; i < targets[k].T.nq; i++) targets[k].T.best_idx[i] = targets[k].T.best_dist[i] = -1;
+        for (int i = 0; i < targets[k].nq; i++) targets[k].best_idx[i] = targets[k].best_dist[i] = -1;
     if (nitems == 0) return ORB_OK;
     // the staging area: [table | item -> table row | queries | query descriptors | per used target: descriptors,
     // keypoints, uright, inv_sigma2, cell_off, cell_idx (a resident frame: inv_sigma2 only)] in one DMA, then the
     // outputs the kernel writes into the mirror
-    const int ncells = kFrameGridCells;
+    const bool fuse = gate == ORB_PROJ_GATE_FUSE;
     Stage st{c};
     const size_t o_tab = st.add(nused * sizeof(ProjTarget)), o_item = st.add(nitems * 4),
                  o_pq = st.add(nitems * sizeof(orb_proj_query)), o_q = st.add(nitems * 32);
-    struct Offsets {   // (-1: the region is not staged)
-        long long o_t, o_kps, o_ur, o_inv, o_coff, o_cidx;
+    struct Regions {
+        TrainStage train;
+        size_t o_inv;
     };
-    std::vector<Offsets> tab;
+    std::vector<Regions> tab;
     tab.reserve(nused);
     for (int k = 0; k < ntargets; k++) {
-        const orb_proj_target& T = targets[k].T;
-        if (T.nq == 0 || T.nt == 0) continue;
-        Offsets R{-1, -1, -1, -1, -1, -1};
-        if (!targets[k].F) {
-            R.o_t = (long long)st.add((size_t)T.nt * 32);
-            R.o_kps = (long long)st.add((size_t)T.nt * sizeof(orb_keypoint));
-            R.o_ur = gate == ORB_PROJ_GATE_FUSE && T.t_uright ? (long long)st.add((size_t)T.nt * 4) : -1;
-        }
-        R.o_inv = gate == ORB_PROJ_GATE_FUSE ? (long long)st.add((size_t)T.nlevels * 4) : 0;
-        if (!targets[k].F) {
-            R.o_coff = (long long)st.add((size_t)(ncells + 1) * 4);
-            R.o_cidx = (long long)st.add((size_t)T.grid.cell_off[ncells] * 4);
-        }
+        const ProjView& V = targets[k];
+        if (V.nq == 0 || V.side.n == 0) continue;
+        Regions R{TrainStage{V.side, fuse && V.side.has_ur()}, 0};
+        R.train.add_arrays(st, false);
+        if (fuse) R.o_inv = st.add((size_t)V.nlevels * 4);
+        R.train.add_grid(st);
         tab.push_back(R);
     }
     const size_t o_in_end = st.off;
@@ -1393,37 +1446,18 @@ int project_best_run(const char* fn, orb_ctx* h, int gate, const std::vector<Pro
     if (rr != ORB_OK) return rr;
     size_t item = 0, row = 0;
     for (int k = 0; k < ntargets; k++) {
-        const orb_proj_target& T = targets[k].T;
-        const orb_frame* F = targets[k].F;
-        if (T.nq == 0 || T.nt == 0) continue;
-        const Offsets& R = tab[row];
+        const ProjView& V = targets[k];
+        if (V.nq == 0 || V.side.n == 0) continue;
+        const Regions& R = tab[row];
         ProjTarget& D = st.hi<ProjTarget>(o_tab)[row];
-        D.inv_sigma2 = st.di<float>((size_t)R.o_inv);
-        D.g = ProjGrid{T.grid.min_x, T.grid.min_y, T.grid.inv_w, T.grid.inv_h};
-        for (int i = 0; i < T.nq; i++) st.hi<int>(o_item)[item + i] = (int)row;
-        std::memcpy(st.hi<orb_proj_query>(o_pq) + item, T.q, (size_t)T.nq * sizeof(orb_proj_query));
-        std::memcpy(st.hi<uint8_t>(o_q) + item * 32, T.qdesc, (size_t)T.nq * 32);
-        if (gate == ORB_PROJ_GATE_FUSE) std::memcpy(st.hi<uint8_t>(R.o_inv), T.inv_sigma2, (size_t)T.nlevels * 4);
-        if (F) {
-            D.t = F->d_desc;
-            D.kps = F->d_kps;
-            D.ur = gate == ORB_PROJ_GATE_FUSE ? F->d_ur : nullptr;
-            D.cell_off = F->d_coff;
-            D.cell_idx = F->d_cidx;
-        } else {
-            D.t = st.di<uint8_t>((size_t)R.o_t);
-            D.kps = st.di<orb_keypoint>((size_t)R.o_kps);
-            D.ur = R.o_ur >= 0 ? st.di<float>((size_t)R.o_ur) : nullptr;
-            D.cell_off = st.di<int>((size_t)R.o_coff);
-            D.cell_idx = st.di<int>((size_t)R.o_cidx);
-            std::memcpy(st.hi<uint8_t>(R.o_t), T.tdesc, (size_t)T.nt * 32);
-            std::memcpy(st.hi<uint8_t>(R.o_kps), T.kps_t, (size_t)T.nt * sizeof(orb_keypoint));
-            if (R.o_ur >= 0) std::memcpy(st.hi<uint8_t>(R.o_ur), T.t_uright, (size_t)T.nt * 4);
-            std::memcpy(st.hi<uint8_t>(R.o_coff), T.grid.cell_off, (size_t)(ncells + 1) * 4);
-            if (T.grid.cell_off[ncells])
-                std::memcpy(st.hi<uint8_t>(R.o_cidx), T.grid.cell_idx, (size_t)T.grid.cell_off[ncells] * 4);
-        }
-        item += (size_t)T.nq;
+        D = R.train.row(st);
+        D.inv_sigma2 = st.di<float>(R.o_inv);
+        for (int i = 0; i < V.nq; i++) st.hi<int>(o_item)[item + i] = (int)row;
+        std::memcpy(st.hi<orb_proj_query>(o_pq) + item, V.q, (size_t)V.nq * sizeof(orb_proj_query));
+        std::memcpy(st.hi<uint8_t>(o_q) + item * 32, V.qdesc, (size_t)V.nq * 32);
+        if (fuse) st.put(R.o_inv, V.inv_sigma2, (size_t)V.nlevels * 4);
+        R.train.put(st);
+        item += (size_t)V.nq;
         row++;
     }
     hipError_t e;
@@ -1437,11 +1471,11 @@ int project_best_run(const char* fn, orb_ctx* h, int gate, const std::vector<Pro
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("download", e), ORB_ERR_HIP;
     item = 0;
     for (int k = 0; k < ntargets; k++) {
-        const orb_proj_target& T = targets[k].T;
-        if (T.nq == 0 || T.nt == 0) continue;
-        std::memcpy(T.best_idx, st.h<int>(o_idx) + item, (size_t)T.nq * 4);
-        std::memcpy(T.best_dist, st.h<int>(o_dist) + item, (size_t)T.nq * 4);
-        item += (size_t)T.nq;
+        const ProjView& V = targets[k];
+        if (V.nq == 0 || V.side.n == 0) continue;
+        std::memcpy(V.best_idx, st.h<int>(o_idx) + item, (size_t)V.nq * 4);
+        std::memcpy(V.best_dist, st.h<int>(o_dist) + item, (size_t)V.nq * 4);
+        item += (size_t)V.nq;
     }
     return ORB_OK;
 }
@@ -1476,37 +1510,18 @@ int orb_project_best_frames(orb_ctx* h, int gate, int ntargets, const orb_proj_f
     return project_best_run(fn, h, gate, v);
 }
 
-/* The grid searches with the train side as a resident frame (orbgpu.h): the counterpart's checks, then the same
- * session with the handle's device pointers and the same replay over the handle's host keypoints. */
-#define FRAME_GUARD(fn, c, F)                                                                        \
-    if (!(c)) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;                             \
-    if ((F)->device != (c)->device) return arg_error(fn, "the frame lives on another device");       \
-    CTX_GUARD(c)
-
+/* The grid searches with the train side as a resident frame (orbgpu.h): the frame's own checks, then the body the
+ * host-pointer form runs, with the handle's device pointers and its host keypoints. */
 int orb_search_by_projection_frame(orb_ctx* h, int mode, float nnratio, int check_ori, int max_dist, int nq,
                                    const orb_proj_query* q, const uint8_t* qdesc, const orb_frame* F,
                                    const uint8_t* t_taken, int use_uright, int* match_t, int* nmatches_out) {
     const char* const fn = "orb_search_by_projection_frame";
-    if (mode != ORB_PROJ_BEST && mode != ORB_PROJ_RATIO_SAME_LEVEL) return arg_error(fn, "unknown mode");
-    if (max_dist < 0 || max_dist > 256) return arg_error(fn, "max_dist outside [0, 256]");
+    if (const char* why = proj_scalars_fault(mode, max_dist)) return arg_error(fn, why);
     if (!F) return arg_error(fn, "NULL frame");
-    const int nt = F->n;
-    if (nq < 0 || (nt && !match_t) || (nq && (!q || !qdesc))) return arg_error(fn, "bad arguments");
+    if (nq < 0 || (F->n && !match_t) || (nq && (!q || !qdesc))) return arg_error(fn, "bad arguments");
     if (use_uright && !F->has_ur) return arg_error(fn, "use_uright with a frame created without uright");
-    for (int i = 0; i < nq; i++)
-        if (!std::isfinite(q[i].u) || !std::isfinite(q[i].v) || !std::isfinite(q[i].r) || q[i].r < 0)
-            return arg_error(fn, "query window not finite or radius negative");
-    Ctx* c = reinterpret_cast<Ctx*>(h);
-    FRAME_GUARD(fn, c, F);
-    for (int t = 0; t < nt; t++) match_t[t] = -1;
-    if (nmatches_out) *nmatches_out = 0;
-    if (nq == 0 || nt == 0) return ORB_OK;
-    const char* e = getenv("ORBGPU_PROJ_LANES");   // (as orb_search_by_projection)
-    const int lanes = (e && atoi(e) == 16) ? 16 : 64;
-    TopkSession s{c};
-    const int st = s.setup_proj(nq, q, qdesc, F, use_uright != 0, lanes);
-    if (st != ORB_OK) return st;
-    return proj_replay(s, mode, nnratio, check_ori, max_dist, q, F->kps.data(), t_taken, match_t, nmatches_out);
+    return projection_search_run(fn, h, mode, nnratio, check_ori, max_dist, nq, q, qdesc,
+                                 TrainSide(F, use_uright != 0), t_taken, match_t, nmatches_out);
 }
 
 int orb_window_match_frame(orb_ctx* h, float nnratio, int check_ori, int level0_only, int n1, const uint8_t* desc1,
@@ -1515,51 +1530,20 @@ int orb_window_match_frame(orb_ctx* h, float nnratio, int check_ori, int level0_
     const char* const fn = "orb_window_match_frame";
     if (!F2) return arg_error(fn, "NULL frame");
     if (n1 < 0 || !match12 || (n1 && (!desc1 || !kps1))) return arg_error(fn, "bad arguments");
-    Ctx* c = reinterpret_cast<Ctx*>(h);
-    FRAME_GUARD(fn, c, F2);
-    if (n1 == 0 || F2->n == 0) {
-        for (int i = 0; i < n1; i++) match12[i] = -1;
-        if (nmatches_out) *nmatches_out = 0;
-        return ORB_OK;
-    }
-    TopkSession s{c};
-    for (int i1 = 0; i1 < n1; i1++) {
-        if (level0_only && kps1[i1].octave > 0) continue;   // :420-423
-        s.item_q.push_back(i1);
-    }
-    const orb_frame_grid g{F2->min_x, F2->min_y, F2->inv_w, F2->inv_h, nullptr, nullptr};
-    const int st = s.setup_grid(desc1, n1, kps1, centres, nullptr, F2->n, nullptr, g, window, F2);
-    if (st != ORB_OK) return st;
-    return window_replay(s, nnratio, check_ori, n1, kps1, F2->n, F2->kps.data(), match12, nmatches_out);
+    return window_grid_run(fn, h, nnratio, check_ori, level0_only, n1, desc1, kps1, centres, window,
+                           TrainSide(F2, false), match12, nmatches_out);
 }
 
 int orb_search_by_match_bird_resident(orb_ctx* h, float nnratio, int check_ori, int max_dist, float r, int nq,
                                       const int* q_id, const float* q_xy, const float* q_angle, const uint8_t* qdesc,
                                       const orb_frame* F, int* match_t, int* nmatches_out) {
     const char* const fn = "orb_search_by_match_bird_resident";
-    if (max_dist < 0 || max_dist > 256) return arg_error(fn, "max_dist outside [0, 256]");
-    if (!std::isfinite(r) || r < 0) return arg_error(fn, "radius not finite or negative");
+    if (const char* why = bird_scalars_fault(max_dist, r)) return arg_error(fn, why);
     if (!F) return arg_error(fn, "NULL frame");
-    const int nt = F->n;
-    if (nq < 0 || (nt && !match_t) || (nq && (!q_xy || !qdesc || (check_ori && !q_angle))))
+    if (nq < 0 || (F->n && !match_t) || (nq && (!q_xy || !qdesc || (check_ori && !q_angle))))
         return arg_error(fn, "bad arguments");
-    for (int i = 0; i < nq; i++) {
-        if (!std::isfinite(q_xy[2 * i]) || !std::isfinite(q_xy[2 * i + 1]))
-            return arg_error(fn, "query centre not finite");
-        if (q_id && q_id[i] < 0) return arg_error(fn, "negative query id");
-    }
-    Ctx* c = reinterpret_cast<Ctx*>(h);
-    FRAME_GUARD(fn, c, F);
-    for (int t = 0; t < nt; t++) match_t[t] = -1;
-    if (nmatches_out) *nmatches_out = 0;
-    if (nq == 0 || nt == 0) return ORB_OK;
-    std::vector<orb_proj_query> q(nq);
-    for (int i = 0; i < nq; i++)   // GetFeaturesInAreaBirdview(pt.x, pt.y, r): the default levels (:2023)
-        q[i] = orb_proj_query{q_xy[2 * i], q_xy[2 * i + 1], r, -1, -1, 0.0f, 0.0f, 0.0f, 0};
-    TopkSession s{c};
-    const int st = s.setup_proj(nq, q.data(), qdesc, F, false, 64);
-    if (st != ORB_OK) return st;
-    return match_bird_replay(s, nnratio, check_ori, max_dist, q_id, q_angle, F->kps.data(), match_t, nmatches_out);
+    return match_bird_run(fn, h, nnratio, check_ori, max_dist, r, nq, q_id, q_xy, q_angle, qdesc, TrainSide(F, false),
+                          match_t, nmatches_out);
 }
 
 int orb_project_best_host(int gate, const orb_proj_target* target, int query, int* best_idx, int* best_dist) {

@@ -553,16 +553,6 @@ int Ctx::run_extract(const uint8_t* d_frames, int nframes, long long frame_pitch
 
 using namespace orbgpu;
 
-#define CTX_GUARD(ctx)                                                              \
-    if (!(ctx)) {                                                                   \
-        set_error("NULL context", hipSuccess);                                      \
-        return ORB_ERR_ARG;                                                         \
-    }                                                                               \
-    {                                                                               \
-        hipError_t _e = hipSetDevice((ctx)->device);                                \
-        if (_e != hipSuccess) return set_error("hipSetDevice", _e), ORB_ERR_HIP;    \
-    }
-
 extern "C" {
 
 int orb_abi_version(void) { return ORBGPU_ABI_VERSION; }

@@ -12,6 +12,19 @@ namespace orbgpu {
 
 void set_error(const char* what, hipError_t e);
 
+// A refused argument: the message "<fn>: <why>" for orb_last_error(), and the status.
+inline int arg_error(const char* fn, const std::string& why) {
+    return set_error((std::string(fn) + ": " + why).c_str(), hipSuccess), ORB_ERR_ARG;
+}
+
+// An entry point's first use of its context: NULL is refused, the context's device made current.
+#define CTX_GUARD(ctx)                                                                    \
+    if (!(ctx)) return orbgpu::set_error("NULL context", hipSuccess), ORB_ERR_ARG;        \
+    {                                                                                     \
+        hipError_t _e = hipSetDevice((ctx)->device);                                      \
+        if (_e != hipSuccess) return orbgpu::set_error("hipSetDevice", _e), ORB_ERR_HIP;  \
+    }
+
 struct ProfPair {
     int id;
     hipEvent_t b, e;
@@ -245,6 +258,9 @@ struct Stage {
     template <class T>
     T* di(size_t o) const {   // inputs, as the kernels read them
         return zc ? reinterpret_cast<T*>(c->h_mstage + o) : d<T>(o);
+    }
+    void put(size_t o, const void* src, size_t bytes) const {   // an input region's content (nothing: src may be NULL)
+        if (bytes) std::memcpy(hi<uint8_t>(o), src, bytes);
     }
     hipError_t up(size_t from, size_t to) const {
         if (zc) return hipSuccess;   // the kernels read the pinned mirror itself

@@ -333,16 +333,6 @@ hipError_t launch_stereo(const Geom* d_geom, const Geom& g, const StereoSide& L,
 
 using namespace orbgpu;
 
-#define CTX_GUARD(ctx)                                                              \
-    if (!(ctx)) {                                                                   \
-        set_error("NULL context", hipSuccess);                                      \
-        return ORB_ERR_ARG;                                                         \
-    }                                                                               \
-    {                                                                               \
-        hipError_t _e = hipSetDevice((ctx)->device);                                \
-        if (_e != hipSuccess) return set_error("hipSetDevice", _e), ORB_ERR_HIP;    \
-    }
-
 static bool same_geometry(const Ctx* a, const Ctx* b) {
     if (!a->have_geom || !b->have_geom) return false;
     const Geom &x = a->geom, &y = b->geom;

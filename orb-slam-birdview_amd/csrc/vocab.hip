@@ -78,16 +78,6 @@ __global__ __launch_bounds__(256) void k_vocab_transform(const int* __restrict__
 
 using namespace orbgpu;
 
-#define CTX_GUARD(ctx)                                                              \
-    if (!(ctx)) {                                                                   \
-        set_error("NULL context", hipSuccess);                                      \
-        return ORB_ERR_ARG;                                                         \
-    }                                                                               \
-    {                                                                               \
-        hipError_t _e = hipSetDevice((ctx)->device);                                \
-        if (_e != hipSuccess) return set_error("hipSetDevice", _e), ORB_ERR_HIP;    \
-    }
-
 static void vocab_free(orb_vocab* v) {
     if (!v) return;
     (void)hipSetDevice(v->device);
