@@ -2348,71 +2348,83 @@ __device__ __forceinline__ void brief_sampled(const uint16_t* rt, float a, float
     if (lane < 4) dst[lane] = lane == 0 ? mq[0] : lane == 1 ? mq[1] : lane == 2 ? mq[2] : mq[3];
 }
 
-template <bool FMA, int CP = 0>
-__device__ __forceinline__ void desc_body(const Geom* __restrict__ g, const DescSlot& d, int f, int lane,
-                                          const uint32_t (&v)[9], uint8_t* wbase, uint16_t* rt,
-                                          orb_keypoint* __restrict__ outK, uint8_t* __restrict__ outD, int kpCap,
-                                          unsigned long long* __restrict__ dstamps) {
-    const int l = d.l, x = d.x, y = d.y, score = d.score, outIdx = d.outIdx;
-    const LevelGeom& L = g->L[l];
-    const LevelPtr src = d.src;
-    [[maybe_unused]] unsigned long long* dst_st = dstamps ? dstamps + ((long long)f * g->nkpcap + d.s) * 8 : nullptr;
+// ---- k_describe's work on one keypoint, in phases (desc_single and desc_pair below compose them) ----
+
+// kernel phase timestamp k of a slot (make STAMPS=1, tools/describe_stamps.py)
+__device__ __forceinline__ void desc_stamp([[maybe_unused]] unsigned long long* st, [[maybe_unused]] int lane,
+                                           [[maybe_unused]] int k) {
 #if ORBGPU_KERNEL_STAMPS
-#define DESC_STAMP(k) \
-    if (dst_st && lane == 0) dst_st[(k)] = __builtin_amdgcn_s_memtime();
-#else
-#define DESC_STAMP(k)
+    if (st && lane == 0) st[k] = __builtin_amdgcn_s_memtime();
 #endif
-    DESC_STAMP(0);
-    // the lane's IC_Angle byte masks (constant table), issued before the window is stored
+}
+
+// the lane's IC_Angle byte masks (constant table)
+__device__ __forceinline__ void desc_ic_masks(int lane, uint32_t (&icm)[4]) {
     const uint4 mm = reinterpret_cast<const uint4*>(&c_ic_masks.m[0][0])[lane];
-    const uint32_t icm[4] = {mm.x, mm.y, mm.z, mm.w};
-    uint32_t* w32 = reinterpret_cast<uint32_t*>(wbase);
-    int sh;
-    if (d.interior) {
+    icm[0] = mm.x;
+    icm[1] = mm.y;
+    icm[2] = mm.z;
+    icm[3] = mm.w;
+}
+
+// Window store, interior form: desc_issue's nine register dwords into the 43 x 48 LDS form at w32.  Returns the
+// window's byte shift sh (the loads start at a 4-byte aligned column).
+__device__ __forceinline__ int desc_store_regs(const DescSlot& d, int lane, const uint32_t (&v)[9], uint32_t* w32) {
 #pragma unroll
-        for (int r = 0; r < 9; r++)   // window dword (wy0 + 5r) * 12 + ww = lane + 60 r; rows < 43 only
-            if (r < 8 || lane < 36) w32[lane + 60 * r] = v[r];
-        sh = (x - 21) & 3;
-    } else {
-               // flight in two batches of 15 (fewer live registers than one batch of 29)
+    for (int r = 0; r < 9; r++)   // window dword (wy0 + 5r) * 12 + ww = lane + 60 r; rows < 43 only
+        if (r < 8 || lane < 36) w32[lane + 60 * r] = v[r];
+    return (d.x - 21) & 3;
+}
+
+// Window store, border form: the REFLECT_101 gather, byte by byte (sh = 0)
+template <int CP>
+__device__ __forceinline__ int desc_store_gather(const Geom* __restrict__ g, const DescSlot& d, int lane, uint8_t* wbase) {
+    const int x = d.x, y = d.y;
+    const LevelGeom& L = g->L[d.l];
+    const LevelPtr src = d.src;
+    // flight in two batches of 15 (fewer live registers than one batch of 29)
 #pragma unroll
-        for (int hb = 0; hb < 2; hb++) {
-            uint8_t v[15];
+    for (int hb = 0; hb < 2; hb++) {
+        uint8_t v[15];
 #pragma unroll
-            for (int r = 0; r < 15; r++) {   // 43*43 = 1849 <= 30 x 64
-                const int idx = lane + 64 * (15 * hb + r);
-                const int wy = (int)(__umul24((unsigned)idx, 24386u) >> 20), wx = idx - wy * kDescWin;   // idx / 43
-                int sy = y - 21 + wy, sx = x - 21 + wx;
-                sy = sy < 0 ? -sy : (sy >= L.h ? 2 * L.h - 2 - sy : sy);
-                sx = sx < 0 ? -sx : (sx >= L.w ? 2 * L.w - 2 - sx : sx);
-                if constexpr (CP != 0) {   // a border window of a pyramid level: sc1 byte loads
-                    const auto brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src.p), 0, 0x7FFFFFFF, 0x00020000);
-                    v[r] = idx < kDescWin * kDescWin ? __builtin_amdgcn_raw_buffer_load_b8(brs, (int)roi_off(sy, src.stride, sx), 0, CP)
-                                                     : (uint8_t)0;
-                } else {
-                    v[r] = idx < kDescWin * kDescWin ? src.p[roi_off(sy, src.stride, sx)] : (uint8_t)0;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 15; r++) {
-                const int idx = lane + 64 * (15 * hb + r);
-                const int wy = (int)(__umul24((unsigned)idx, 24386u) >> 20), wx = idx - wy * kDescWin;
-                if (idx < kDescWin * kDescWin) wbase[wy * kDescWinPitch + wx] = v[r];
+        for (int r = 0; r < 15; r++) {   // 43*43 = 1849 <= 30 x 64
+            const int idx = lane + 64 * (15 * hb + r);
+            const int wy = (int)(__umul24((unsigned)idx, 24386u) >> 20), wx = idx - wy * kDescWin;   // idx / 43
+            int sy = y - 21 + wy, sx = x - 21 + wx;
+            sy = sy < 0 ? -sy : (sy >= L.h ? 2 * L.h - 2 - sy : sy);
+            sx = sx < 0 ? -sx : (sx >= L.w ? 2 * L.w - 2 - sx : sx);
+            if constexpr (CP != 0) {   // a border window of a pyramid level: sc1 byte loads
+                const auto brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src.p), 0, 0x7FFFFFFF, 0x00020000);
+                v[r] = idx < kDescWin * kDescWin ? __builtin_amdgcn_raw_buffer_load_b8(brs, (int)roi_off(sy, src.stride, sx), 0, CP)
+                                                 : (uint8_t)0;
+            } else {
+                v[r] = idx < kDescWin * kDescWin ? src.p[roi_off(sy, src.stride, sx)] : (uint8_t)0;
             }
         }
-        sh = 0;
+#pragma unroll
+        for (int r = 0; r < 15; r++) {
+            const int idx = lane + 64 * (15 * hb + r);
+            const int wy = (int)(__umul24((unsigned)idx, 24386u) >> 20), wx = idx - wy * kDescWin;
+            if (idx < kDescWin * kDescWin) wbase[wy * kDescWinPitch + wx] = v[r];
+        }
     }
-    wave_lds_sync();
-    DESC_STAMP(1);
-#if defined(ORBGPU_DESC_CUT) && ORBGPU_DESC_CUT == 1   // instruction-count diagnostics only (tools/diag_cut.sh)
-    if (lane == 0) outD[((long long)f * kpCap + outIdx) * 32] = wbase[lane];
-    return;
-#endif
+    return 0;
+}
 
-    // ---- IC_Angle (:77-104) on the unblurred window: lanes 2r, 2r+1 (r < 31) sum halves of row v = r - 15
-    // over the circular patch |u| <= umax[|v|] with v_dot4_u32_u8 (u*I = (u+16)*I - 16*I); two lanes per
-    // row halve the wave's instructions
+template <int CP>
+__device__ __forceinline__ int desc_store_window(const Geom* __restrict__ g, const DescSlot& d, int lane,
+                                                 const uint32_t (&v)[9], uint8_t* wbase) {
+    if (d.interior) return desc_store_regs(d, lane, v, reinterpret_cast<uint32_t*>(wbase));
+    return desc_store_gather<CP>(g, d, lane, wbase);
+}
+
+// IC_Angle's moments (:77-104) of the unblurred window at w32 (byte shift sh): lanes 2r, 2r+1 (r < 31) sum halves
+// of row v = r - 15 over the circular patch |u| <= umax[|v|] with v_dot4_u32_u8 (u*I = (u+16)*I - 16*I); two
+// lanes per row halve the wave's instructions.  The sums are wave-uniform (SGPRs).
+struct IcMoments {
+    int m01, m10;
+};
+__device__ __forceinline__ IcMoments desc_ic_moments(const uint32_t* w32, int sh, int lane, const uint32_t (&icm)[4]) {
     int m10 = 0, m01 = 0;
     if (lane < 62) {
         const int v = (lane >> 1) - 15, h = lane & 1;
@@ -2433,76 +2445,74 @@ __device__ __forceinline__ void desc_body(const Geom* __restrict__ g, const Desc
         m10 = (int)sW - 16 * (int)sI;
         m01 = v * (int)sI;
     }
-    m10 = wave_sum(m10);   // DPP reductions: no LDS round trips
-    m01 = wave_sum(m01);
-    const float angle = fast_atan2((float)m01, (float)m10);
-    DESC_STAMP(2);
-#if defined(ORBGPU_DESC_CUT) && ORBGPU_DESC_CUT == 2
-    if (lane == 0) outD[((long long)f * kpCap + outIdx) * 32] = (uint8_t)angle;
-    return;
-#endif
+    IcMoments m;
+    m.m10 = wave_sum(m10);   // DPP reductions: no LDS round trips
+    m.m01 = wave_sum(m01);
+    return m;
+}
 
-    // ---- GaussianBlur 7x7 sigma 2 (:1085-1086), exact integer row pass on the matrix cores: RT[c][y] =
-    // sum_t k_t * window[y][sh + c + t] is D = W T with W the window (43 x 64 bytes: row y's 48 loaded bytes,
-    // the rest of the K range meets zero taps) and T the banded tap matrix (Geom::desc_taps, per sh).  Nine
-    // v_mfma_i32_16x16x64_i8 (y and c in tiles of 16); the window bytes are signed by ^ 0x80 (i8 operands)
-    // and the accumulator starts at 128 * sum(k) = 128 * 257, which restores the unsigned sums exactly
-    // (every sum < 2^16).  Lane l holds W[y = 16 ty + (l & 15)][16 (l >> 4) .. + 15] (one 16-byte LDS read)
-    // and, of D, column c = 16 tc + (l & 15) at rows 4 (l >> 4) .. + 3: four u16 of RT's column c, one
-    // 8-byte store (kRtPitch even).
-    {
-        typedef int v4i_t __attribute__((ext_vector_type(4)));
-        const int4* tp = g->desc_taps + sh * kDescTapTiles * 64 + lane;
-        v4i_t bt[kDescTapTiles];
+// Orientation trig: the keypoint's angle (:104, degrees) and the BRIEF rotation a = cos, b = sin of it as glibc's
+// cosf/sinf compute them (:113, glibc_trig.h).  desc_single runs the two halves where they always ran (the
+// angle before the row pass, the rotation after it); desc_pair runs desc_trig once for two keypoints.
+__device__ __forceinline__ float desc_trig_angle(float m01, float m10) { return fast_atan2(m01, m10); }
+__device__ __forceinline__ void desc_trig_rotation(float angle, float* a, float* b) {
+    glibc_sincosf(angle * kFactorPI, b, a);
+}
+struct DescTrig {
+    float angle, a, b;
+};
+__device__ __forceinline__ DescTrig desc_trig(float m01, float m10) {
+    DescTrig t;
+    t.angle = desc_trig_angle(m01, m10);
+    desc_trig_rotation(t.angle, &t.a, &t.b);
+    return t;
+}
+
+// GaussianBlur 7x7 sigma 2 (:1085-1086), exact integer row pass on the matrix cores: RT[c][y] =
+// sum_t k_t * window[y][sh + c + t] is D = W T with W the window (43 x 64 bytes: row y's 48 loaded bytes,
+// the rest of the K range meets zero taps) and T the banded tap matrix (Geom::desc_taps, per sh).  Nine
+// v_mfma_i32_16x16x64_i8 (y and c in tiles of 16); the window bytes are signed by ^ 0x80 (i8 operands)
+// and the accumulator starts at 128 * sum(k) = 128 * 257, which restores the unsigned sums exactly
+// (every sum < 2^16).  Lane l holds W[y = 16 ty + (l & 15)][16 (l >> 4) .. + 15] (one 16-byte LDS read)
+// and, of D, column c = 16 tc + (l & 15) at rows 4 (l >> 4) .. + 3: four u16 of RT's column c, one
+// 8-byte store (kRtPitch even).
+__device__ __forceinline__ void desc_row_pass(const Geom* __restrict__ g, int sh, int lane, const uint8_t* wbase,
+                                              uint16_t* rt) {
+    typedef int v4i_t __attribute__((ext_vector_type(4)));
+    const int4* tp = g->desc_taps + sh * kDescTapTiles * 64 + lane;
+    v4i_t bt[kDescTapTiles];
+#pragma unroll
+    for (int tc = 0; tc < kDescTapTiles; tc++) {
+        const int4 q = tp[tc * 64];
+        bt[tc] = v4i_t{q.x, q.y, q.z, q.w};
+    }
+    const int yl = lane & 15, kq = lane >> 4;
+    const int bias = 128 * (g->gk[0] + g->gk[1] + g->gk[2] + g->gk[3] + g->gk[4] + g->gk[5] + g->gk[6]);
+#pragma unroll
+    for (int ty = 0; ty < 3; ty++) {
+        const int y = min(16 * ty + yl, kDescWin - 1);   // rows 43..47 repeat row 42 (not stored)
+        const uint4 w = *reinterpret_cast<const uint4*>(wbase + y * kDescWinPitch + 16 * kq);
+        const v4i_t a = v4i_t{(int)(w.x ^ 0x80808080u), (int)(w.y ^ 0x80808080u), (int)(w.z ^ 0x80808080u),
+                              (int)(w.w ^ 0x80808080u)};
+        const int y0 = 16 * ty + 4 * kq;   // this lane's first D row
 #pragma unroll
         for (int tc = 0; tc < kDescTapTiles; tc++) {
-            const int4 q = tp[tc * 64];
-            bt[tc] = v4i_t{q.x, q.y, q.z, q.w};
-        }
-        const int yl = lane & 15, kq = lane >> 4;
-        const int bias = 128 * (g->gk[0] + g->gk[1] + g->gk[2] + g->gk[3] + g->gk[4] + g->gk[5] + g->gk[6]);
-#pragma unroll
-        for (int ty = 0; ty < 3; ty++) {
-            const int y = min(16 * ty + yl, kDescWin - 1);   // rows 43..47 repeat row 42 (not stored)
-            const uint4 w = *reinterpret_cast<const uint4*>(wbase + y * kDescWinPitch + 16 * kq);
-            const v4i_t a = v4i_t{(int)(w.x ^ 0x80808080u), (int)(w.y ^ 0x80808080u), (int)(w.z ^ 0x80808080u),
-                                  (int)(w.w ^ 0x80808080u)};
-            const int y0 = 16 * ty + 4 * kq;   // this lane's first D row
-#pragma unroll
-            for (int tc = 0; tc < kDescTapTiles; tc++) {
-                v4i_t d = v4i_t{bias, bias, bias, bias};
-                d = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bt[tc], d, 0, 0, 0);
-                const int c = 16 * tc + yl;
-                if (y0 < kDescWin && c < kDescRtCols) {   // (row 43 of the last group lands in the column's pad)
-                    uint2 pk;   // the low halves of two results per dword: one v_perm each
-                    pk.x = __builtin_amdgcn_perm((uint32_t)d[1], (uint32_t)d[0], 0x05040100u);
-                    pk.y = __builtin_amdgcn_perm((uint32_t)d[3], (uint32_t)d[2], 0x05040100u);
-                    *reinterpret_cast<uint2*>(rt + c * kRtPitch + y0) = pk;
-                }
+            v4i_t d = v4i_t{bias, bias, bias, bias};
+            d = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bt[tc], d, 0, 0, 0);
+            const int c = 16 * tc + yl;
+            if (y0 < kDescWin && c < kDescRtCols) {   // (row 43 of the last group lands in the column's pad)
+                uint2 pk;   // the low halves of two results per dword: one v_perm each
+                pk.x = __builtin_amdgcn_perm((uint32_t)d[1], (uint32_t)d[0], 0x05040100u);
+                pk.y = __builtin_amdgcn_perm((uint32_t)d[3], (uint32_t)d[2], 0x05040100u);
+                *reinterpret_cast<uint2*>(rt + c * kRtPitch + y0) = pk;
             }
         }
     }
-    wave_lds_sync();
-    DESC_STAMP(3);
-#if defined(ORBGPU_DESC_CUT) && ORBGPU_DESC_CUT == 3
-    if (lane == 0) outD[((long long)f * kpCap + outIdx) * 32] = (uint8_t)(angle + rt[lane]);
-    return;
-#endif
+}
 
-    // ---- column pass: evaluated only at the 512 BRIEF sample pixels (brief_sampled), v_dot2_u32_u16 on
-    // row pairs of RT; rounding as the pinned OpenCV 3.2 8U path: half-to-even where the SSE2 body runs
-    // (x < W & ~3), half-up in the scalar tail; ORB_VARIANT_BLUR_HALFUP: half-up everywhere (no SSE2 body).
-    const int xsimd = (g->variant & ORB_VARIANT_BLUR_HALFUP) ? 0 : (L.w & ~3);
-    const int k0 = g->gk[0], k1 = g->gk[1], k2 = g->gk[2], k3 = g->gk[3], k4 = g->gk[4], k5 = g->gk[5],
-              k6 = g->gk[6];
-    const ushort2_t K01 = {(unsigned short)k0, (unsigned short)k1}, K23 = {(unsigned short)k2, (unsigned short)k3},
-                    K45 = {(unsigned short)k4, (unsigned short)k5}, K60 = {(unsigned short)k6, 0};
-    DESC_STAMP(4);
-
-    // BRIEF test pairs of this lane (lane + 64 gq) from the constant table, issued before the trig so their
-    // latency hides under it; loaded here rather than once per wave to keep them out of the row pass's
-    // live registers
-    float pf[4][4];
+// BRIEF test pairs of this lane (lane + 64 gq) from the constant table; loaded per keypoint rather than once per
+// wave to keep them out of the row pass's live registers
+__device__ __forceinline__ void desc_pattern(int lane, float (&pf)[4][4]) {
 #pragma unroll
     for (int gq = 0; gq < 4; gq++) {
         const float4 pp = reinterpret_cast<const float4*>(c_pattern_f)[lane + 64 * gq];
@@ -2511,15 +2521,39 @@ __device__ __forceinline__ void desc_body(const Geom* __restrict__ g, const Desc
         pf[gq][2] = pp.z;
         pf[gq][3] = pp.w;
     }
-    // ---- rBRIEF (:108-147): cos/sin as glibc's cosf/sinf compute them (:113, glibc_trig.h); 256 tests
-    // as four 64-lane ballots; sample (ix, iy) of the blurred patch at blurT[(18+ix)*40 + 18+iy]
-    const float ang = angle * kFactorPI;
-    float a, b;
-    glibc_sincosf(ang, &b, &a);
-    DESC_STAMP(5);
-    unsigned long long* dst = reinterpret_cast<unsigned long long*>(outD + ((long long)f * kpCap + outIdx) * 32);
-    if (x + 18 < xsimd) brief_sampled<true, FMA>(rt, a, b, pf, x - 18, xsimd, K01, K23, K45, K60, lane, dst);
-    else brief_sampled<false, FMA>(rt, a, b, pf, x - 18, xsimd, K01, K23, K45, K60, lane, dst);
+}
+
+// The column pass's constants: evaluated only at the 512 BRIEF sample pixels (brief_sampled), v_dot2_u32_u16 on
+// row pairs of RT; rounding as the pinned OpenCV 3.2 8U path: half-to-even where the SSE2 body runs
+// (x < W & ~3), half-up in the scalar tail; ORB_VARIANT_BLUR_HALFUP: half-up everywhere (no SSE2 body).
+struct DescBlurK {
+    int xsimd;
+    ushort2_t K01, K23, K45, K60;
+};
+__device__ __forceinline__ DescBlurK desc_blur_k(const Geom* __restrict__ g, const DescSlot& d) {
+    DescBlurK k;
+    k.xsimd = (g->variant & ORB_VARIANT_BLUR_HALFUP) ? 0 : (g->L[d.l].w & ~3);
+    const int k0 = g->gk[0], k1 = g->gk[1], k2 = g->gk[2], k3 = g->gk[3], k4 = g->gk[4], k5 = g->gk[5],
+              k6 = g->gk[6];
+    k.K01 = ushort2_t{(unsigned short)k0, (unsigned short)k1};
+    k.K23 = ushort2_t{(unsigned short)k2, (unsigned short)k3};
+    k.K45 = ushort2_t{(unsigned short)k4, (unsigned short)k5};
+    k.K60 = ushort2_t{(unsigned short)k6, 0};
+    return k;
+}
+
+// rBRIEF (:108-147) from RT and the keypoint store: 256 tests as four 64-lane ballots; sample (ix, iy) of the
+// blurred patch at blurT[(18+ix)*40 + 18+iy]
+template <bool FMA>
+__device__ __forceinline__ void desc_brief_store(const Geom* __restrict__ g, const DescSlot& d, int f, int lane,
+                                                 const uint16_t* rt, const DescBlurK& k, const float (&pf)[4][4],
+                                                 float angle, float a, float b, orb_keypoint* __restrict__ outK,
+                                                 uint8_t* __restrict__ outD, int kpCap) {
+    const int l = d.l, x = d.x, y = d.y;
+    const LevelGeom& L = g->L[l];
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(outD + ((long long)f * kpCap + d.outIdx) * 32);
+    if (x + 18 < k.xsimd) brief_sampled<true, FMA>(rt, a, b, pf, x - 18, k.xsimd, k.K01, k.K23, k.K45, k.K60, lane, dst);
+    else brief_sampled<false, FMA>(rt, a, b, pf, x - 18, k.xsimd, k.K01, k.K23, k.K45, k.K60, lane, dst);
     if (lane == 0) {
         orb_keypoint o;
         o.x = (float)x;
@@ -2530,17 +2564,135 @@ __device__ __forceinline__ void desc_body(const Geom* __restrict__ g, const Desc
         }
         o.size = L.patch_size;
         o.angle = angle;
-        o.response = (float)score;
+        o.response = (float)d.score;
         o.octave = l;
         o.class_id = -1;
-        outK[(long long)f * kpCap + outIdx] = o;
+        outK[(long long)f * kpCap + d.outIdx] = o;
     }
-    DESC_STAMP(6);
-#undef DESC_STAMP
+}
+
+__device__ __forceinline__ unsigned long long* desc_stamp_row(const Geom* __restrict__ g, const DescSlot& d, int f,
+                                                              unsigned long long* __restrict__ dstamps) {
+    return dstamps ? dstamps + ((long long)f * g->nkpcap + d.s) * 8 : nullptr;
+}
+
+// One keypoint from its window to its descriptor: spw == 1 (one-frame batches, the host path), the dataflow
+// launch, and every slot of k_describe that desc_pair does not take.
+template <bool FMA, int CP = 0>
+__device__ __forceinline__ void desc_single(const Geom* __restrict__ g, const DescSlot& d, int f, int lane,
+                                            const uint32_t (&v)[9], uint8_t* wbase, uint16_t* rt,
+                                            orb_keypoint* __restrict__ outK, uint8_t* __restrict__ outD, int kpCap,
+                                            unsigned long long* __restrict__ dstamps) {
+    [[maybe_unused]] unsigned long long* st = desc_stamp_row(g, d, f, dstamps);
+    desc_stamp(st, lane, 0);
+    uint32_t icm[4];
+    desc_ic_masks(lane, icm);   // issued before the window is stored
+    const int sh = desc_store_window<CP>(g, d, lane, v, wbase);
+    wave_lds_sync();
+    desc_stamp(st, lane, 1);
+#if defined(ORBGPU_DESC_CUT) && ORBGPU_DESC_CUT == 1   // instruction-count diagnostics only (tools/diag_cut.sh)
+    if (lane == 0) outD[((long long)f * kpCap + d.outIdx) * 32] = wbase[lane];
+    return;
+#endif
+    const IcMoments m = desc_ic_moments(reinterpret_cast<const uint32_t*>(wbase), sh, lane, icm);
+    const float angle = desc_trig_angle((float)m.m01, (float)m.m10);
+    desc_stamp(st, lane, 2);
+#if defined(ORBGPU_DESC_CUT) && ORBGPU_DESC_CUT == 2
+    if (lane == 0) outD[((long long)f * kpCap + d.outIdx) * 32] = (uint8_t)angle;
+    return;
+#endif
+    desc_row_pass(g, sh, lane, wbase, rt);
+    wave_lds_sync();
+    desc_stamp(st, lane, 3);
+#if defined(ORBGPU_DESC_CUT) && ORBGPU_DESC_CUT == 3
+    if (lane == 0) outD[((long long)f * kpCap + d.outIdx) * 32] = (uint8_t)(angle + rt[lane]);
+    return;
+#endif
+    const DescBlurK k = desc_blur_k(g, d);
+    desc_stamp(st, lane, 4);
+    float pf[4][4];
+    desc_pattern(lane, pf);   // issued before the rotation so their latency hides under it
+    float a, b;
+    desc_trig_rotation(angle, &a, &b);
+    desc_stamp(st, lane, 5);
+    desc_brief_store<FMA>(g, d, f, lane, rt, k, pf, angle, a, b, outK, outD, kpCap);
+    desc_stamp(st, lane, 6);
+}
+
+// Slot 1's window waits in the wave's RT region (from offset 0) while both slots' moments are taken: that region
+// is dead until slot 0's row pass stores into it, and the whole 43 x 48 window ends below slot 0's window
+static_assert(kDescWin * kDescWinPitch <= kDescWinOff, "k_describe: the paired slot's temporary window");
+
+// Two keypoints of one wave, slot 1 interior (its window is in registers, v1): the IC moments of both windows
+// are taken first and the orientation trig runs once, lanes 0..31 on slot 0's moments and lanes 32..63 on slot
+// 1's; each slot's angle, cos and sin come back by readlane (SGPRs) and the rest of each slot runs as in
+// desc_single.  The trig is the same instruction sequence on the same inputs, so the values are desc_single's.
+template <bool FMA>
+__device__ __forceinline__ void desc_pair(const Geom* __restrict__ g, const DescSlot& d0, const DescSlot& d1, int f,
+                                          int lane, const uint32_t (&v0)[9], const uint32_t (&v1)[9], uint8_t* wbase,
+                                          uint16_t* rt, orb_keypoint* __restrict__ outK, uint8_t* __restrict__ outD,
+                                          int kpCap, unsigned long long* __restrict__ dstamps) {
+    [[maybe_unused]] unsigned long long* st0 = desc_stamp_row(g, d0, f, dstamps);
+    [[maybe_unused]] unsigned long long* st1 = desc_stamp_row(g, d1, f, dstamps);
+    desc_stamp(st0, lane, 0);
+    uint32_t icm[4];
+    desc_ic_masks(lane, icm);
+    uint32_t* const w32 = reinterpret_cast<uint32_t*>(wbase);
+    uint32_t* const t32 = reinterpret_cast<uint32_t*>(rt);   // slot 1's temporary window
+    const int sh0 = desc_store_window<0>(g, d0, lane, v0, wbase);
+    const int sh1 = desc_store_regs(d1, lane, v1, t32);
+    wave_lds_sync();
+    desc_stamp(st0, lane, 1);
+    const IcMoments m0 = desc_ic_moments(w32, sh0, lane, icm);
+    const IcMoments m1 = desc_ic_moments(t32, sh1, lane, icm);
+    // The temporary window is read here and RT is written by slot 0's row pass below.  As for RT's overlay of
+    // the window rows (kDescWinOff), the order is the wave's program order: both are plain LDS accesses through
+    // one carve, which the compiler keeps in order (-fno-strict-aliasing), and a wave's LDS instructions issue
+    // and complete in order: no sync of its own.
+    const bool hi = lane >= 32;
+    const DescTrig t = desc_trig((float)(hi ? m1.m01 : m0.m01), (float)(hi ? m1.m10 : m0.m10));
+    auto lane_f = [](float x, int l) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
+    };
+    const float angle0 = lane_f(t.angle, 0), a0 = lane_f(t.a, 0), b0 = lane_f(t.b, 0);
+    const float angle1 = lane_f(t.angle, 32), a1 = lane_f(t.a, 32), b1 = lane_f(t.b, 32);
+    desc_stamp(st0, lane, 2);
+    {   // slot 0
+        desc_row_pass(g, sh0, lane, wbase, rt);
+        wave_lds_sync();
+        desc_stamp(st0, lane, 3);
+        const DescBlurK k = desc_blur_k(g, d0);
+        desc_stamp(st0, lane, 4);
+        float pf[4][4];
+        desc_pattern(lane, pf);
+        desc_stamp(st0, lane, 5);
+        desc_brief_store<FMA>(g, d0, f, lane, rt, k, pf, angle0, a0, b0, outK, outD, kpCap);
+        desc_stamp(st0, lane, 6);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    wave_lds_sync();   // slot 0's LDS reads precede these window stores
+    {   // slot 1: its moments and trig are done
+        desc_stamp(st1, lane, 0);
+        desc_store_regs(d1, lane, v1, w32);
+        wave_lds_sync();
+        desc_stamp(st1, lane, 1);
+        desc_stamp(st1, lane, 2);
+        desc_row_pass(g, sh1, lane, wbase, rt);
+        wave_lds_sync();
+        desc_stamp(st1, lane, 3);
+        const DescBlurK k = desc_blur_k(g, d1);
+        desc_stamp(st1, lane, 4);
+        float pf[4][4];
+        desc_pattern(lane, pf);
+        desc_stamp(st1, lane, 5);
+        desc_brief_store<FMA>(g, d1, f, lane, rt, k, pf, angle1, a1, b1, outK, outD, kpCap);
+        desc_stamp(st1, lane, 6);
+    }
 }
 
 /* Fused IC angle + 7x7 blur + rBRIEF, one wavefront per keypoint slot; a wavefront owns two consecutive
- * slots and issues the second interior window's loads before processing the first. */
+ * slots and issues the second interior window's loads before processing the first.  With both slots filled and
+ * the second one interior the two share one orientation-trig pass (desc_pair). */
 constexpr int kDescWaves = 4, kDescSlotsPerWave = 2;
 template <bool FMA>   // false: ORB_VARIANT_NO_FMA
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_describe(const Geom* __restrict__ g, const uint8_t* __restrict__ frames,
@@ -2590,11 +2742,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     if (d0.ok && d0.interior) desc_issue(d0, lane, v0);
     if (d1.ok && d1.interior) desc_issue(d1, lane, v1);
     write_n();   // (after the window loads are issued)
-    if (d0.ok) desc_body<FMA>(g, d0, f, lane, v0, s_wave + kDescWinOff, reinterpret_cast<uint16_t*>(s_wave), outK, outD, kpCap, dstamps);
+    uint8_t* const wbase = s_wave + kDescWinOff;
+    uint16_t* const rt = reinterpret_cast<uint16_t*>(s_wave);
+#ifdef ORBGPU_DESC_CUT   // the phase-cut diagnostics cut desc_single
+    constexpr bool kPair = false;
+#else
+    constexpr bool kPair = true;
+#endif
+    if (kPair && d0.ok && d1.ok && d1.interior) {   // one trig pass for the two keypoints
+        desc_pair<FMA>(g, d0, d1, f, lane, v0, v1, wbase, rt, outK, outD, kpCap, dstamps);
+        return;
+    }
+    if (d0.ok) desc_single<FMA>(g, d0, f, lane, v0, wbase, rt, outK, outD, kpCap, dstamps);
     if (d1.ok) {
         __builtin_amdgcn_sched_barrier(0);
         wave_lds_sync();   // the first keypoint's LDS reads precede these window stores
-        desc_body<FMA>(g, d1, f, lane, v1, s_wave + kDescWinOff, reinterpret_cast<uint16_t*>(s_wave), outK, outD, kpCap, dstamps);
+        desc_single<FMA>(g, d1, f, lane, v1, wbase, rt, outK, outD, kpCap, dstamps);
     }
 }
 
@@ -2771,8 +2934,8 @@ __device__ __forceinline__ void flow_describe(const FlowArgs* __restrict__ Ap, i
     if (!d.ok) return;
     uint32_t v[9];
     if (d.interior) desc_issue<kCpSc1>(d, lane, v);
-    desc_body<FMA, kCpSc1>(g, d, f, lane, v, sw + kDescWinOff, reinterpret_cast<uint16_t*>(sw), Ap->outK, Ap->outD,
-                           Ap->kpCap, nullptr);
+    desc_single<FMA, kCpSc1>(g, d, f, lane, v, sw + kDescWinOff, reinterpret_cast<uint16_t*>(sw), Ap->outK, Ap->outD,
+                             Ap->kpCap, nullptr);
 }
 
 template <int TQ, bool FMA>
