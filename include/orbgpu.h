@@ -621,6 +621,71 @@ int orb_vocab_bow(const orb_vocab* v, int n, const int* word_id, const float* we
  * an empty list (the reference returns without touching mDescriptor).  Host pointers, synchronous. */
 int orb_distinctive_descriptors(orb_ctx* ctx, int nmp, const int* offsets, const uint8_t* desc, int* best_idx);
 
+/* ======================= KeyFrameDatabase: loop and relocalisation candidates ======================= */
+
+/* The step between ComputeBoW and the candidates' SearchByBoW: KeyFrameDatabase (src/KeyFrameDatabase.cc:33-309) and
+ * ORBVocabulary::score for an L1 vocabulary (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), with the BowVectors of
+ * the live keyframes resident on the context's device.  A BowVector is nbow (word, value) pairs, words strictly
+ * ascending and >= 0, values finite (orb_vocab_bow's output).  Every entry point returns ORB_ERR_ARG before any GPU
+ * work for a NULL handle or NULL outputs, negative counts, words that are negative or not strictly ascending, a value
+ * that is not finite, and a handle of another device than the context's.  One thread at a time per handle; the handle
+ * is destroyed before its context.
+ * ONLY L1 SCORING is offered (the ORB vocabulary's): L2Scoring sums vi * wi, whose contraction into an FMA the
+ * reference build leaves to its compiler flags and which would have to be pinned first.
+ *
+ *   orb_kfdb_create / destroy   an empty database on ctx's device / frees it.
+ *   orb_kfdb_add       KeyFrameDatabase::add (:40-46).  *id = the add sequence number: ids start at 0, count up and are
+ *                      never reused.  The pool starts at 1,024 words and grows by doubling.
+ *   orb_kfdb_erase     KeyFrameDatabase::erase (:48-67): the entry is flagged, the others keep their order; an unknown
+ *                      or already erased id is ORB_ERR_ARG.  Once more than half of the pool is dead the next add or
+ *                      query packs it again (order and ids unchanged).
+ *   orb_kfdb_clear     KeyFrameDatabase::clear (:69-73); ids keep counting up.
+ *   orb_kfdb_size      live entries (0 for NULL).
+ *   orb_kfdb_query     the sharing-list loops of DetectLoopCandidates (:86-104) and DetectRelocalizationCandidates
+ *                      (:207-222), and the scores of :133 / :249 and of LoopClosing::DetectLoop's minScore loop
+ *                      (LoopClosing.cc:122-141), in one launch and one synchronisation.  Returns, in the order of
+ *                      lKFsSharingWords (ascending index of the keyframe's first common word within the query, then add
+ *                      sequence), every live keyframe that is not in excl_ids and shares at least one word: ids[i],
+ *                      common[i] (mnLoopWords / mnRelocWords) and score[i], the DOUBLE L1Scoring::score(query, keyframe)
+ *                      returns, byte for byte (terms added in ascending word order, one at a time).  That is a superset
+ *                      of the keyframes the reference scores; orb_kfdb_candidates applies the cut.  excl_ids are
+ *                      spConnectedKeyFrames (:78, :96); excl_score (nexcl entries, or NULL) receives the same double for
+ *                      each excluded keyframe, -0.0 when it shares no word; an excluded id that was erased is accepted
+ *                      and ignored and its excl_score left untouched; an id that was never issued is ORB_ERR_ARG.
+ *                      ORB_ERR_CAPACITY with *n set when cap < *n; every output array is then untouched.  nbow == 0 or
+ *                      an empty database: ORB_OK, *n = 0, no GPU work.
+ *   orb_kfdb_candidates  pure host: everything after the sharing list, for either form (:107-196 LOOP, :224-308 RELOC),
+ *                      on orb_kfdb_query's outputs: int minCommonWords = maxCommonWords * 0.8f, float si = score, the
+ *                      covisibility accumulation in float over nb(user, id, out, 10) = GetBestCovisibilityKeyFrames(10)
+ *                      (the callback writes up to cap ids in the reference's order and returns their number; it is called
+ *                      only for the entries of lScoreAndMatch, in order), 0.75f * bestAccScore, first occurrence of
+ *                      each best keyframe.  cand_ids needs room for n ids.  RELOC: a neighbour counts iff it is in the
+ *                      list, scored or not, and contributes its mRelocScore, which lives in the handle, is set by every
+ *                      RELOC call that scores the keyframe, and is 0.0f until then (PINNED: the reference leaves it
+ *                      uninitialised, KeyFrame.cc:35); min_score is ignored.  LOOP: lScoreAndMatch holds si >= min_score,
+ *                      a neighbour counts iff it is in the list and above the cut, with this call's score;
+ *                      bestAccScore starts at min_score.  db == NULL is accepted by this entry point alone: a call
+ *                      without state (every mRelocScore reads 0.0f before this call scores it; nothing is kept).
+ *   orb_bow_score      pure host: ORBVocabulary::score(v1, v2) of an L1 vocabulary.
+ *   orb_kfdb_query_lds_words  the longest query orb_kfdb_query stages in LDS; a longer one is read from global memory
+ *                      (same results). */
+typedef struct orb_kfdb orb_kfdb;
+int  orb_kfdb_create(orb_ctx* ctx, orb_kfdb** out);
+void orb_kfdb_destroy(orb_kfdb* db);
+int  orb_kfdb_add(orb_ctx* ctx, orb_kfdb* db, int nbow, const int* words, const double* values, int* id);
+int  orb_kfdb_erase(orb_kfdb* db, int id);
+int  orb_kfdb_clear(orb_kfdb* db);
+int  orb_kfdb_size(const orb_kfdb* db);
+int  orb_kfdb_query(orb_ctx* ctx, orb_kfdb* db, int nbow, const int* words, const double* values,
+                    int nexcl, const int* excl_ids, double* excl_score,
+                    int cap, int* ids, int* common, double* score, int* n);
+typedef int (*orb_kfdb_neighbours_fn)(void* user, int id, int* out, int cap);
+enum { ORB_KFDB_RELOC = 0, ORB_KFDB_LOOP = 1 };
+int  orb_kfdb_candidates(orb_kfdb* db, int mode, float min_score, int n, const int* ids, const int* common,
+                         const double* score, orb_kfdb_neighbours_fn nb, void* user, int* cand_ids, int* ncand);
+int  orb_bow_score(int n1, const int* w1, const double* v1, int n2, const int* w2, const double* v2, double* score);
+int  orb_kfdb_query_lds_words(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,8 +33,8 @@ bool ORBVocabulary::loadFromBinaryFile(const std::string& filename) {
     if (voc_) orb_vocab_destroy(voc_);
     voc_ = nullptr;
     if (orb_vocab_load(ctx_, filename.c_str(), &voc_) != ORB_OK) return false;
-    int sc, wt, nn;
-    orb_vocab_info(voc_, &k_, &L_, &sc, &wt, &nn, &nwords_);
+    int wt, nn;
+    orb_vocab_info(voc_, &k_, &L_, &scoring_, &wt, &nn, &nwords_);
     return true;
 }
 
@@ -58,6 +58,22 @@ void ORBVocabulary::transform(const DescriptorMat& features, BowVector& v, BowFe
     for (int j = 0; j < nf; j++)
         fv.insert(fv.end(), BowFeatureVector::value_type(fn[j], std::vector<unsigned int>(idx.begin() + off[j],
                                                                                               idx.begin() + off[j + 1])));
+}
+
+double ORBVocabulary::score(const BowVector& v1, const BowVector& v2) const {
+    if (scoring_ != 0) throw OrbGpuError(ORB_ERR_ARG, "ORBVocabulary::score: only L1 scoring is offered");
+    std::vector<int> w[2];
+    std::vector<double> x[2];
+    const BowVector* v[2] = {&v1, &v2};
+    for (int k = 0; k < 2; k++)
+        for (BowVector::const_iterator it = v[k]->begin(); it != v[k]->end(); ++it) {
+            w[k].push_back((int)it->first);   // (a word id above 2^31 - 1 turns negative: refused below)
+            x[k].push_back(it->second);
+        }
+    double s = 0;
+    const int st = orb_bow_score((int)w[0].size(), w[0].data(), x[0].data(), (int)w[1].size(), w[1].data(), x[1].data(), &s);
+    if (st != ORB_OK) throw OrbGpuError(st, "ORBVocabulary::score");
+    return s;
 }
 
 }  // namespace ORB_SLAM2

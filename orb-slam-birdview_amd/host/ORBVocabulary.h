@@ -5,6 +5,8 @@
  * FeatureVector&, levelsup) (:1139-1210, called by Frame::ComputeBoW, Frame.cc:562-569).  The tree
  * descent of every feature runs on the GPU; BowVector / FeatureVector are assembled in feature order
  * exactly as DBoW2 does.  GPU failures throw ORB_SLAM2::OrbGpuError.
+ * score(v1, v2) (TemplatedVocabulary.h: m_scoring_object->score) is L1Scoring::score (ScoringObject.cpp:23-68), the ORB
+ * vocabulary's, on the host; a vocabulary loaded with another scoring type throws (only L1 is offered).
  */
 #ifndef ORBGPU_HOST_ORBVOCABULARY_H
 #define ORBGPU_HOST_ORBVOCABULARY_H
@@ -29,6 +31,7 @@ public:
 
     bool loadFromBinaryFile(const std::string& filename);
     void transform(const DescriptorMat& features, BowVector& v, BowFeatureVector& fv, int levelsup) const;
+    double score(const BowVector& v1, const BowVector& v2) const;
 
     bool empty() const { return nwords_ == 0; }
     unsigned int size() const { return (unsigned int)nwords_; }
@@ -38,7 +41,7 @@ public:
 private:
     orb_ctx* ctx_ = nullptr;
     orb_vocab* voc_ = nullptr;
-    int k_ = 0, L_ = 0, nwords_ = 0;
+    int k_ = 0, L_ = 0, nwords_ = 0, scoring_ = 0;   // scoring_: DBoW2::ScoringType, L1_NORM = 0
 };
 
 }  // namespace ORB_SLAM2

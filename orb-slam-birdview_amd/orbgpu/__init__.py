@@ -12,12 +12,13 @@ import numpy as np
 
 from ._lib import (VARIANT_BLUR_HALFUP, VARIANT_DEFAULT, VARIANT_NO_FMA, VARIANT_RESIZE_GENERIC,
                    VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, OrbProjFrameTarget,
-                   OrbProjTarget, check, lib)
+                   OrbProjTarget, KfdbNeighboursFn, check, lib)
 
 __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError", "device_count",
            "features_in_area", "frame_grid", "Frame", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
            "PROJ_GATE_NONE", "PROJ_GATE_FUSE", "proj_queries", "project_best_host",
-           "compute_stereo_matches", "ORBVocabulary", "BirdORB", "cornerSubPix",
+           "compute_stereo_matches", "ORBVocabulary", "KeyFrameDatabase", "bow_score", "KFDB_RELOC", "KFDB_LOOP",
+           "BirdORB", "cornerSubPix",
            "bird_footprint_mask", "VARIANT_DEFAULT", "VARIANT_TIE_REVERSE", "VARIANT_RESIZE_GENERIC",
            "VARIANT_BLUR_HALFUP", "VARIANT_NO_FMA"]
 
@@ -1111,3 +1112,125 @@ def bird_footprint_mask(mask):
     h, w = m.shape
     check(lib().orb_bird_footprint_mask(_p(m), w, h, m.strides[0]), "orb_bird_footprint_mask")
     return m
+
+
+KFDB_RELOC, KFDB_LOOP = 0, 1   # ORB_KFDB_*
+
+
+def _bow_arrays(words, values=None):
+    """A BowVector as (int32 words ascending, float64 values): two arrays, or a {word: value} dict (sorted here)."""
+    if values is None:
+        items = sorted(dict(words).items())
+        words, values = [w for w, _ in items], [v for _, v in items]
+    w = np.ascontiguousarray(words, np.int64)
+    assert len(w) == 0 or (0 <= w.min() and w.max() < 2 ** 31), "word ids are non-negative int32"
+    w, v = np.ascontiguousarray(w, np.int32), np.ascontiguousarray(values, np.float64)
+    assert w.ndim == 1 and w.shape == v.shape
+    return w, v
+
+
+def bow_score(words1, values1, words2, values2):
+    """ORBVocabulary::score(v1, v2) of an L1 vocabulary (DBoW2 L1Scoring::score, ScoringObject.cpp:23-68): the double.
+    Pure host."""
+    w1, v1 = _bow_arrays(words1, values1)
+    w2, v2 = _bow_arrays(words2, values2)
+    out = ctypes.c_double()
+    check(lib().orb_bow_score(len(w1), _p(w1), _p(v1), len(w2), _p(w2), _p(v2), ctypes.byref(out)), "orb_bow_score")
+    return out.value
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc) with the keyframes'
+    BowVectors resident on the GPU (orb_kfdb).  Keyframes are named by the id add() returns (the add sequence: from 0,
+    never reused).  BowVectors are (words, values) arrays with words ascending, or {word: value} dicts with values=None.
+    Only L1 scoring (the ORB vocabulary's).
+
+    KeyFrameDatabase(ctx_or_matcher) shares that object's context (several databases may); KeyFrameDatabase(device=d)
+    owns one.  close() frees the database; close it before its context."""
+
+    def __init__(self, ctx_or_matcher=None, device=0):
+        self.h = None
+        self._ctx = _Ctx(1000, 1.2, 8, 20, 7, device) if ctx_or_matcher is None else getattr(ctx_or_matcher, "_ctx",
+                                                                                           ctx_or_matcher)
+        out = ctypes.c_void_p()
+        check(lib().orb_kfdb_create(self._ctx.h, ctypes.byref(out)), "orb_kfdb_create")
+        self.h = out
+
+    def add(self, words, values=None):
+        """KeyFrameDatabase::add (:40-46) -> the keyframe's id."""
+        w, v = _bow_arrays(words, values)
+        out = ctypes.c_int(-1)
+        check(lib().orb_kfdb_add(self._ctx.h, self.h, len(w), _p(w), _p(v), ctypes.byref(out)), "orb_kfdb_add")
+        return out.value
+
+    def erase(self, kf_id):
+        check(lib().orb_kfdb_erase(self.h, int(kf_id)), "orb_kfdb_erase")
+
+    def clear(self):
+        check(lib().orb_kfdb_clear(self.h), "orb_kfdb_clear")
+
+    def __len__(self):
+        return lib().orb_kfdb_size(self.h)
+
+    def query(self, words, values=None, exclude=()):
+        """The sharing list of a query BowVector -> (ids, common, score, excl_score): the live keyframes outside
+        `exclude` that share a word, in the reference's lKFsSharingWords order, their common-word counts and the
+        doubles L1Scoring::score(query, keyframe) returns; excl_score[j] is that double for exclude[j] (-0.0: no word
+        shared; NaN: erased, not scored)."""
+        w, v = _bow_arrays(words, values)
+        ex = np.ascontiguousarray(list(exclude), np.int32)
+        xs = np.full(max(len(ex), 1), np.nan, np.float64)
+        cap = len(self)
+        ids, common = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        score = np.zeros(max(cap, 1), np.float64)
+        n = ctypes.c_int()
+        check(lib().orb_kfdb_query(self._ctx.h, self.h, len(w), _p(w), _p(v), len(ex), _p(ex), _p(xs), cap, _p(ids),
+                                   _p(common), _p(score), ctypes.byref(n)), "orb_kfdb_query")
+        return ids[:n.value], common[:n.value], score[:n.value], xs[:len(ex)]
+
+    def candidates(self, mode, ids, common, score, neighbours, min_score=0.0):
+        """Everything after the sharing list (orb_kfdb_candidates) -> candidate ids.  neighbours(id) returns the ids of
+        GetBestCovisibilityKeyFrames(10) of that keyframe, best first (more than 10 are cut to 10)."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        common = np.ascontiguousarray(common, np.int32)
+        score = np.ascontiguousarray(score, np.float64)
+        n = len(ids)
+        out = np.zeros(max(n, 1), np.int32)
+        nc = ctypes.c_int()
+        failure = []
+
+        def nb(_user, kf_id, dst, cap):
+            try:
+                got = [int(x) for x in neighbours(kf_id)][:cap]
+            except Exception as e:   # (an exception cannot cross the C frame)
+                failure.append(e)
+                return -1
+            for i, x in enumerate(got):
+                dst[i] = x
+            return len(got)
+
+        st = lib().orb_kfdb_candidates(self.h, mode, float(min_score), n, _p(ids), _p(common), _p(score),
+                                       KfdbNeighboursFn(nb), None, _p(out), ctypes.byref(nc))
+        if failure:
+            raise failure[0]
+        check(st, "orb_kfdb_candidates")
+        return out[:nc.value].copy()
+
+    def detect_relocalization_candidates(self, words, values=None, neighbours=lambda kf_id: ()):
+        """KeyFrameDatabase::DetectRelocalizationCandidates (:199-309) of a frame's BowVector -> keyframe ids."""
+        ids, common, score, _ = self.query(words, values)
+        return self.candidates(KFDB_RELOC, ids, common, score, neighbours)
+
+    def detect_loop_candidates(self, words, values=None, connected=(), min_score=0.0, neighbours=lambda kf_id: ()):
+        """KeyFrameDatabase::DetectLoopCandidates (:76-197) of a keyframe's BowVector; connected = the ids of
+        GetConnectedKeyFrames() -> keyframe ids."""
+        ids, common, score, _ = self.query(words, values, connected)
+        return self.candidates(KFDB_LOOP, ids, common, score, neighbours, min_score)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().orb_kfdb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()

@@ -61,6 +61,9 @@ class OrbProjFrameTarget(ctypes.Structure):   # orb_proj_frame_target
                 ("best_idx", vp), ("best_dist", vp)]
 
 
+# orb_kfdb_neighbours_fn: int (*)(void* user, int id, int* out, int cap)
+KfdbNeighboursFn = ctypes.CFUNCTYPE(ci, vp, ci, ctypes.POINTER(ci), ci)
+
 # name -> (restype, argtypes); mirrors include/orbgpu.h
 SIGNATURES = {
     "orb_abi_version": (ci, []),
@@ -142,6 +145,16 @@ SIGNATURES = {
     "orb_bird_footprint_mask": (ci, [vp, ci, ci, csz]),
     "orb_bird_debug_candidates": (ci, [vp, ci, vp, ci]),
     "orb_bird_debug_level": (ci, [vp, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "orb_kfdb_create": (ci, [vp, ctypes.POINTER(vp)]),
+    "orb_kfdb_destroy": (None, [vp]),
+    "orb_kfdb_add": (ci, [vp, vp, ci, vp, vp, ctypes.POINTER(ci)]),
+    "orb_kfdb_erase": (ci, [vp, ci]),
+    "orb_kfdb_clear": (ci, [vp]),
+    "orb_kfdb_size": (ci, [vp]),
+    "orb_kfdb_query": (ci, [vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, ctypes.POINTER(ci)]),
+    "orb_kfdb_candidates": (ci, [vp, ci, cf, ci, vp, vp, vp, KfdbNeighboursFn, vp, vp, ctypes.POINTER(ci)]),
+    "orb_bow_score": (ci, [ci, vp, vp, ci, vp, vp, ctypes.POINTER(ctypes.c_double)]),
+    "orb_kfdb_query_lds_words": (ci, []),
 }
 
 STATUS = {0: "ORB_OK", -1: "ORB_ERR_ARG", -2: "ORB_ERR_HIP", -3: "ORB_ERR_CAPACITY",
