@@ -670,10 +670,11 @@ __global__ __launch_bounds__(256) void k_pyramid_chain(const Geom* __restrict__ 
 // the low half and the max of -p = -(min p) in the high half: the 9-arc extrema of both sides are 16 + 16
 // pk_maximum3, their min over the 16 arcs 8 pk_minimum3 (the -p negation folds into neg_hi modifiers).
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+// The pair is a splat of the loaded byte's low half, so the first-level maxima read both halves from it
+// (op_sel_hi:[0,0,0] with neg_hi): no instruction per circle value forms the pair.
 __device__ __forceinline__ half2_t circle_pair(int p) {   // (p, -p)
-    half2_t q = __builtin_bit_cast(half2_t, (uint32_t)p * 0x10001u);
-    q.y = -q.y;
-    return q;
+    const _Float16 h = __builtin_bit_cast(_Float16, (uint16_t)p);
+    return half2_t{h, -h};
 }
 __device__ __forceinline__ half2_t pk_max3h(half2_t a, half2_t b, half2_t c) {
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
@@ -1028,7 +1029,7 @@ __device__ __forceinline__ uint32_t prefilter16(lds_cu32* w, uint32_t tt) {   //
 // sList in raster order (one wave prefix sum of the per-lane counts per row round, then each lane
 // writes its entries at its offset).  Returns the list length.
 template <int TQ>
-__device__ __forceinline__ int prefilter_cell(const uint32_t* t32, int dh, int rpi, int lrow, bool lane_on, int x0,
+__device__ __forceinline__ int prefilter_cell(const uint32_t* t32, int dh, int rpi, int lrow, bool lane_on, int lbase,
                                               uint32_t xvalid, uint32_t tt, uint16_t* sList) {
     int nlist = 0;
     for (int r0 = 0; r0 < dh; r0 += rpi) {
@@ -1043,8 +1044,10 @@ __device__ __forceinline__ int prefilter_cell(const uint32_t* t32, int dh, int r
         const int cnt = __popc(pm);
         const int incl = wave_incl_scan(cnt);
         int pos = nlist + incl - cnt;
-        // entries are the pixels' byte offsets in the tile from domain pixel (0, 0): dy * 2TQ + 2x
-        const int base = dy * (2 * TQ) + 2 * x0;
+        // entries are the pixels' byte offsets in the tile from domain pixel (0, 0): dy * 2TQ + 2x.  The lane's
+        // part (lbase = lrow * 2TQ + 2 x0, t32's byte offset) is fixed for the cell and the row round's part is
+        // wave-uniform: one add per round, no per-lane multiply (v_mul_lo_u32 is quarter rate)
+        const int base = lbase + r0 * (2 * TQ);
         // one iteration per set bit (survivors are sparse: the wave runs max-popcount iterations)
         for (uint32_t b = (uint32_t)pm; b; b &= b - 1) sList[pos++] = (uint16_t)(base + 2 * __builtin_ctz(b));
         nlist += __builtin_amdgcn_readlane(incl, 63);
@@ -1073,7 +1076,8 @@ __device__ __forceinline__ void fast_cell_body(const Geom* __restrict__ g, const
     const int x0 = PX * (lane - lrow * nruns);
     const bool lane_on = lrow < rpi;
     const uint32_t xvalid = x0 + PX <= dw ? (1u << PX) - 1u : (1u << max(dw - x0, 0)) - 1u;
-    const uint32_t* t32 = reinterpret_cast<const uint32_t*>(tile) + ((lrow * TQ + x0) >> 1);   // row step TQ / 2
+    const int lpix = lrow * TQ + x0;   // the lane's first pixel as a tile element
+    const uint32_t* t32 = reinterpret_cast<const uint32_t*>(tile) + (lpix >> 1);   // row step TQ / 2
     uint8_t* t0 = reinterpret_cast<uint8_t*>(&tile[3 * TQ + 4]);   // domain pixel (0, 0), low byte
     // Pass 0 runs the whole cell at iniThFAST; only a cell left with no keypoint (:812-816) runs pass 1
     // at minThFAST.  The prefilter is a necessary condition for M > th at the pass threshold, so a
@@ -1086,7 +1090,7 @@ __device__ __forceinline__ void fast_cell_body(const Geom* __restrict__ g, const
         // ---- stage 1: compass prefilter at th, 8 pixels per lane as 16-bit pixel pairs, survivors
         // compacted into sList by one wave scan
         const uint32_t tt = (uint32_t)th | ((uint32_t)th << 16);
-        const int nlist = prefilter_cell<TQ>(t32, dh, rpi, lrow, lane_on, x0, xvalid, tt, sList);
+        const int nlist = prefilter_cell<TQ>(t32, dh, rpi, lrow, lane_on, 2 * lpix, xvalid, tt, sList);
         wave_lds_sync();
         ORBGPU_STAMP(2);
 #if defined(ORBGPU_FAST_CUT) && ORBGPU_FAST_CUT == 2
