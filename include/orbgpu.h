@@ -184,6 +184,39 @@ int orb_bird_extract(orb_bird* b, const uint8_t* img, int w, int h, size_t strid
 /* Same, image and mask already in device memory (bench / multi-stream callers). */
 int orb_bird_extract_device(orb_bird* b, const uint8_t* d_img, int w, int h, size_t stride, const uint8_t* d_mask,
                             size_t mask_stride, orb_keypoint* kps, int cap, int* n, uint8_t* desc);
+/* Frame.cc:320-342 for nframes birdview images of one size in one call: every stage before the keypoint
+ * selection is one launch over all frames, the host selects frame by frame, and the selected keypoints go
+ * through cornerSubPix / compute in groups behind the host.  0 <= nframes <= ORB_BIRD_MAX_BATCH.
+ *   device form: frame f starts at d_imgs + f * frame_pitch (frame_pitch >= stride * h), its mask at
+ *     d_masks + f * mask_frame_pitch; mask_frame_pitch 0: one mask shared by all frames (its pyramid is
+ *     built once per call); d_masks NULL: no mask.
+ *   host form: imgs[f] are host pointers; masks has nmasks entries: 0 (none), 1 (shared) or nframes.
+ * Masks are the caller's birdviewMask and are not modified (footprint zeroed in the device copy).
+ * Outputs are host memory: frame f's keypoints at kps + f * cap, descriptors at desc + f * cap * 32, count
+ * in counts[f]; each frame's output is byte for byte what orb_bird_extract_device returns for that frame
+ * and mask alone.  Slots past counts[f] are not written.
+ * Errors: ORB_ERR_ARG (before any GPU work, outputs untouched) for nframes out of range, NULL counts,
+ * NULL kps / desc with cap > 0, stride < w, mask_stride < w with a mask, a frame pitch below stride * h,
+ * nmasks not in {0, 1, nframes}.  nframes 0: ORB_OK, nothing touched.  w <= 0 or h <= 0: every count 0,
+ * ORB_OK.  ORB_ERR_CAPACITY when any counts[f] > cap: all counts are set, frames that fit are written in
+ * full, frames that do not are left untouched.  ORB_ERR_GEOMETRY / ORB_ERR_NOMEM as in the single call.
+ * Single and batch calls may alternate on one object at any sizes; the buffers of a size grow to the
+ * largest batch seen at that size and are reused (a new size starts again from the batch it is called
+ * with).  Device memory by the pyramid formulas: three pyramids (image, FAST score, blur) of about 3.0 MB
+ * and a candidate slot of about 12 MB per 1280x720 frame, plus a mask pyramid per frame with per-frame
+ * masks (one in all with a shared mask): about 24 MB per frame, about 1.5 GB at ORB_BIRD_MAX_BATCH.
+ * orb_bird_debug_candidates / orb_bird_debug_level are unspecified after a batch call. */
+#define ORB_BIRD_MAX_BATCH 64
+int orb_bird_extract_batch_device(orb_bird* b, int nframes, const uint8_t* d_imgs, int w, int h, size_t stride,
+                                  size_t frame_pitch, const uint8_t* d_masks, size_t mask_stride,
+                                  size_t mask_frame_pitch, orb_keypoint* kps, uint8_t* desc, int cap, int* counts);
+int orb_bird_extract_batch(orb_bird* b, int nframes, const uint8_t* const* imgs, int w, int h, size_t stride,
+                           const uint8_t* const* masks, int nmasks, size_t mask_stride, orb_keypoint* kps,
+                           uint8_t* desc, int cap, int* counts);
+/* Frames per post-selection group of the batch calls (keypoint upload + angle / subpix / desc launches
+ * that run while the host selects the next group).  group > 0 sets it (clamped to ORB_BIRD_MAX_BATCH);
+ * returns the value in force.  Results do not depend on it. */
+int orb_bird_batch_group(orb_bird* b, int group);
 /* Frame.cc:320-327: zero the vehicle footprint (+15 px boundary) of a birdview mask in place (host). */
 int orb_bird_footprint_mask(uint8_t* mask, int w, int h, size_t stride);
 /* debug: last detect's level-l candidates after mask / border / NMS, raster order, level coordinates;

@@ -8,6 +8,8 @@
 // restated from OpenCV 3.2 orb.cpp / keypoint.cpp / cornersubpix.cpp / samplers.cpp (the oracle's
 // oracle/cvorb_oracle.inc states each detail).
 //
+// Every kernel carries a frame dimension: the single-frame calls run it with one frame, the batch calls
+// (orb_bird_extract_batch*) run each stage once for up to ORB_BIRD_MAX_BATCH frames of one size.
 // Device side: pyramid (+ mask pyramid) by per-level resize launches, one FAST score-map launch over
 // all levels, a count / scan / emit pass that writes the masked, border-filtered, non-max-suppressed
 // candidates of every level in raster order together with their Harris responses, the 7x7 blurred
@@ -73,15 +75,17 @@ __device__ __forceinline__ int reflect101_d(int p, int len) {
 }
 
 /* ---------------- pyramid: cv::resize(prev level, INTER_LINEAR) (orb.cpp detectAndCompute) --------
- * plane 1 is the mask pyramid: resize of the previous (thresholded) mask level, then
- * threshold(254, 0, THRESH_TOZERO). */
+ * blockIdx.z < nframes is that frame's image pyramid; blockIdx.z - nframes is a mask pyramid (one when
+ * the batch shares its mask, one per frame otherwise): resize of the previous (thresholded) mask level,
+ * then threshold(254, 0, THRESH_TOZERO).  fpitch: bytes between two frames' pyramids. */
 __global__ __launch_bounds__(256) void k_bird_resize(const BirdGeom* __restrict__ g, int l,
                                                      const ResizeCoef* __restrict__ coef, uint8_t* __restrict__ pyr,
-                                                     uint8_t* __restrict__ mpyr) {
+                                                     uint8_t* __restrict__ mpyr, int nframes, unsigned fpitch) {
     const BirdLevel D = g->L[l], S = g->L[l - 1];
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= D.w) return;
-    uint8_t* base = blockIdx.z ? mpyr : pyr;
+    const bool is_mask = (int)blockIdx.z >= nframes;
+    uint8_t* base = is_mask ? mpyr + (size_t)(blockIdx.z - nframes) * fpitch : pyr + (size_t)blockIdx.z * fpitch;
     const ResizeCoef cx = coef[x], cy = coef[D.w + y];
     const uint8_t* r0 = base + S.off + (long long)cy.s0 * S.pitch;
     const uint8_t* r1 = base + S.off + (long long)cy.s1 * S.pitch;
@@ -90,15 +94,38 @@ __global__ __launch_bounds__(256) void k_bird_resize(const BirdGeom* __restrict_
     int v = (g->variant & ORB_VARIANT_RESIZE_GENERIC)
                 ? min((cy.c0 * h0 + cy.c1 * h1 + (1 << 21)) >> 22, 255)   // generic FixedPtCast
                 : (((cy.c0 * (h0 >> 4)) >> 16) + ((cy.c1 * (h1 >> 4)) >> 16) + 2) >> 2;
-    if (blockIdx.z) v = v > 254 ? v : 0;
+    if (is_mask) v = v > 254 ? v : 0;
     base[D.off + (long long)y * D.pitch + x] = (uint8_t)v;
+}
+
+/* ---------------- level 0 of a device-resident batch ----------------------------------------------------
+ * blockIdx.z < nframes copies frame z into its pyramid's level 0; blockIdx.z - nframes copies a mask and
+ * zeroes the vehicle footprint [fx0, fx1) x [fy0, fy1) in the copy (Frame.cc:320-327), so the caller's
+ * mask is only read. */
+__global__ __launch_bounds__(256) void k_bird_ingest(const BirdGeom* __restrict__ g, const uint8_t* __restrict__ imgs,
+                                                     size_t stride, size_t frame_pitch,
+                                                     const uint8_t* __restrict__ masks, size_t mstride,
+                                                     size_t mask_frame_pitch, uint8_t* __restrict__ pyr,
+                                                     uint8_t* __restrict__ mpyr, int nframes, unsigned fpitch, int fx0,
+                                                     int fy0, int fx1, int fy1) {
+    const BirdLevel L = g->L[0];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= L.w) return;
+    const unsigned d = (unsigned)L.off + y * L.pitch + x;
+    if ((int)blockIdx.z < nframes) {
+        (pyr + (size_t)blockIdx.z * fpitch)[d] = (imgs + blockIdx.z * frame_pitch)[y * stride + x];
+    } else {
+        const unsigned m = blockIdx.z - nframes;
+        const bool foot = fx0 <= x && x < fx1 && fy0 <= y && y < fy1;
+        (mpyr + (size_t)m * fpitch)[d] = foot ? (uint8_t)0 : (masks + m * mask_frame_pitch)[y * mstride + x];
+    }
 }
 
 /* ---------------- FAST 9/16 score map (cv::FAST, threshold fastThreshold, TYPE_9_16) -------------
  * score = (max over 9-arcs of the arc's weakest |v - p|, same sign) - 1 when that exceeds the
  * threshold (OpenCV cornerScore<16>), else 0.  Only rows/columns [edge-1, dim-edge] are scored: every
  * candidate that survives runByImageBorder(edge) lies in [edge, dim-edge) and its NMS neighbours one
- * pixel further out.  rows: (level, y) table. */
+ * pixel further out.  rows: (level, y) table; blockIdx.z: frame. */
 __device__ __forceinline__ int fast_score_at(const uint8_t* c, int P, int t) {
     const int v = c[0];
     int d[16];
@@ -135,11 +162,14 @@ __device__ __forceinline__ int fast_score_at(const uint8_t* c, int P, int t) {
 }
 
 __global__ __launch_bounds__(256) void k_bird_fast(const BirdGeom* __restrict__ g, const int2* __restrict__ rows,
-                                                   const uint8_t* __restrict__ pyr, uint8_t* __restrict__ score) {
+                                                   const uint8_t* __restrict__ pyr, uint8_t* __restrict__ score,
+                                                   unsigned fpitch) {
     const int2 r = rows[blockIdx.y];
     const BirdLevel L = g->L[r.x];
     const int x = g->edge - 1 + blockIdx.x * 256 + threadIdx.x;
     if (x > L.w - g->edge) return;
+    pyr += (size_t)blockIdx.z * fpitch;
+    score += (size_t)blockIdx.z * fpitch;
     const long long o = L.off + (long long)r.y * L.pitch + x;
     const uint8_t* c = pyr + o;
     const int P = L.pitch, t = g->fastTh, v = c[0];
@@ -152,17 +182,30 @@ __global__ __launch_bounds__(256) void k_bird_fast(const BirdGeom* __restrict__ 
 }
 
 /* ---------------- candidates: NMS + runByPixelsMask + runByImageBorder, raster order ------------
- * One wave per (level, y) row of [edge, h-edge); mode 0 counts, mode 1 writes at the scanned
- * offsets with the Harris response (orb.cpp HarrisResponses, blockSize 7, HARRIS_K 0.04f: integer
+ * One wave per (level, y) row of [edge, h-edge) of frame blockIdx.y; mode 0 counts, mode 1 writes at
+ * the scanned offsets of the frame's candidate slot with the Harris response (orb.cpp HarrisResponses, blockSize 7, HARRIS_K 0.04f: integer
  * gradient sums, then the float formula in the reference's evaluation order). */
 template <int kMode>
 __global__ __launch_bounds__(256) void k_bird_cands(const BirdGeom* __restrict__ g, const int2* __restrict__ rows,
                                                     int nrows, const uint8_t* __restrict__ pyr,
                                                     const uint8_t* __restrict__ mpyr, const uint8_t* __restrict__ score,
                                                     int* __restrict__ rowcnt, const int* __restrict__ rowoff,
-                                                    BirdCand* __restrict__ out) {
+                                                    BirdCand* __restrict__ out, unsigned fpitch, unsigned mfpitch,
+                                                    unsigned cand_slot) {
     const int wid = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (wid >= nrows) return;
+    {   // this frame's pyramid, mask pyramid (mfpitch 0: shared), score map, row tables and candidate slot
+        const unsigned f = blockIdx.y;
+        pyr += (size_t)f * fpitch;
+        score += (size_t)f * fpitch;
+        if (mpyr) mpyr += (size_t)f * mfpitch;
+        if (kMode) {
+            rowoff += f * (nrows + 1);
+            out += (size_t)f * cand_slot;
+        } else {
+            rowcnt += f * (nrows + 1);
+        }
+    }
     const int2 r = rows[wid];
     const BirdLevel L = g->L[r.x];
     const int e = g->edge, P = L.pitch;
@@ -226,12 +269,15 @@ __global__ __launch_bounds__(256) void k_bird_cands(const BirdGeom* __restrict__
     if (!kMode && lane == 0) rowcnt[wid] = pos;
 }
 
-// exclusive scan of the row counts (one block); per-level counts from the level row ranges
+// exclusive scan of a frame's row counts (one block per frame); per-level counts from the level row ranges
 __global__ __launch_bounds__(1024) void k_bird_scan(const int* __restrict__ rowcnt, int nrows,
                                                     const int* __restrict__ lvl_row0, int nlevels,
                                                     int* __restrict__ rowoff, int* __restrict__ lvlcnt) {
     __shared__ int s_w[16];
     __shared__ int s_carry;
+    rowcnt += blockIdx.x * (nrows + 1);
+    rowoff += blockIdx.x * (nrows + 1);
+    lvlcnt += blockIdx.x * kBirdMaxLevels;
     if (threadIdx.x == 0) s_carry = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -263,12 +309,14 @@ __global__ __launch_bounds__(1024) void k_bird_scan(const int* __restrict__ rowc
  * Integer separable filter; the column pass rounds half-to-even on columns x < (w & ~3) (OpenCV's SSE2
  * SymmColumnVec_32s8u) and half-up on the tail (FixedPtCastEx) — the oracle's gauss7_blur. */
 __global__ __launch_bounds__(256) void k_bird_blur(const BirdGeom* __restrict__ g, const int2* __restrict__ rows,
-                                                   const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur) {
+                                                   const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur,
+                                                   unsigned fpitch) {
     const int2 r = rows[blockIdx.y];
     const BirdLevel L = g->L[r.x];
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= L.w) return;
-    const uint8_t* src = pyr + L.off;
+    blur += (size_t)blockIdx.z * fpitch;
+    const uint8_t* src = pyr + (size_t)blockIdx.z * fpitch + L.off;
     int xs[7];
 #pragma unroll
     for (int j = 0; j < 7; j++) xs[j] = reflect101_d(x + j - 3, L.w);
@@ -291,7 +339,7 @@ __global__ __launch_bounds__(256) void k_bird_blur(const BirdGeom* __restrict__ 
 
 /* ---------------- ICAngles + pt *= layerScale (orb.cpp computeKeyPoints tail) ----------------------
  * One wave per keypoint: lane v in [0, 31) sums row v-15 of the circular patch (integer moments,
- * order-free), then cv::fastAtan2. */
+ * order-free), then cv::fastAtan2.  kframe (batch only): the frame whose pyramid keypoint k reads. */
 constexpr float kAtanScale = (float)(180 / 3.14159265358979323846);
 constexpr float kP1 = 0.9997878412794807f * kAtanScale;
 constexpr float kP3 = -0.3258083974640975f * kAtanScale;
@@ -317,11 +365,13 @@ __device__ __forceinline__ float cv_fast_atan2(float y, float x) {
 }
 
 __global__ __launch_bounds__(256) void k_bird_angle(const BirdGeom* __restrict__ g, const uint8_t* __restrict__ pyr,
-                                                    orb_keypoint* __restrict__ kps, int n) {
+                                                    orb_keypoint* __restrict__ kps, int n,
+                                                    const int* __restrict__ kframe, unsigned fpitch) {
     const int k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (k >= n) return;
     orb_keypoint kp = kps[k];
     const BirdLevel L = g->L[kp.octave];
+    if (kframe) pyr += (size_t)kframe[k] * fpitch;
     const uint8_t* center = pyr + L.off + (long long)(int)rintf(kp.y) * L.pitch + (int)rintf(kp.x);
     int m10 = 0, m01 = 0;
     if (lane < 31) {
@@ -398,13 +448,15 @@ __device__ __forceinline__ void subpix_row(const SubpixSrc& s, bool inside, int 
 
 __global__ __launch_bounds__(256) void k_bird_subpix(SubpixSrc s, const float* __restrict__ wmask, float* pts,
                                                      int stride, int n, int max_iters, double eps2, int edge,
-                                                     int* __restrict__ keep) {
+                                                     int* __restrict__ keep, const int* __restrict__ kframe,
+                                                     unsigned fpitch) {
     __shared__ float s_patch[4][kSubP * kSubP + 3];
     __shared__ double s_terms[4][5 * kSubE + 1];
     __shared__ __attribute__((aligned(16))) uint8_t s_cache[4][kSubC * kSubC];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int k = blockIdx.x * 4 + wv;
     if (k >= n) return;
+    if (kframe) s.img += (size_t)kframe[k] * fpitch;   // batch: the level-0 image of the point's frame
     float* patch = s_patch[wv];
     double* terms = s_terms[wv];
     float* pt = pts + (long long)k * stride;
@@ -513,9 +565,15 @@ __global__ __launch_bounds__(256) void k_bird_subpix(SubpixSrc s, const float* _
 __global__ __launch_bounds__(256) void k_bird_desc(const BirdGeom* __restrict__ g, const uint8_t* __restrict__ pyr,
                                                    const uint8_t* __restrict__ blur, const int* __restrict__ pattern,
                                                    const orb_keypoint* __restrict__ kps, const int* __restrict__ keep,
-                                                   int n, uint8_t* __restrict__ desc) {
+                                                   int n, uint8_t* __restrict__ desc, const int* __restrict__ kframe,
+                                                   unsigned fpitch) {
     const int k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (k >= n) return;
+    if (kframe) {   // batch: the pyramid and blurred pyramid of the keypoint's frame
+        const size_t fo = (size_t)kframe[k] * fpitch;
+        pyr += fo;
+        blur += fo;
+    }
     const orb_keypoint kp = kps[k];
     unsigned long long* out = reinterpret_cast<unsigned long long*>(desc + (long long)k * 32);
     if (keep && !keep[k]) {
@@ -608,10 +666,12 @@ struct Bird {
     uint8_t *d_pyr = nullptr, *d_mpyr = nullptr, *d_score = nullptr, *d_blur = nullptr;
     int *d_rowcnt = nullptr, *d_rowoff = nullptr, *d_lvlcnt = nullptr;
     BirdCand* d_cand = nullptr;
-    size_t cand_cap = 0;
+    size_t cand_cap = 0;            // allocated candidates (>= cand_slot * nb_cap)
+    size_t cand_slot = 0;           // candidates per frame of this geometry (the NMS bound)
     size_t cand_guess = 16384;      // candidates downloaded with the counts (next frame: this one's + 1/8)
     orb_keypoint* d_kps = nullptr;
     int* d_keep = nullptr;
+    int* d_kframe = nullptr;        // batch: frame of each keypoint
     uint8_t* d_desc = nullptr;
     size_t kp_cap = 0;
     float* d_pts = nullptr;
@@ -619,21 +679,35 @@ struct Bird {
     void* h_pin = nullptr;
     size_t pin_cap = 0;
 
+    // batch form: the pyramid, score, blur and row-count buffers hold nb_cap frames fpitch() bytes (or nr + 1
+    // counts) apart, the mask pyramid mnb_cap frames; the single calls use frame 0
+    int nb_cap = 0, mnb_cap = 0;
+    int batch_group = 4;            // frames whose keypoints go up in one upload + angle / subpix / desc launch
+                                    // (measured, DESIGN 5.2: 2 .. 8 are within 5 % of each other, 1 and 64 lose more)
+    void *h_up = nullptr, *h_res = nullptr;   // pinned: keypoint uploads (device layout), second download / results
+    size_t up_cap = 0, res_cap = 0;
+    unsigned fpitch() const { return (unsigned)pyr_bytes; }
+
     // last detect (debug view): candidates per level
     std::vector<BirdCand> last_cands;
     std::vector<int> last_lvlcnt;
 
     ~Bird();
     void free_geom();
-    int ensure_geometry(int W, int H, int nl);
+    int ensure_geometry(int W, int H, int nl, int nb = 1);
+    int ensure_mask_frames(int n);
     int ensure_kp(size_t n);
     int ensure_pin(size_t bytes);
-    int upload(const uint8_t* img, size_t stride, const uint8_t* mask, size_t mstride, bool footprint, bool device_src);
-    int build_pyramid(int nl, bool with_mask);
+    int ensure_pinned(void*& p, size_t& cap, size_t bytes);
+    int upload(const uint8_t* img, size_t stride, const uint8_t* mask, size_t mstride, bool footprint, bool device_src,
+               int frame = 0, int mask_frame = 0);
+    int build_pyramid(int nl, bool with_mask, int nframes = 1, int nmasks = 1);
+    int launch_candidates(bool with_mask, int nframes, bool per_frame_mask);
+    void select(const BirdCand* cands, const int* lvlcnt, std::vector<HostKP>& sel) const;
     int detect_select(bool with_mask, std::vector<HostKP>& sel, int blur_levels);
     int launch_angle(int n);
     int launch_subpix(int n, bool keep);
-    int launch_blur(int nl);
+    int launch_blur(int nl, int nframes = 1);
     int launch_desc(int n, bool keep);
 };
 
@@ -648,22 +722,27 @@ void Bird::free_geom() {
     d_pyr = d_mpyr = d_score = d_blur = nullptr;
     d_rowcnt = d_rowoff = d_lvlcnt = nullptr;
     have_geom = false;
+    nb_cap = mnb_cap = 0;
 }
 
 Bird::~Bird() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     free_geom();
-    for (void* p : {(void*)d_pattern, (void*)d_wmask, (void*)d_cand, (void*)d_kps, (void*)d_keep, (void*)d_desc,
-                    (void*)d_pts})
+    for (void* p : {(void*)d_pattern, (void*)d_wmask, (void*)d_cand, (void*)d_kps, (void*)d_keep, (void*)d_kframe,
+                    (void*)d_desc, (void*)d_pts})
         if (p) (void)hipFree(p);
-    if (h_pin) (void)hipHostFree(h_pin);
+    for (void* p : {h_pin, h_up, h_res})
+        if (p) (void)hipHostFree(p);
     if (stream) (void)hipStreamDestroy(stream);
 }
 
-// orb.cpp detectAndCompute: level sizes cvRound(cols / getScale(level)); nfeaturesPerLevel
-int Bird::ensure_geometry(int W, int H, int nl) {
-    if (have_geom && g.W == W && g.H == H && g.nlevels == nl) return ORB_OK;
+// orb.cpp detectAndCompute: level sizes cvRound(cols / getScale(level)); nfeaturesPerLevel.  nb: frames
+// the buffers must hold; a geometry keeps the largest batch it has seen.
+int Bird::ensure_geometry(int W, int H, int nl, int nb) {
+    const bool same = have_geom && g.W == W && g.H == H && g.nlevels == nl;
+    if (same && nb <= nb_cap) return ORB_OK;
+    if (same) nb = std::max(nb, nb_cap);
     hipError_t e;
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return set_error("sync", e), ORB_ERR_HIP;
     free_geom();
@@ -746,6 +825,8 @@ int Bird::ensure_geometry(int W, int H, int nl) {
     if (edge < 4) return set_error("edgeThreshold < 4 is not supported", hipSuccess), ORB_ERR_ARG;
     lvl_row0[nl] = (int)crows.size();
     brow0[nl] = (int)brows.size();
+    // frame f of a batch is addressed as base + f * pyr_bytes with 32-bit level offsets
+    if (off >= (1ll << 31)) return set_error("birdview image too large", hipSuccess), ORB_ERR_GEOMETRY;
     pyr_bytes = off;
     g = G;
     std::vector<int2> rows(frows);
@@ -758,21 +839,22 @@ int Bird::ensure_geometry(int W, int H, int nl) {
         (e = hipMalloc((void**)&d_rows, std::max<size_t>(rows.size(), 1) * sizeof(int2))) != hipSuccess ||
         (e = hipMalloc((void**)&d_lvlrow0, (nl + 1) * sizeof(int))) != hipSuccess ||
         (e = hipMalloc((void**)&d_rcoef, std::max<size_t>(coefs.size(), 1) * sizeof(ResizeCoef))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_pyr, pyr_bytes)) != hipSuccess ||
+        (e = hipMalloc((void**)&d_pyr, (size_t)pyr_bytes * nb)) != hipSuccess ||
         (e = hipMalloc((void**)&d_mpyr, pyr_bytes)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_score, pyr_bytes)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_blur, pyr_bytes)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_rowcnt, (nr + 1) * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_rowoff, (nr + 1) * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_lvlcnt, kBirdMaxLevels * sizeof(int))) != hipSuccess)
+        (e = hipMalloc((void**)&d_score, (size_t)pyr_bytes * nb)) != hipSuccess ||
+        (e = hipMalloc((void**)&d_blur, (size_t)pyr_bytes * nb)) != hipSuccess ||
+        (e = hipMalloc((void**)&d_rowcnt, (nr + 1) * nb * sizeof(int))) != hipSuccess ||
+        (e = hipMalloc((void**)&d_rowoff, (nr + 1) * nb * sizeof(int))) != hipSuccess ||
+        (e = hipMalloc((void**)&d_lvlcnt, (size_t)kBirdMaxLevels * nb * sizeof(int))) != hipSuccess)
         return free_geom(), set_error("birdview buffers", e), ORB_ERR_NOMEM;
-    if (ccap > cand_cap) {
+    cand_slot = ccap;
+    if (ccap * nb > cand_cap) {
         if (d_cand) (void)hipFree(d_cand);
         d_cand = nullptr;
         cand_cap = 0;
-        if ((e = hipMalloc((void**)&d_cand, ccap * sizeof(BirdCand))) != hipSuccess)
+        if ((e = hipMalloc((void**)&d_cand, ccap * nb * sizeof(BirdCand))) != hipSuccess)
             return free_geom(), set_error("birdview candidates", e), ORB_ERR_NOMEM;
-        cand_cap = ccap;
+        cand_cap = ccap * nb;
     }
     if ((e = hipMemcpyAsync(d_geom, &g, sizeof(BirdGeom), hipMemcpyHostToDevice, stream)) != hipSuccess ||
         (!rows.empty() &&
@@ -785,38 +867,61 @@ int Bird::ensure_geometry(int W, int H, int nl) {
         (e = hipStreamSynchronize(stream)) != hipSuccess)
         return free_geom(), set_error("birdview geometry upload", e), ORB_ERR_HIP;
     have_geom = true;
+    nb_cap = nb;
+    mnb_cap = 1;
     return ORB_OK;
 }
 
+// per-frame masks: one mask pyramid per frame (a shared mask needs the one ensure_geometry allocates)
+int Bird::ensure_mask_frames(int n) {
+    if (n <= mnb_cap) return ORB_OK;
+    hipError_t e;
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return set_error("sync", e), ORB_ERR_HIP;
+    if (d_mpyr) (void)hipFree(d_mpyr);
+    d_mpyr = nullptr;
+    mnb_cap = 0;
+    if ((e = hipMalloc((void**)&d_mpyr, (size_t)pyr_bytes * n)) != hipSuccess) {
+        // the geometry cannot stay without its mask pyramid
+        return free_geom(), set_error("birdview mask pyramids", e), ORB_ERR_NOMEM;
+    }
+    mnb_cap = n;
+    return ORB_OK;
+}
+
+// nothing may be in flight on the keypoint buffers when they grow
 int Bird::ensure_kp(size_t n) {
     if (n <= kp_cap && d_kps) return ORB_OK;
     size_t cap = std::max<size_t>(n, 4096);
-    for (void* p : {(void*)d_kps, (void*)d_keep, (void*)d_desc})
+    for (void* p : {(void*)d_kps, (void*)d_keep, (void*)d_kframe, (void*)d_desc})
         if (p) (void)hipFree(p);
     d_kps = nullptr;
     d_keep = nullptr;
+    d_kframe = nullptr;
     d_desc = nullptr;
     kp_cap = 0;
     hipError_t e;
     if ((e = hipMalloc((void**)&d_kps, cap * sizeof(orb_keypoint))) != hipSuccess ||
         (e = hipMalloc((void**)&d_keep, cap * sizeof(int))) != hipSuccess ||
+        (e = hipMalloc((void**)&d_kframe, cap * sizeof(int))) != hipSuccess ||
         (e = hipMalloc((void**)&d_desc, cap * 32)) != hipSuccess)
         return set_error("birdview keypoint buffers", e), ORB_ERR_NOMEM;
     kp_cap = cap;
     return ORB_OK;
 }
 
-int Bird::ensure_pin(size_t bytes) {
-    if (bytes <= pin_cap && h_pin) return ORB_OK;
-    if (h_pin) (void)hipHostFree(h_pin);
-    h_pin = nullptr;
-    pin_cap = 0;
+int Bird::ensure_pinned(void*& p, size_t& pcap, size_t bytes) {
+    if (bytes <= pcap && p) return ORB_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    pcap = 0;
     size_t cap = std::max<size_t>(bytes, 1 << 20);
-    hipError_t e = hipHostMalloc(&h_pin, cap);
+    hipError_t e = hipHostMalloc(&p, cap);
     if (e != hipSuccess) return set_error("pinned staging", e), ORB_ERR_NOMEM;
-    pin_cap = cap;
+    pcap = cap;
     return ORB_OK;
 }
+
+int Bird::ensure_pin(size_t bytes) { return ensure_pinned(h_pin, pin_cap, bytes); }
 
 // Frame.cc:320-327 footprint rectangle (doubles truncated into cv::Rect, filled, clipped)
 static void footprint_rect(int W, int H, int& x0, int& y0, int& x1, int& y1) {
@@ -834,21 +939,24 @@ static void footprint_rect(int W, int H, int& x0, int& y0, int& x1, int& y1) {
     y1 = std::min(ry + rh, H);
 }
 
+// img (may be NULL: mask only) into level 0 of pyramid `frame`, mask into level 0 of mask pyramid `mask_frame`
 int Bird::upload(const uint8_t* img, size_t stride, const uint8_t* mask, size_t mstride, bool footprint,
-                 bool device_src) {
+                 bool device_src, int frame, int mask_frame) {
     const hipMemcpyKind kind = device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const BirdLevel& L0 = g.L[0];
     hipError_t e;
-    if ((e = hipMemcpy2DAsync(d_pyr + L0.off, L0.pitch, img, stride, L0.w, L0.h, kind, stream)) != hipSuccess)
+    if (img && (e = hipMemcpy2DAsync(d_pyr + (size_t)frame * pyr_bytes + L0.off, L0.pitch, img, stride, L0.w, L0.h, kind,
+                                     stream)) != hipSuccess)
         return set_error("birdview image upload", e), ORB_ERR_HIP;
     if (mask) {
-        if ((e = hipMemcpy2DAsync(d_mpyr + L0.off, L0.pitch, mask, mstride, L0.w, L0.h, kind, stream)) != hipSuccess)
+        uint8_t* m0 = d_mpyr + (size_t)mask_frame * pyr_bytes + L0.off;
+        if ((e = hipMemcpy2DAsync(m0, L0.pitch, mask, mstride, L0.w, L0.h, kind, stream)) != hipSuccess)
             return set_error("birdview mask upload", e), ORB_ERR_HIP;
         if (footprint) {
             int x0, y0, x1, y1;
             footprint_rect(L0.w, L0.h, x0, y0, x1, y1);
             if (x1 > x0 && y1 > y0 &&
-                (e = hipMemset2DAsync(d_mpyr + L0.off + (long long)y0 * L0.pitch + x0, L0.pitch, 0, x1 - x0, y1 - y0,
+                (e = hipMemset2DAsync(m0 + (long long)y0 * L0.pitch + x0, L0.pitch, 0, x1 - x0, y1 - y0,
                                       stream)) != hipSuccess)
                 return set_error("footprint", e), ORB_ERR_HIP;
         }
@@ -856,13 +964,37 @@ int Bird::upload(const uint8_t* img, size_t stride, const uint8_t* mask, size_t 
     return ORB_OK;
 }
 
-int Bird::build_pyramid(int nl, bool with_mask) {
+// one launch per level: nframes image pyramids and, with a mask, nmasks (1: shared, or nframes) mask pyramids
+int Bird::build_pyramid(int nl, bool with_mask, int nframes, int nmasks) {
     for (int l = 1; l < nl; l++) {
-        dim3 grid((g.L[l].w + 255) / 256, g.L[l].h, with_mask ? 2 : 1);
-        hipLaunchKernelGGL(k_bird_resize, grid, dim3(256), 0, stream, d_geom, l, d_rcoef + rcoef_off[l], d_pyr, d_mpyr);
+        dim3 grid((g.L[l].w + 255) / 256, g.L[l].h, nframes + (with_mask ? nmasks : 0));
+        hipLaunchKernelGGL(k_bird_resize, grid, dim3(256), 0, stream, d_geom, l, d_rcoef + rcoef_off[l], d_pyr, d_mpyr,
+                           nframes, fpitch());
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error("k_bird_resize", e), ORB_ERR_HIP;
+    return ORB_OK;
+}
+
+// FAST score map, count / scan / emit for nframes frames (crows is not empty)
+int Bird::launch_candidates(bool with_mask, int nframes, bool per_frame_mask) {
+    const int nl = g.nlevels;
+    const int nf = (int)frows.size(), nc = (int)crows.size();
+    const int2* d_frows = d_rows;
+    const int2* d_crows = d_rows + nf;
+    const int fx = (max_w - 2 * edge + 2 + 255) / 256;
+    const unsigned fp = fpitch(), mfp = per_frame_mask ? fp : 0u, slot = (unsigned)cand_slot;
+    hipLaunchKernelGGL(k_bird_fast, dim3(std::max(fx, 1), nf, nframes), dim3(256), 0, stream, d_geom, d_frows, d_pyr,
+                       d_score, fp);
+    const uint8_t* mp = with_mask ? d_mpyr : nullptr;
+    hipLaunchKernelGGL(k_bird_cands<0>, dim3((nc + 3) / 4, nframes), dim3(256), 0, stream, d_geom, d_crows, nc, d_pyr,
+                       mp, d_score, d_rowcnt, (const int*)nullptr, (BirdCand*)nullptr, fp, mfp, slot);
+    hipLaunchKernelGGL(k_bird_scan, dim3(nframes), dim3(1024), 0, stream, d_rowcnt, nc, d_lvlrow0, nl, d_rowoff,
+                       d_lvlcnt);
+    hipLaunchKernelGGL(k_bird_cands<1>, dim3((nc + 3) / 4, nframes), dim3(256), 0, stream, d_geom, d_crows, nc, d_pyr,
+                       mp, d_score, (int*)nullptr, d_rowoff, d_cand, fp, mfp, slot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error("birdview FAST", e), ORB_ERR_HIP;
     return ORB_OK;
 }
 
@@ -871,25 +1003,13 @@ int Bird::build_pyramid(int nl, bool with_mask) {
 int Bird::detect_select(bool with_mask, std::vector<HostKP>& sel, int blur_levels) {
     sel.clear();
     const int nl = g.nlevels;
-    const int nf = (int)frows.size(), nc = (int)crows.size();
+    const int nc = (int)crows.size();
     hipError_t e;
     last_lvlcnt.assign(nl, 0);
     last_cands.clear();
     if (nc > 0) {
-        const int2* d_frows = d_rows;
-        const int2* d_crows = d_rows + nf;
-        const int fx = (max_w - 2 * edge + 2 + 255) / 256;
-        hipLaunchKernelGGL(k_bird_fast, dim3(std::max(fx, 1), nf), dim3(256), 0, stream, d_geom, d_frows, d_pyr,
-                           d_score);
-        const uint8_t* mp = with_mask ? d_mpyr : nullptr;
-        hipLaunchKernelGGL(k_bird_cands<0>, dim3((nc + 3) / 4), dim3(256), 0, stream, d_geom, d_crows, nc, d_pyr, mp,
-                           d_score, d_rowcnt, (const int*)nullptr, (BirdCand*)nullptr);
-        hipLaunchKernelGGL(k_bird_scan, dim3(1), dim3(1024), 0, stream, d_rowcnt, nc, d_lvlrow0, nl, d_rowoff,
-                           d_lvlcnt);
-        hipLaunchKernelGGL(k_bird_cands<1>, dim3((nc + 3) / 4), dim3(256), 0, stream, d_geom, d_crows, nc, d_pyr, mp,
-                           d_score, (int*)nullptr, d_rowoff, d_cand);
-        if ((e = hipGetLastError()) != hipSuccess) return set_error("birdview FAST", e), ORB_ERR_HIP;
         int r;
+        if ((r = launch_candidates(with_mask, 1, false)) != ORB_OK) return r;
         // the blurred pyramid only needs the pyramid: it runs while the host selects
         if (blur_levels > 0 && (r = launch_blur(blur_levels)) != ORB_OK) return r;
         // one download of the level counts and a speculative prefix of the candidates (sized from the
@@ -905,7 +1025,7 @@ int Bird::detect_select(bool with_mask, std::vector<HostKP>& sel, int blur_level
         std::memcpy(last_lvlcnt.data(), hp, nl * sizeof(int));
         size_t total = 0;
         for (int l = 0; l < nl; l++) total += last_lvlcnt[l];
-        if (total > cand_cap) return set_error("birdview candidate overflow", hipSuccess), ORB_ERR_INTERNAL;
+        if (total > cand_slot) return set_error("birdview candidate overflow", hipSuccess), ORB_ERR_INTERNAL;
         last_cands.resize(total);
         std::memcpy(last_cands.data(), hp + hdr, std::min(total, guess) * sizeof(BirdCand));
         if (total > guess) {
@@ -922,35 +1042,42 @@ int Bird::detect_select(bool with_mask, std::vector<HostKP>& sel, int blur_level
         int r;
         if ((r = launch_blur(blur_levels)) != ORB_OK) return r;
     }
-    // KeyPointsFilter::retainBest(2 N) on the FAST response, per level; then Harris, retainBest(N).
-    // nth_element / partition see only the responses, so they run on 8-byte (response, candidate)
-    // keys: the resulting arrangement is the one a vector<cv::KeyPoint> gets.
+    select(last_cands.data(), last_lvlcnt.data(), sel);
+    return ORB_OK;
+}
+
+// KeyPointsFilter::retainBest(2 N) on the FAST response, per level; then Harris, retainBest(N).
+// nth_element / partition see only the responses, so they run on 8-byte (response, candidate)
+// keys: the resulting arrangement is the one a vector<cv::KeyPoint> gets.
+void Bird::select(const BirdCand* cands, const int* lvlcnt, std::vector<HostKP>& sel) const {
+    const int nl = g.nlevels;
     std::vector<std::vector<SelKey>> lv(nl);
     size_t off = 0;
     for (int l = 0; l < nl; l++) {
         auto& k = lv[l];
-        k.resize(last_lvlcnt[l]);
-        for (int i = 0; i < last_lvlcnt[l]; i++) k[i] = {(float)last_cands[off + i].score, (int)(off + i)};
-        off += last_lvlcnt[l];
+        k.resize(lvlcnt[l]);
+        for (int i = 0; i < lvlcnt[l]; i++) k[i] = {(float)cands[off + i].score, (int)(off + i)};
+        off += lvlcnt[l];
         retain_best(k, 2 * g.L[l].nfeat);
     }
     size_t any = 0;
     for (int l = 0; l < nl; l++) any += lv[l].size();
-    if (!any) return ORB_OK;
+    if (!any) return;
     for (int l = 0; l < nl; l++) {
-        for (auto& kp : lv[l]) kp.response = last_cands[kp.cand].harris;
+        for (auto& kp : lv[l]) kp.response = cands[kp.cand].harris;
         retain_best(lv[l], g.L[l].nfeat);
         const float size = 31 * g.L[l].scale;
         for (const auto& kp : lv[l]) {
-            const BirdCand& c = last_cands[kp.cand];
+            const BirdCand& c = cands[kp.cand];
             sel.push_back({(float)(c.xy & 0xFFFF), (float)(c.xy >> 16), size, -1.f, kp.response, l, -1, kp.cand});
         }
     }
-    return ORB_OK;
 }
 
 int Bird::launch_angle(int n) {
-    if (n) hipLaunchKernelGGL(k_bird_angle, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom, d_pyr, d_kps, n);
+    if (n)
+        hipLaunchKernelGGL(k_bird_angle, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom, d_pyr, d_kps, n,
+                           (const int*)nullptr, 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_angle", e), ORB_ERR_HIP);
 }
@@ -959,15 +1086,18 @@ int Bird::launch_subpix(int n, bool keep) {
     SubpixSrc s{d_pyr + g.L[0].off, g.L[0].pitch, g.L[0].w, g.L[0].h};
     if (n)
         hipLaunchKernelGGL(k_bird_subpix, dim3((n + 3) / 4), dim3(256), 0, stream, s, d_wmask,
-                           reinterpret_cast<float*>(d_kps), 7, n, 40, 0.001 * 0.001, edge, keep ? d_keep : nullptr);
+                           reinterpret_cast<float*>(d_kps), 7, n, 40, 0.001 * 0.001, edge, keep ? d_keep : nullptr,
+                           (const int*)nullptr, 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_subpix", e), ORB_ERR_HIP);
 }
 
-int Bird::launch_blur(int nl) {
+int Bird::launch_blur(int nl, int nframes) {
     const int2* d_brows = d_rows + frows.size() + crows.size();
     const int nb = brow0[nl];
-    if (nb) hipLaunchKernelGGL(k_bird_blur, dim3((max_w + 255) / 256, nb), dim3(256), 0, stream, d_geom, d_brows, d_pyr, d_blur);
+    if (nb)
+        hipLaunchKernelGGL(k_bird_blur, dim3((max_w + 255) / 256, nb, nframes), dim3(256), 0, stream, d_geom, d_brows,
+                           d_pyr, d_blur, fpitch());
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_blur", e), ORB_ERR_HIP);
 }
@@ -975,7 +1105,7 @@ int Bird::launch_blur(int nl) {
 int Bird::launch_desc(int n, bool keep) {
     if (n)
         hipLaunchKernelGGL(k_bird_desc, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom, d_pyr, d_blur, d_pattern, d_kps,
-                           keep ? d_keep : nullptr, n, d_desc);
+                           keep ? d_keep : nullptr, n, d_desc, (const int*)nullptr, 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_desc", e), ORB_ERR_HIP);
 }
@@ -1164,6 +1294,278 @@ extern "C" int orb_bird_extract_device(orb_bird* b, const uint8_t* d_img, int w,
     return bird_extract(b, d_img, w, h, stride, d_mask, mask_stride, kps, cap, n, desc, true);
 }
 
+/* ---------------- batch form: nframes images of one size through the chain in one call -----------------
+ * Every stage before the selection is one launch over all frames; the selection runs frame by frame on
+ * the host, and the keypoints of each group of batch_group frames go up and through angle / subpix / desc
+ * while the host selects the next group.  One synchronise for the candidates, one at the end. */
+namespace {
+
+struct BatchFrame {   // keypoints [off, off + ns) of the device buffers are this frame's selection
+    int frame, off, ns;
+};
+
+}  // namespace
+
+// download everything launched so far; compact each frame by its keep flags into the caller's slot
+static int bird_batch_flush(orb_bird* b, std::vector<BatchFrame>& done, int used, orb_keypoint* kps, uint8_t* desc,
+                            int cap, int* counts, bool& over) {
+    int r;
+    hipError_t e;
+    const size_t kb = (size_t)used * sizeof(orb_keypoint), fb = (size_t)used * sizeof(int), db = (size_t)used * 32;
+    if ((r = b->ensure_pinned(b->h_res, b->res_cap, kb + fb + db + 64)) != ORB_OK) return r;
+    uint8_t* hp = (uint8_t*)b->h_res;
+    if (used && ((e = hipMemcpyAsync(hp, b->d_kps, kb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+                 (e = hipMemcpyAsync(hp + kb, b->d_keep, fb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+                 (e = hipMemcpyAsync(hp + kb + fb, b->d_desc, db, hipMemcpyDeviceToHost, b->stream)) != hipSuccess))
+        return set_error("birdview result download", e), ORB_ERR_HIP;
+    if ((e = hipStreamSynchronize(b->stream)) != hipSuccess) return set_error("birdview sync", e), ORB_ERR_HIP;
+    const orb_keypoint* rk = (const orb_keypoint*)hp;
+    const int* keep = (const int*)(hp + kb);
+    const uint8_t* rd = hp + kb + fb;
+    for (const BatchFrame& q : done) {
+        int m = 0;
+        for (int i = q.off; i < q.off + q.ns; i++) m += keep[i] != 0;
+        counts[q.frame] = m;
+        if (m > cap) {   // this frame's slot stays untouched
+            over = true;
+            continue;
+        }
+        orb_keypoint* ok = kps + (size_t)q.frame * cap;
+        uint8_t* od = desc + (size_t)q.frame * cap * 32;
+        for (int i = q.off, j = 0; i < q.off + q.ns; i++)
+            if (keep[i]) {
+                ok[j] = rk[i];
+                std::memcpy(od + (size_t)j * 32, rd + (size_t)i * 32, 32);
+                j++;
+            }
+    }
+    done.clear();
+    return ORB_OK;
+}
+
+// the frames (and nmasks = 0, 1 or B footprint-zeroed masks) are in the level-0 slots
+static int bird_batch_run(orb_bird* b, int B, int nmasks, orb_keypoint* kps, uint8_t* desc, int cap, int* counts) {
+    int r;
+    hipError_t e;
+    const int nl = b->g.nlevels, nc = (int)b->crows.size();
+    const bool with_mask = nmasks > 0;
+    if ((r = b->build_pyramid(nl, with_mask, B, std::max(nmasks, 1))) != ORB_OK) return r;
+    b->last_lvlcnt.clear();   // the debug views describe single calls only
+    b->last_cands.clear();
+    std::vector<const BirdCand*> cands(B, nullptr);
+    std::vector<int> lvl((size_t)B * kBirdMaxLevels, 0);
+    std::vector<std::vector<BirdCand>> big;   // frames whose candidates exceed the speculative prefix
+    if (nc > 0) {
+        if ((r = b->launch_candidates(with_mask, B, nmasks > 1)) != ORB_OK) return r;
+        // the blurred pyramids only need the pyramids: they run while the host selects
+        if ((r = b->launch_blur(nl, B)) != ORB_OK) return r;
+        // one download of every frame's level counts and speculative candidate prefix, one synchronise;
+        // a second download only for the frames that have more
+        const size_t slot = b->cand_slot, guess = std::min(b->cand_guess, slot);
+        const size_t hdr = ((size_t)B * kBirdMaxLevels * sizeof(int) + 63) & ~(size_t)63;
+        if ((r = b->ensure_pin(hdr + (size_t)B * guess * sizeof(BirdCand))) != ORB_OK) return r;
+        uint8_t* hp = (uint8_t*)b->h_pin;
+        if ((e = hipMemcpyAsync(hp, b->d_lvlcnt, (size_t)B * kBirdMaxLevels * sizeof(int), hipMemcpyDeviceToHost,
+                                b->stream)) != hipSuccess)
+            return set_error("birdview count download", e), ORB_ERR_HIP;
+        const BirdCand* pre = (const BirdCand*)(hp + hdr);
+        for (int f = 0; f < B && guess; f++)
+            if ((e = hipMemcpyAsync((void*)(pre + f * guess), b->d_cand + f * slot, guess * sizeof(BirdCand),
+                                    hipMemcpyDeviceToHost, b->stream)) != hipSuccess)
+                return set_error("birdview candidate download", e), ORB_ERR_HIP;
+        if ((e = hipStreamSynchronize(b->stream)) != hipSuccess)
+            return set_error("birdview candidate download", e), ORB_ERR_HIP;
+        std::vector<size_t> total(B, 0);
+        size_t rest_total = 0, max_total = 0;
+        for (int f = 0; f < B; f++) {
+            for (int l = 0; l < nl; l++) {
+                lvl[(size_t)f * kBirdMaxLevels + l] = ((const int*)hp)[f * kBirdMaxLevels + l];
+                total[f] += lvl[(size_t)f * kBirdMaxLevels + l];
+            }
+            if (total[f] > slot) return set_error("birdview candidate overflow", hipSuccess), ORB_ERR_INTERNAL;
+            cands[f] = pre + f * guess;
+            if (total[f] > guess) rest_total += total[f] - guess;
+            max_total = std::max(max_total, total[f]);
+        }
+        if (rest_total) {
+            if ((r = b->ensure_pinned(b->h_res, b->res_cap, rest_total * sizeof(BirdCand))) != ORB_OK) return r;
+            BirdCand* hr = (BirdCand*)b->h_res;
+            size_t ro = 0;
+            for (int f = 0; f < B; f++)
+                if (total[f] > guess) {
+                    const size_t rest = total[f] - guess;
+                    if ((e = hipMemcpyAsync(hr + ro, b->d_cand + f * slot + guess, rest * sizeof(BirdCand),
+                                            hipMemcpyDeviceToHost, b->stream)) != hipSuccess)
+                        return set_error("birdview candidates download", e), ORB_ERR_HIP;
+                    ro += rest;
+                }
+            if ((e = hipStreamSynchronize(b->stream)) != hipSuccess)
+                return set_error("birdview candidates download", e), ORB_ERR_HIP;
+            big.resize(B);
+            ro = 0;
+            for (int f = 0; f < B; f++)
+                if (total[f] > guess) {
+                    const size_t rest = total[f] - guess;
+                    big[f].resize(total[f]);
+                    std::memcpy(big[f].data(), pre + f * guess, guess * sizeof(BirdCand));
+                    std::memcpy(big[f].data() + guess, hr + ro, rest * sizeof(BirdCand));
+                    ro += rest;
+                    cands[f] = big[f].data();
+                }
+        }
+        b->cand_guess = max_total + max_total / 8 + 256;
+    } else if ((r = b->launch_blur(nl, B)) != ORB_OK) {
+        return r;
+    }
+
+    // selection frame by frame; each full group goes up and through its kernels behind the host
+    orb_keypoint* up_k = (orb_keypoint*)b->h_up;
+    int* up_f = (int*)((uint8_t*)b->h_up + b->kp_cap * sizeof(orb_keypoint));
+    std::vector<BatchFrame> done;
+    std::vector<HostKP> sel;
+    int used = 0, g0 = 0, gframes = 0;
+    bool over = false;
+    const unsigned fp = b->fpitch();
+    const BirdLevel L0 = b->g.L[0];
+    auto launch_group = [&]() -> int {
+        const int n = used - g0;
+        if (n) {
+            hipError_t le;
+            if ((le = hipMemcpyAsync(b->d_kps + g0, up_k + g0, (size_t)n * sizeof(orb_keypoint), hipMemcpyHostToDevice,
+                                     b->stream)) != hipSuccess ||
+                (le = hipMemcpyAsync(b->d_kframe + g0, up_f + g0, (size_t)n * sizeof(int), hipMemcpyHostToDevice,
+                                     b->stream)) != hipSuccess)
+                return set_error("birdview keypoint upload", le), ORB_ERR_HIP;
+            const dim3 grid((n + 3) / 4), block(256);
+            const int* kf = b->d_kframe + g0;
+            hipLaunchKernelGGL(k_bird_angle, grid, block, 0, b->stream, b->d_geom, b->d_pyr, b->d_kps + g0, n, kf, fp);
+            SubpixSrc s{b->d_pyr + L0.off, L0.pitch, L0.w, L0.h};
+            hipLaunchKernelGGL(k_bird_subpix, grid, block, 0, b->stream, s, b->d_wmask,
+                               reinterpret_cast<float*>(b->d_kps + g0), 7, n, 40, 0.001 * 0.001, b->edge, b->d_keep + g0,
+                               kf, fp);
+            hipLaunchKernelGGL(k_bird_desc, grid, block, 0, b->stream, b->d_geom, b->d_pyr, b->d_blur, b->d_pattern,
+                               b->d_kps + g0, b->d_keep + g0, n, b->d_desc + (size_t)g0 * 32, kf, fp);
+            if ((le = hipGetLastError()) != hipSuccess) return set_error("birdview keypoint kernels", le), ORB_ERR_HIP;
+        }
+        g0 = used;
+        gframes = 0;
+        return ORB_OK;
+    };
+    for (int f = 0; f < B; f++) {
+        sel.clear();
+        if (cands[f]) b->select(cands[f], &lvl[(size_t)f * kBirdMaxLevels], sel);
+        const int ns = (int)sel.size();
+        if ((size_t)used + ns > b->kp_cap) {
+            // boundary ties kept more than nfeatures per frame: drain what is in flight, then grow if needed
+            if ((r = launch_group()) != ORB_OK ||
+                (r = bird_batch_flush(b, done, used, kps, desc, cap, counts, over)) != ORB_OK)
+                return r;
+            used = g0 = 0;
+            if ((r = b->ensure_kp(ns)) != ORB_OK ||
+                (r = b->ensure_pinned(b->h_up, b->up_cap, b->kp_cap * (sizeof(orb_keypoint) + sizeof(int)))) != ORB_OK)
+                return r;
+            up_k = (orb_keypoint*)b->h_up;
+            up_f = (int*)((uint8_t*)b->h_up + b->kp_cap * sizeof(orb_keypoint));
+        }
+        for (int i = 0; i < ns; i++) {
+            to_kp(sel[i], up_k[used + i]);
+            up_f[used + i] = f;
+        }
+        done.push_back({f, used, ns});
+        used += ns;
+        if (++gframes >= b->batch_group && (r = launch_group()) != ORB_OK) return r;
+    }
+    if ((r = launch_group()) != ORB_OK) return r;
+    if ((r = bird_batch_flush(b, done, used, kps, desc, cap, counts, over)) != ORB_OK) return r;
+    if (over) return set_error("orb_bird_extract_batch: capacity", hipSuccess), ORB_ERR_CAPACITY;
+    return ORB_OK;
+}
+
+// argument rules shared by the two batch forms; *done: the call is complete (nothing to do)
+static int bird_batch_enter(orb_bird* b, int nframes, const void* imgs, int w, int h, size_t stride, size_t frame_pitch,
+                            bool with_mask, size_t mask_stride, size_t mask_frame_pitch, const orb_keypoint* kps,
+                            const uint8_t* desc, int cap, int* counts, bool* done) {
+    *done = true;
+    if (!b) return set_error("NULL orb_bird", hipSuccess), ORB_ERR_ARG;
+    if (nframes < 0 || nframes > ORB_BIRD_MAX_BATCH || !counts || cap < 0 || (cap && (!kps || !desc)))
+        return set_error("orb_bird_extract_batch: bad arguments", hipSuccess), ORB_ERR_ARG;
+    if (nframes == 0) return ORB_OK;
+    if (!imgs || w <= 0 || h <= 0) {
+        for (int f = 0; f < nframes; f++) counts[f] = 0;
+        return ORB_OK;
+    }
+    if (stride < (size_t)w || frame_pitch < stride * (size_t)h ||
+        (with_mask && (mask_stride < (size_t)w || (mask_frame_pitch && mask_frame_pitch < mask_stride * (size_t)h))))
+        return set_error("orb_bird_extract_batch: bad strides", hipSuccess), ORB_ERR_ARG;
+    int r;
+    if ((r = bird_enter(b)) != ORB_OK) return r;
+    *done = false;
+    return ORB_OK;
+}
+
+// buffers for B frames of w x h with nmasks mask pyramids, keypoint buffers for the expected selection
+static int bird_batch_reserve(orb_bird* b, int B, int w, int h, int nmasks) {
+    int r;
+    if ((r = b->ensure_geometry(w, h, b->nlevels, B)) != ORB_OK) return r;
+    if ((r = b->ensure_mask_frames(nmasks)) != ORB_OK) return r;
+    if ((r = b->ensure_kp((size_t)B * ((size_t)b->nfeatures + 64))) != ORB_OK) return r;
+    return b->ensure_pinned(b->h_up, b->up_cap, b->kp_cap * (sizeof(orb_keypoint) + sizeof(int)));
+}
+
+extern "C" int orb_bird_extract_batch_device(orb_bird* b, int nframes, const uint8_t* d_imgs, int w, int h,
+                                             size_t stride, size_t frame_pitch, const uint8_t* d_masks,
+                                             size_t mask_stride, size_t mask_frame_pitch, orb_keypoint* kps,
+                                             uint8_t* desc, int cap, int* counts) {
+    int r;
+    bool done;
+    if ((r = bird_batch_enter(b, nframes, d_imgs, w, h, stride, frame_pitch, d_masks != nullptr, mask_stride,
+                              mask_frame_pitch, kps, desc, cap, counts, &done)) != ORB_OK ||
+        done)
+        return r;
+    const int nmasks = !d_masks ? 0 : (mask_frame_pitch ? nframes : 1);
+    if ((r = bird_batch_reserve(b, nframes, w, h, nmasks)) != ORB_OK) return r;
+    int x0, y0, x1, y1;
+    footprint_rect(w, h, x0, y0, x1, y1);
+    hipLaunchKernelGGL(k_bird_ingest, dim3((w + 255) / 256, h, nframes + nmasks), dim3(256), 0, b->stream, b->d_geom,
+                       d_imgs, stride, frame_pitch, d_masks, mask_stride, mask_frame_pitch, b->d_pyr, b->d_mpyr, nframes,
+                       b->fpitch(), x0, y0, x1, y1);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error("k_bird_ingest", e), ORB_ERR_HIP;
+    return bird_batch_run(b, nframes, nmasks, kps, desc, cap, counts);
+}
+
+extern "C" int orb_bird_extract_batch(orb_bird* b, int nframes, const uint8_t* const* imgs, int w, int h, size_t stride,
+                                      const uint8_t* const* masks, int nmasks, size_t mask_stride, orb_keypoint* kps,
+                                      uint8_t* desc, int cap, int* counts) {
+    int r;
+    bool done;
+    if (nframes >= 0 && nmasks != 0 && nmasks != 1 && nmasks != nframes)
+        return set_error("orb_bird_extract_batch: nmasks must be 0, 1 or nframes", hipSuccess), ORB_ERR_ARG;
+    if (nframes > 0 && nframes <= ORB_BIRD_MAX_BATCH && w > 0 && h > 0) {
+        if (nmasks && !masks) return set_error("orb_bird_extract_batch: NULL masks", hipSuccess), ORB_ERR_ARG;
+        for (int f = 0; imgs && f < nframes; f++)
+            if (!imgs[f]) return set_error("orb_bird_extract_batch: NULL image", hipSuccess), ORB_ERR_ARG;
+        for (int m = 0; m < nmasks; m++)
+            if (!masks[m]) return set_error("orb_bird_extract_batch: NULL mask", hipSuccess), ORB_ERR_ARG;
+    }
+    if ((r = bird_batch_enter(b, nframes, imgs, w, h, stride, stride * (size_t)(h > 0 ? h : 0), nmasks > 0, mask_stride, 0,
+                              kps, desc, cap, counts, &done)) != ORB_OK ||
+        done)
+        return r;
+    if ((r = bird_batch_reserve(b, nframes, w, h, nmasks)) != ORB_OK) return r;
+    for (int f = 0; f < nframes; f++)
+        if ((r = b->upload(imgs[f], stride, nullptr, 0, false, false, f, 0)) != ORB_OK) return r;
+    for (int m = 0; m < nmasks; m++)
+        if ((r = b->upload(nullptr, 0, masks[m], mask_stride, true, false, 0, m)) != ORB_OK) return r;
+    return bird_batch_run(b, nframes, nmasks, kps, desc, cap, counts);
+}
+
+extern "C" int orb_bird_batch_group(orb_bird* b, int group) {
+    if (!b) return set_error("NULL orb_bird", hipSuccess), ORB_ERR_ARG;
+    if (group > 0) b->batch_group = std::min(group, ORB_BIRD_MAX_BATCH);
+    return b->batch_group;
+}
+
 extern "C" int orb_bird_compute(orb_bird* b, const uint8_t* img, int w, int h, size_t stride, orb_keypoint* kps,
                                 int* n, uint8_t* desc) {
     int r;
@@ -1245,7 +1647,7 @@ extern "C" int orb_corner_subpix(orb_bird* b, const uint8_t* img, int w, int h, 
     if ((e = hipMemcpyAsync(b->d_pts, pts, (size_t)n * 8, hipMemcpyHostToDevice, b->stream)) != hipSuccess)
         return set_error("subpix upload", e), ORB_ERR_HIP;
     hipLaunchKernelGGL(k_bird_subpix, dim3((n + 3) / 4), dim3(256), 0, b->stream, s, b->d_wmask, b->d_pts, 2, n, iters,
-                       ep * ep, b->edge, (int*)nullptr);
+                       ep * ep, b->edge, (int*)nullptr, (const int*)nullptr, 0u);
     if ((e = hipGetLastError()) != hipSuccess ||
         (e = hipMemcpyAsync(pts, b->d_pts, (size_t)n * 8, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(b->stream)) != hipSuccess)

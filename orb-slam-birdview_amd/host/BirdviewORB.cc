@@ -102,6 +102,58 @@ void BirdviewORB::extractBirdview(const ImageView& image, const ImageView& birdv
     else descriptors.create(n);
 }
 
+void BirdviewORB::extractBirdviewBatch(const std::vector<ImageView>& images,
+                                       const std::vector<ImageView>& birdviewMasks,
+                                       std::vector<std::vector<KeyPoint>>& keypoints,
+                                       std::vector<DescriptorMat>& descriptors) {
+    const int nf = (int)images.size(), nm = (int)birdviewMasks.size();
+    keypoints.assign(nf, {});
+    descriptors.assign(nf, DescriptorMat());
+    if (nf == 0) return;
+    if (nf > ORB_BIRD_MAX_BATCH) throw OrbGpuError(ORB_ERR_ARG, "extractBirdviewBatch: more than ORB_BIRD_MAX_BATCH images");
+    if (nm != 0 && nm != 1 && nm != nf) throw OrbGpuError(ORB_ERR_ARG, "extractBirdviewBatch: 0, 1 or N masks");
+    const ImageView& i0 = images[0];
+    std::vector<const uint8_t*> ip(nf), mp(nm);
+    for (int f = 0; f < nf; f++) {
+        const ImageView& im = images[f];
+        if (im.cols != i0.cols || im.rows != i0.rows || im.step != i0.step || im.empty() != i0.empty())
+            throw OrbGpuError(ORB_ERR_ARG, "extractBirdviewBatch: images of one size and step");
+        ip[f] = im.data;
+    }
+    if (i0.empty()) return;
+    for (int m = 0; m < nm; m++) {
+        const ImageView& mk = birdviewMasks[m];
+        if (mk.empty() || mk.cols != i0.cols || mk.rows != i0.rows || mk.step != birdviewMasks[0].step)
+            throw OrbGpuError(ORB_ERR_ARG, "extractBirdviewBatch: masks of the image size and one step");
+        mp[m] = mk.data;
+    }
+    int cap = 2 * std::max(nfeatures_, 1) + 256;
+    std::vector<KeyPoint> kbuf;
+    std::vector<uint8_t> dbuf;
+    std::vector<int> counts(nf, 0);
+    for (;;) {
+        kbuf.resize((size_t)nf * cap);
+        dbuf.resize((size_t)nf * cap * 32);
+        const int st = orb_bird_extract_batch(h_, nf, ip.data(), i0.cols, i0.rows, i0.step, nm ? mp.data() : nullptr, nm,
+                                              nm ? birdviewMasks[0].step : 0, kbuf.data(), dbuf.data(), cap,
+                                              counts.data());
+        if (st == ORB_ERR_CAPACITY) {
+            cap = *std::max_element(counts.begin(), counts.end());
+            continue;
+        }
+        check(st, "orb_bird_extract_batch");
+        break;
+    }
+    for (int f = 0; f < nf; f++) {
+        const int n = counts[f];
+        keypoints[f].assign(kbuf.begin() + (size_t)f * cap, kbuf.begin() + (size_t)f * cap + n);
+        if (n == 0) continue;
+        descriptors[f].create(n);
+        std::copy(dbuf.begin() + (size_t)f * cap * 32, dbuf.begin() + ((size_t)f * cap + n) * 32,
+                  descriptors[f].buf.begin());
+    }
+}
+
 void cornerSubPix(const ImageView& image, std::vector<Point2f>& corners, Size winSize, Size zeroZone,
                   TermCriteria criteria) {
     if (zeroZone.width >= 0 && zeroZone.height >= 0)

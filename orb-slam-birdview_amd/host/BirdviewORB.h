@@ -8,7 +8,8 @@
  *     cv::cornerSubPix(mBirdviewImg, vKeysBird, Size(5,5), Size(-1,-1), criteria);   -> cornerSubPix
  *     extractorBird->compute(mBirdviewImg, mvKeysBird, mDescriptorsBird);            -> compute
  *
- * plus the fused BirdviewORB::extractBirdview, which does all of it on one device upload.  Only the
+ * plus the fused BirdviewORB::extractBirdview, which does all of it on one device upload, and
+ * extractBirdviewBatch, which does it for several frames of one size in one call.  Only the
  * configuration the reference uses is built: firstLevel 0, WTA_K 2, HARRIS_SCORE, patchSize 31,
  * cornerSubPix window (5,5) without a zero zone; other values throw OrbGpuError(ORB_ERR_ARG).
  * No CPU path: a GPU failure throws OrbGpuError.
@@ -53,6 +54,12 @@ public:
     // Frame.cc:320-342 in one call: footprint-masked detect, cornerSubPix(5x5, 40, 0.001), compute
     void extractBirdview(const ImageView& image, const ImageView& birdviewMask, std::vector<KeyPoint>& keypoints,
                          DescriptorMat& descriptors);
+
+    // extractBirdview for several queued frames of one size in one call (orb_bird_extract_batch): at most
+    // ORB_BIRD_MAX_BATCH images; birdviewMasks holds 0 (no mask), 1 (shared by all frames) or images.size()
+    // masks.  keypoints[f] / descriptors[f] are what extractBirdview returns for frame f alone.
+    void extractBirdviewBatch(const std::vector<ImageView>& images, const std::vector<ImageView>& birdviewMasks,
+                              std::vector<std::vector<KeyPoint>>& keypoints, std::vector<DescriptorMat>& descriptors);
 
     int descriptorSize() const { return 32; }
     orb_bird* handle() const { return h_; }

@@ -1077,6 +1077,60 @@ class BirdORB:
                                             ctypes.byref(n), _p(desc)), "orb_bird_extract_device")
         return kps[:n.value], desc[:n.value]
 
+    def _batch(self, n, cap, call, where):
+        """Run a batch call into fresh (n, cap) outputs; a frame that does not fit raises cap and repeats."""
+        cap = cap or 2 * max(self.params.nfeatures, 1) + 256
+        while True:
+            kps = np.zeros((max(n, 1), cap), KP_DTYPE)
+            desc = np.zeros((max(n, 1), cap, 32), np.uint8)
+            counts = np.zeros(max(n, 1), np.int32)
+            st = call(_p(kps), _p(desc), cap, _p(counts))
+            if st == -3:
+                cap = int(counts[:n].max())
+                continue
+            check(st, where)
+            return [(kps[f, :counts[f]].copy(), desc[f, :counts[f]].copy()) for f in range(n)]
+
+    def extract_batch(self, images, masks=None):
+        """Frame.cc:320-342 for a list of equally sized images in one call.  masks: None, one array shared by
+        all frames, or a list with one mask per frame.  Returns [(keypoints, descriptors)] per frame, each
+        what extract(image, mask) returns."""
+        imgs = [self._img(i) for i in images]
+        n = len(imgs)
+        if n == 0:
+            return []
+        h, w = imgs[0].shape
+        assert all(i.shape == (h, w) for i in imgs), "one size per batch"
+        if masks is None:
+            ms = []
+        elif isinstance(masks, (list, tuple)):
+            ms = [self._img(m) for m in masks]
+        else:
+            ms = [self._img(masks)]
+        assert all(m.shape == (h, w) for m in ms), "masks have the image size"
+        if imgs[0].size == 0:
+            return [(np.zeros(0, KP_DTYPE), np.zeros((0, 32), np.uint8)) for _ in imgs]
+        ip = (ctypes.c_void_p * n)(*[i.ctypes.data for i in imgs])
+        mp = (ctypes.c_void_p * max(len(ms), 1))(*[m.ctypes.data for m in ms])
+        return self._batch(n, None, lambda k, d, cap, c: lib().orb_bird_extract_batch(
+            self.h, n, ip, w, h, w, mp if ms else None, len(ms), w, k, d, cap, c), "orb_bird_extract_batch")
+
+    def extract_batch_device(self, d_imgs, n, w, h, frame_pitch=None, d_masks=None, mask_frame_pitch=0, cap=None,
+                             stride=None, mask_stride=None):
+        """Batch extract on n device-resident frames (device pointers as ints): frame f at d_imgs + f *
+        frame_pitch (default stride * h), its mask at d_masks + f * mask_frame_pitch (0: one shared mask)."""
+        stride = stride or w
+        mask_stride = mask_stride or w
+        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        return self._batch(n, cap, lambda k, d, cp, c: lib().orb_bird_extract_batch_device(
+            self.h, n, ctypes.c_void_p(d_imgs), w, h, stride, frame_pitch,
+            None if d_masks is None else ctypes.c_void_p(d_masks), mask_stride, mask_frame_pitch, k, d, cp, c),
+            "orb_bird_extract_batch_device")
+
+    def batch_group(self, group=0):
+        """Frames per post-selection group of the batch calls; group > 0 sets it.  Returns the value in force."""
+        return lib().orb_bird_batch_group(self.h, group)
+
     def debug_candidates(self, level):
         cap = 1 << 16
         while True:

@@ -142,6 +142,9 @@ SIGNATURES = {
     "orb_corner_subpix": (ci, [vp, vp, ci, ci, csz, vp, ci, ci, ci, ci, ctypes.c_double]),
     "orb_bird_extract": (ci, [vp, vp, ci, ci, csz, vp, csz, vp, ci, ctypes.POINTER(ci), vp]),
     "orb_bird_extract_device": (ci, [vp, vp, ci, ci, csz, vp, csz, vp, ci, ctypes.POINTER(ci), vp]),
+    "orb_bird_extract_batch_device": (ci, [vp, ci, vp, ci, ci, csz, csz, vp, csz, csz, vp, vp, ci, vp]),
+    "orb_bird_extract_batch": (ci, [vp, ci, vp, ci, ci, csz, vp, ci, csz, vp, vp, ci, vp]),
+    "orb_bird_batch_group": (ci, [vp, ci]),
     "orb_bird_footprint_mask": (ci, [vp, ci, ci, csz]),
     "orb_bird_debug_candidates": (ci, [vp, ci, vp, ci]),
     "orb_bird_debug_level": (ci, [vp, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
