@@ -591,6 +591,110 @@ typedef struct orb_proj_frame_target {
 } orb_proj_frame_target;
 int orb_project_best_frames(orb_ctx* ctx, int gate, int ntargets, const orb_proj_frame_target* targets);
 
+/* ======================= Resident map points: isInFrustum and Fuse's projection ======================= */
+
+/* The query side of the projection searches, kept on the device: the same map points are projected frame after frame
+ * (Tracking::SearchLocalPoints, Tracking.cc:1635-1648 -> Frame::isInFrustum, Frame.cc:436-492) and keyframe after
+ * keyframe (ORBmatcher::Fuse, ORBmatcher.cc:852-890).  A handle owns slots 0 .. capacity-1; a slot holds GetWorldPos
+ * (3 floats), GetNormal (3 floats), the raw mfMinDistance / mfMaxDistance (not the invariance values: the kernel
+ * applies 0.8f / 1.2f) and GetDescriptor (32 B).
+ *   orb_points_create    capacity >= 0 slots on ctx's device (their content is undefined until written).
+ *   orb_points_write     slots first .. first+n-1 from host arrays (pos, normal: 3 n floats; min_dist, max_dist: n;
+ *                        desc: 32 n bytes).  Synchronous.  Grows the handle when first + n > capacity (earlier slots keep
+ *                        their content; the growth waits for the device).  A point whose descriptor, position or normal
+ *                        changed (Replace, UpdateNormalAndDepth, bundle adjustment) is rewritten through this call.
+ *   orb_points_capacity  slots (0 for NULL).
+ * Lifetime and device rules are orb_frame's: usable with any context of the same device, one thread at a time, destroyed
+ * before the context that created it.  ORB_ERR_ARG before any GPU work: a negative capacity, first or n, NULL arrays
+ * with n > 0, a position, normal or distance that is not finite, first + n beyond INT_MAX. */
+typedef struct orb_points orb_points;
+int  orb_points_create(orb_ctx* ctx, int capacity, orb_points** out);
+int  orb_points_write(orb_points* points, int first, int n, const float* pos, const float* normal,
+                      const float* min_dist, const float* max_dist, const uint8_t* desc);
+int  orb_points_capacity(const orb_points* points);
+void orb_points_destroy(orb_points* points);
+
+/* The pose and intrinsics the projection reads: the Frame's / KeyFrame's own members, as floats. */
+typedef struct orb_camera {
+    float Rcw[9];                /* mRcw / GetRotation(), row-major */
+    float tcw[3];                /* mtcw / GetTranslation() */
+    float Ow[3];                 /* mOw / GetCameraCenter() */
+    float fx, fy, cx, cy, mbf;
+    float min_x, max_x, min_y, max_y;   /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+    int   nlevels;               /* mnScaleLevels */
+    float log_scale_factor;      /* mfLogScaleFactor */
+    float scale_factors[ORBGPU_MAX_LEVELS];   /* mvScaleFactors, nlevels entries read */
+} orb_camera;
+
+/* The projection of one point, in one of two forms.  Shared (DESIGN 3.2 has the pins):
+ *   Pc_i = (float)(((double)R_i0 P0 + (double)R_i1 P1 + (double)R_i2 P2) + (double)t_i)   (OpenCV's gemm, as modelled)
+ *   PO = P - Ow in float; dist = (float)sqrt(sum (double)PO_i^2); dot = sum (double)PO_i (double)n_i  (cv::norm, Mat::dot)
+ *   distance gates dist < 0.8f * min_dist, dist > 1.2f * max_dist
+ *   level = MapPoint::PredictScale (MapPoint.cc:385-417): ratio = max_dist / dist, ceil(logf(ratio) / log_scale_factor)
+ *     clamped to [0, nlevels - 1], computed on the device as the number of per-level thresholds ratio reaches; the
+ *     thresholds come from the host's own logf (a ratio that is not finite gives level 0).
+ * ORB_FRUSTUM_FRAME (Frame::isInFrustum; the search radius of SearchByProjection(Frame&, vector<MapPoint*>, th),
+ *   ORBmatcher.cc:63-69): PcZ < 0.0f rejects; invz = 1.0f / PcZ; u = fmaf(fx * PcX, invz, cx), v likewise; u < min_x ||
+ *   u > max_x (v likewise) rejects; the distance gates; view_cos = (float)(dot / (double)dist) < view_cos_limit rejects;
+ *   ur = fmaf(-mbf, invz, u); r = (view_cos > 0.998 ? 2.5f : 4.0f) [* th if th != 1.0f] * scale_factors[level].
+ * ORB_FRUSTUM_FUSE (Fuse(KeyFrame*, vector<MapPoint*>, th)): PcZ < 0.0f rejects; invz = 1 / PcZ; x = PcX * invz, y
+ *   likewise; u = fmaf(fx, x, cx), v likewise; KeyFrame::IsInImage u >= min_x && u < max_x && v >= min_y && v < max_y;
+ *   ur = fmaf(-mbf, invz, u); the distance gates; dot < 0.5 * (double)dist rejects; r = th * scale_factors[level].
+ *   view_cos_limit is not read and view_cos stays 0.
+ * verdict: 0 visible, 1 depth, 2 bounds, 3 distance, 4 angle, in the reference's order of tests, and 5: every test
+ * passed but u, v, ur or r is not finite (PcZ == 0; the reference goes on into undefined casts there: DESIGN 3.3).  A
+ * record holds what the reference had computed when it rejected; the other fields are 0 and level -1 (verdict 5 comes
+ * last: its record is complete). */
+enum { ORB_FRUSTUM_FRAME = 0, ORB_FRUSTUM_FUSE = 1 };
+enum { ORB_POINT_VISIBLE = 0, ORB_POINT_DEPTH = 1, ORB_POINT_BOUNDS = 2, ORB_POINT_DISTANCE = 3, ORB_POINT_ANGLE = 4,
+       ORB_POINT_NOT_FINITE = 5 };
+typedef struct orb_point_proj {
+    float u, v, ur, invz, dist, view_cos, r;
+    int   level, verdict;
+} orb_point_proj;
+
+/* The entry points.  ids: n slot ids, in any order, repeats allowed.  ORB_ERR_ARG before the context is touched or
+ * any output is written: a NULL handle or one of another device, negative counts, NULL arrays with non-zero counts, an
+ * id outside [0, capacity), an unknown mode, a camera field that is not finite, nlevels outside [1, ORBGPU_MAX_LEVELS],
+ * log_scale_factor <= 0, th or view_cos_limit not finite, th < 0, and everything the underlying search refuses.  n == 0
+ * or an empty frame: ORB_OK, the outputs as the underlying search leaves them, no GPU work.
+ *   orb_project_points       the projection alone: proj_out[i] for ids[i].
+ *   orb_project_points_host  the same records on the CPU from host arrays indexed by i (no context, no handle): the
+ *                            arithmetic of the kernel, for a caller that replays single points.
+ *   orb_search_local_points  Tracking::SearchLocalPoints' isInFrustum loop and SearchByProjection(Frame&,
+ *                            vector<MapPoint*>, th) in one call: the projection (FRAME), the projection top-k over the
+ *                            resident frame and the host replay, nothing of the query side staged.  The outputs equal
+ *                            orb_search_by_projection_frame(ORB_PROJ_RATIO_SAME_LEVEL, max_dist = TH_HIGH = 100) fed with
+ *                            the visible points in ids order, every query built as orbgpu.h maps that search (levels
+ *                            (level - 1, level), ur_tol = r, blocks = 1); match_t[t] holds positions in ids.  Rejected
+ *                            points stay in the launch with an empty window.  proj_out may be NULL.  The caller leaves
+ *                            out what the reference skips before isInFrustum (isBad, mnLastFrameSeen == mnId).
+ *   orb_fuse_search_points   Fuse(KeyFrame*, vector<MapPoint*>, th) for many target keyframes in one launch: per
+ *                            target the projection (FUSE) of its ids through its camera, then the search of
+ *                            orb_project_best_frames(ORB_PROJ_GATE_FUSE) with levels (level - 1, level): best_idx /
+ *                            best_dist as that call gives them for the visible points, -1 / -1 for the others.  proj_out
+ *                            may be NULL.  isBad, IsInKeyFrame, TH_LOW and the dirty-descriptor replay
+ *                            (orb_project_best_host) stay the caller's. */
+int orb_project_points(orb_ctx* ctx, const orb_points* points, int mode, const orb_camera* camera, float view_cos_limit,
+                       float th, int n, const int* ids, orb_point_proj* proj_out);
+int orb_project_points_host(int mode, const orb_camera* camera, float view_cos_limit, float th, int n, const float* pos,
+                            const float* normal, const float* min_dist, const float* max_dist, orb_point_proj* proj_out);
+int orb_search_local_points(orb_ctx* ctx, const orb_points* points, const orb_camera* camera, float view_cos_limit,
+                            float th, float nnratio, int n, const int* ids, const orb_frame* frame,
+                            const uint8_t* t_taken, int use_uright, int* match_t, int* nmatches,
+                            orb_point_proj* proj_out);
+typedef struct orb_fuse_points_target {
+    orb_camera camera;          /* the keyframe's pose and intrinsics */
+    const orb_frame* frame;     /* the keyframe */
+    const float* inv_sigma2;    /* mvInvLevelSigma2, camera.nlevels entries */
+    float th;
+    int n; const int* ids;      /* the points projected into this keyframe */
+    int* best_idx; int* best_dist;   /* n each */
+    orb_point_proj* proj_out;   /* n records, or NULL */
+} orb_fuse_points_target;
+int orb_fuse_search_points(orb_ctx* ctx, const orb_points* points, int ntargets,
+                           const orb_fuse_points_target* targets);
+
 /* ======================= Frame::ComputeStereoMatches ======================= */
 
 /* The descriptor search keeps its running best as dist << 24 | right index: at most this many right keypoints

@@ -198,6 +198,11 @@ int frame_create(const char* fn, Ctx* c, int n, const uint8_t* desc, const orb_k
                                d_work, c->stream)) != hipSuccess)
         return fail("k_frame_grid", ORB_ERR_HIP);
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail("orb_frame synchronise", ORB_ERR_HIP);
+    for (int i = 0; i < n; i++) {   // (orb_fuse_search_points checks them against its camera's nlevels per call)
+        const int o = F->kps[i].octave;
+        F->oct_min = i ? std::min(F->oct_min, o) : o;
+        F->oct_max = i ? std::max(F->oct_max, o) : o;
+    }
     *out = F;
     return ORB_OK;
 }

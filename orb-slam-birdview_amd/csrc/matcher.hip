@@ -14,12 +14,14 @@
 #include <vector>
 
 #include "orbgpu_ctx.h"
+#include "point_project.h"
 #include "topk_scan.h"
 
 namespace orbgpu {
 namespace {
 
 constexpr int TH_LOW = 50;          // ORBmatcher.cc:38
+constexpr int TH_HIGH = 100;        // :37
 constexpr int HISTO_LENGTH = 30;    // :39
 constexpr int K = 8;
 
@@ -232,12 +234,19 @@ struct TopkSession {
         st.c = c;
         return nitems > 0;
     }
-    int finish_layout() {
+    // device_queries: the queries and their descriptors are written on the device (setup_points): their regions come
+    // last, past the end of the pinned mirror
+    int finish_layout(bool device_queries = false) {
         o_thr = st.add((size_t)nt * 4);
         o_in_end = st.off;
         o_dist = st.add((size_t)nitems * K * 4);
         o_idx = st.add((size_t)nitems * K * 4);
         o_nv = st.add((size_t)nitems * 4);
+        if (device_queries) {
+            st.end_mirror();
+            o_pq = st.add((size_t)nitems * sizeof(orb_proj_query));
+            o_q = st.add((size_t)nitems * 32);
+        }
         const int r = st.alloc();
         if (r != ORB_OK) return r;
         dist = st.h<int>(o_dist);
@@ -310,6 +319,37 @@ struct TopkSession {
         st.put(o_pq, q, pq);
         st.put(o_q, qdesc, (size_t)nq * 32);
         train.put(st);
+        return ORB_OK;
+    }
+
+    // Projection mode over resident map points (orb_search_local_points): item i = slot ids[i] of P projected through
+    // cam (ORB_FRUSTUM_FRAME).  Only [camera | ids] are staged and go up; the queries and their descriptors are
+    // device-only regions (past the mirror's end) that k_project_points fills, queued here ahead of the ranking, so
+    // run() uploads nothing but its thresholds.  The kernel stores the records (want_rec) into the pinned mirror at o_rec.
+    size_t o_cam = 0, o_ids = 0, o_rec = 0;
+    int setup_points(const orb_points* P, const PointCam& cam, int n, const int* ids, const TrainSide& side,
+                     int nlanes, bool want_rec) {
+        if (!begin(PROJ, n, side.n)) return ORB_OK;
+        train = TrainStage{side, side.has_ur()};
+        lanes = nlanes;
+        o_cam = st.add(sizeof(PointCam));
+        o_ids = st.add((size_t)n * 4);
+        const size_t in_end = st.off;
+        o_rec = st.add(want_rec ? (size_t)n * sizeof(orb_point_proj) : 0);
+        train.add_arrays(st, true);
+        train.add_grid(st);
+        const int rr = finish_layout(true);
+        if (rr != ORB_OK) return rr;
+        *st.hi<PointCam>(o_cam) = cam;
+        st.put(o_ids, ids, (size_t)n * 4);
+        train.put(st);
+        hipError_t e;
+        if ((e = st.up(0, in_end)) != hipSuccess) return set_error("upload", e), ORB_ERR_HIP;
+        if ((e = launch_project_points(ORB_FRUSTUM_FRAME, st.d<PointCam>(o_cam), nullptr, st.d<int>(o_ids), n, P->d_geo,
+                                       P->d_desc, want_rec ? st.h<orb_point_proj>(o_rec) : nullptr,
+                                       st.d<orb_proj_query>(o_pq), st.d<uint8_t>(o_q), c->stream)) != hipSuccess)
+            return set_error("k_project_points", e), ORB_ERR_HIP;
+        uploaded = true;
         return ORB_OK;
     }
 
@@ -1592,6 +1632,149 @@ int orb_features_in_area(int n, const orb_keypoint* kps_un, float mnMinX, float 
                 }
             }
     return cnt > cap ? -cnt - 1 : cnt;
+}
+
+}  // extern "C"
+
+namespace orbgpu {
+namespace {
+
+// What is wrong with target k of orb_fuse_search_points, or NULL.  k_projection_best indexes inv_sigma2 by the
+// train's octave and k_project_points the slots by ids, so both are checked here.
+const char* fuse_points_target_fault(const orb_points* P, const orb_fuse_points_target& T) {
+    if (const char* why = camera_fault(&T.camera)) return why;
+    if (const char* why = frustum_scalars_fault(0.0f, T.th)) return why;
+    if (const char* why = point_ids_fault(P, T.n, T.ids)) return why;
+    if (!T.frame) return "NULL frame";
+    if (T.n > 0 && (!T.best_idx || !T.best_dist)) return "NULL outputs";
+    if (!T.inv_sigma2) return "inv_sigma2 NULL";
+    if (T.frame->n > 0 && (T.frame->oct_min < 0 || T.frame->oct_max >= T.camera.nlevels))
+        return "train octave outside [0, nlevels)";
+    return nullptr;
+}
+
+}  // namespace
+}  // namespace orbgpu
+
+extern "C" {
+
+/* Tracking::SearchLocalPoints' isInFrustum loop and SearchByProjection(Frame&, vector<MapPoint*>, th) over resident
+ * points and a resident frame (orbgpu.h): k_project_points, k_projection_topk and proj_replay, one synchronisation. */
+int orb_search_local_points(orb_ctx* h, const orb_points* P, const orb_camera* camera, float view_cos_limit, float th,
+                            float nnratio, int n, const int* ids, const orb_frame* F, const uint8_t* t_taken,
+                            int use_uright, int* match_t, int* nmatches_out, orb_point_proj* proj_out) {
+    const char* const fn = "orb_search_local_points";
+    if (const char* why = camera_fault(camera)) return arg_error(fn, why);
+    if (const char* why = frustum_scalars_fault(view_cos_limit, th)) return arg_error(fn, why);
+    if (const char* why = point_ids_fault(P, n, ids)) return arg_error(fn, why);
+    if (!F) return arg_error(fn, "NULL frame");
+    if (F->n && !match_t) return arg_error(fn, "bad arguments");
+    if (use_uright && !F->has_ur) return arg_error(fn, "use_uright with a frame created without uright");
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (c && P->device != c->device) return arg_error(fn, "the points live on another device");
+    const TrainSide side(F, use_uright != 0);
+    if (const int st = side_guard(fn, c, side)) return st;
+    for (int t = 0; t < side.n; t++) match_t[t] = -1;
+    if (nmatches_out) *nmatches_out = 0;
+    if (n == 0 || side.n == 0) return ORB_OK;
+    TopkSession s{c};
+    int st = s.setup_points(P, point_cam(c, *camera, view_cos_limit, th), n, ids, side, proj_lanes(), proj_out != nullptr);
+    if (st != ORB_OK) return st;
+    // the replay reads a query's `blocks` only (RATIO_SAME_LEVEL): every map point here has observations (:87-89)
+    std::vector<orb_proj_query> q((size_t)n, orb_proj_query{0.0f, 0.0f, 0.0f, -1, -1, 0.0f, 0.0f, 0.0f, 1});
+    st = proj_replay(s, ORB_PROJ_RATIO_SAME_LEVEL, nnratio, 0, TH_HIGH, q.data(), side.kps, t_taken, match_t,
+                     nmatches_out);
+    if (st != ORB_OK) return st;
+    if (proj_out) std::memcpy(proj_out, s.st.h<orb_point_proj>(s.o_rec), (size_t)n * sizeof(orb_point_proj));
+    return ORB_OK;
+}
+
+/* Fuse(KeyFrame*, vector<MapPoint*>, th) for many keyframes over resident points and resident frames (orbgpu.h):
+ * every target's items in one k_project_points launch (FUSE form, the item's camera) and one k_projection_best launch
+ * (gate FUSE) over the queries it wrote. */
+int orb_fuse_search_points(orb_ctx* h, const orb_points* P, int ntargets, const orb_fuse_points_target* targets) {
+    const char* const fn = "orb_fuse_search_points";
+    if (!P) return arg_error(fn, "NULL points handle");
+    if (ntargets < 0 || (ntargets > 0 && !targets)) return arg_error(fn, "ntargets < 0 or targets NULL");
+    size_t nitems = 0, nused = 0;
+    bool want_rec = false;
+    for (int k = 0; k < ntargets; k++) {
+        const orb_fuse_points_target& T = targets[k];
+        if (const char* why = fuse_points_target_fault(P, T))
+            return arg_error(fn, "target " + std::to_string(k) + ": " + why);
+        if (T.n > 0 && T.frame->n > 0) {
+            nitems += (size_t)T.n;
+            nused++;
+            want_rec = want_rec || T.proj_out;
+        }
+    }
+    if (nitems > (size_t)INT_MAX / 2) return arg_error(fn, "too many points");
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
+    if (P->device != c->device) return arg_error(fn, "the points live on another device");
+    for (int k = 0; k < ntargets; k++)
+        if (targets[k].frame->device != c->device)
+            return arg_error(fn, "target " + std::to_string(k) + ": the frame lives on another device");
+    CTX_GUARD(c);
+    for (int k = 0; k < ntargets; k++)
+        for (int i = 0; i < targets[k].n; i++) targets[k].best_idx[i] = targets[k].best_dist[i] = -1;
+    if (nitems == 0) return ORB_OK;
+    // staged and uploaded: [table | cameras | item -> row | ids | per used target inv_sigma2]; then the outputs, stored
+    // into the mirror; past the mirror's end, device only: the queries and their descriptors (k_project_points' output)
+    Stage st{c};
+    const size_t o_tab = st.add(nused * sizeof(ProjTarget)), o_cam = st.add(nused * sizeof(PointCam)),
+                 o_item = st.add(nitems * 4), o_ids = st.add(nitems * 4);
+    std::vector<size_t> o_inv;
+    o_inv.reserve(nused);
+    for (int k = 0; k < ntargets; k++)
+        if (targets[k].n > 0 && targets[k].frame->n > 0) o_inv.push_back(st.add((size_t)targets[k].camera.nlevels * 4));
+    const size_t o_in_end = st.off;
+    const size_t o_idx = st.add(nitems * 4), o_dist = st.add(nitems * 4),
+                 o_rec = st.add(want_rec ? nitems * sizeof(orb_point_proj) : 0);
+    st.end_mirror();
+    const size_t o_pq = st.add(nitems * sizeof(orb_proj_query)), o_q = st.add(nitems * 32);
+    const int rr = st.alloc();
+    if (rr != ORB_OK) return rr;
+    size_t item = 0, row = 0;
+    for (int k = 0; k < ntargets; k++) {
+        const orb_fuse_points_target& T = targets[k];
+        if (T.n == 0 || T.frame->n == 0) continue;
+        const TrainStage train{TrainSide(T.frame, true), T.frame->has_ur};
+        ProjTarget& D = st.hi<ProjTarget>(o_tab)[row];
+        D = train.row(st);
+        D.inv_sigma2 = st.d<float>(o_inv[row]);
+        st.hi<PointCam>(o_cam)[row] = point_cam(c, T.camera, 0.0f, T.th);
+        for (int i = 0; i < T.n; i++) st.hi<int>(o_item)[item + i] = (int)row;
+        std::memcpy(st.hi<int>(o_ids) + item, T.ids, (size_t)T.n * 4);
+        st.put(o_inv[row], T.inv_sigma2, (size_t)T.camera.nlevels * 4);
+        item += (size_t)T.n;
+        row++;
+    }
+    hipError_t e;
+    if ((e = st.up(0, o_in_end)) != hipSuccess) return set_error("upload", e), ORB_ERR_HIP;
+    if ((e = launch_project_points(ORB_FRUSTUM_FUSE, st.d<PointCam>(o_cam), st.d<int>(o_item), st.d<int>(o_ids),
+                                   (int)nitems, P->d_geo, P->d_desc,
+                                   want_rec ? st.h<orb_point_proj>(o_rec) : nullptr, st.d<orb_proj_query>(o_pq),
+                                   st.d<uint8_t>(o_q), c->stream)) != hipSuccess)
+        return set_error("k_project_points", e), ORB_ERR_HIP;
+    if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
+    e = launch_projection_best(ORB_PROJ_GATE_FUSE, st.d<ProjTarget>(o_tab), st.d<int>(o_item),
+                               st.d<orb_proj_query>(o_pq), st.d<uint8_t>(o_q), (int)nitems, st.h<int>(o_idx),
+                               st.h<int>(o_dist), c->stream);
+    if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 0, c->stream);
+    if (e != hipSuccess) return set_error("projection kernel", e), ORB_ERR_HIP;
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("download", e), ORB_ERR_HIP;
+    item = 0;
+    for (int k = 0; k < ntargets; k++) {
+        const orb_fuse_points_target& T = targets[k];
+        if (T.n == 0 || T.frame->n == 0) continue;
+        std::memcpy(T.best_idx, st.h<int>(o_idx) + item, (size_t)T.n * 4);
+        std::memcpy(T.best_dist, st.h<int>(o_dist) + item, (size_t)T.n * 4);
+        if (T.proj_out)
+            std::memcpy(T.proj_out, st.h<orb_point_proj>(o_rec) + item, (size_t)T.n * sizeof(orb_point_proj));
+        item += (size_t)T.n;
+    }
+    return ORB_OK;
 }
 
 }  // extern "C"

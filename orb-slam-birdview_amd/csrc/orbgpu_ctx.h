@@ -173,6 +173,14 @@ struct Ctx {
     unsigned flow_serial = 0;       // geom_serial the plan was built for
     bool flow_ok = false;           // flow holds a plan for (flow_serial, flow.nframes)
 
+    // MapPoint::PredictScale's level thresholds (point_project.h), found once per (log_scale_factor, nlevels)
+    struct LevelThresholds {
+        float lsf;
+        int nlevels;
+        float T[ORBGPU_MAX_LEVELS];
+    };
+    std::vector<LevelThresholds> level_thr;
+
     int ensure_geometry(int W, int H);
     int ensure_flow(int nframes);
     int ensure_frames(int nframes);
@@ -293,4 +301,5 @@ struct orb_frame {
     const int* d_coff = nullptr;   // kFrameGridCells + 1
     const int* d_cidx = nullptr;   // n slots (cell_off[kFrameGridCells] of them used)
     std::vector<orb_keypoint> kps;
+    int oct_min = 0, oct_max = -1;   // the octaves of kps, found once by the creator (n > 0)
 };

@@ -232,6 +232,29 @@ ResidentFrame& ResidentFrame::operator=(ResidentFrame&& o) noexcept {
     return *this;
 }
 
+/* ---------------- ResidentPoints (orb_points) ---------------- */
+ResidentPoints::ResidentPoints(int capacity) {
+    check(orb_points_create(matcher_ctx(), capacity, &h_), "ResidentPoints");
+}
+
+ResidentPoints::~ResidentPoints() { orb_points_destroy(h_); }
+
+ResidentPoints::ResidentPoints(ResidentPoints&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+
+ResidentPoints& ResidentPoints::operator=(ResidentPoints&& o) noexcept {
+    if (this != &o) {
+        orb_points_destroy(h_);
+        h_ = o.h_;
+        o.h_ = nullptr;
+    }
+    return *this;
+}
+
+void ResidentPoints::Write(int first, int n, const float* pos, const float* normal, const float* minDistance,
+                           const float* maxDistance, const uint8_t* descriptors) {
+    check(orb_points_write(h_, first, n, pos, normal, minDistance, maxDistance, descriptors), "ResidentPoints::Write");
+}
+
 void ResidentFrame::Grid(std::vector<int>& off, std::vector<int>& idx) const {
     require(h_ != nullptr, "ResidentFrame::Grid: empty handle");
     off.assign((size_t)ORBGPU_FRAME_GRID_COLS * ORBGPU_FRAME_GRID_ROWS + 1, 0);
@@ -854,6 +877,61 @@ int ORBmatcher::SearchByMatchBird(const KeyFrameBirdPoints& KF, const ResidentFr
 int ORBmatcher::BirdviewMatch(const FrameData& F1, const ResidentFrame& F2, std::vector<int>& vnMatches12,
                               int windowSize) {
     return window_match(false, F1, with_resident(FrameData(), F2), nullptr, windowSize, vnMatches12);
+}
+
+/* ---------------- the searches over ResidentPoints: projection and search in one GPU call ---------------- */
+
+int ORBmatcher::SearchLocalPoints(const ResidentPoints& points, const orb_camera& camera, const std::vector<int>& ids,
+                                  const ResidentFrame& F, const FrameData& members, const float th,
+                                  const float viewingCosLimit, std::vector<int>& vpMapPointMatches,
+                                  std::vector<orb_point_proj>* proj) {
+    require(points && F, "SearchLocalPoints: empty handle");
+    const int n = (int)ids.size();
+    vpMapPointMatches.assign(std::max(F.N(), 1), -1);
+    if (proj) proj->assign(std::max(n, 1), orb_point_proj());
+    int nmatches = 0;
+    check(orb_search_local_points(matcher_ctx(), points.handle(), &camera, viewingCosLimit, th, mfNNratio, n,
+                                  n ? ids.data() : nullptr, F.handle(), members.hasMapPoint, F.hasURight() ? 1 : 0,
+                                  vpMapPointMatches.data(), &nmatches, proj ? proj->data() : nullptr),
+          "SearchLocalPoints");
+    vpMapPointMatches.resize(F.N());
+    if (proj) proj->resize(n);
+    return nmatches;
+}
+
+void ORBmatcher::FuseSearch(const ResidentPoints& points, const std::vector<FusePointsTarget>& targets,
+                            std::vector<std::vector<FuseBest> >& best,
+                            std::vector<std::vector<orb_point_proj> >* proj) {
+    require((bool)points, "FuseSearch: empty points handle");
+    const size_t nt = targets.size();
+    std::vector<orb_fuse_points_target> T(std::max<size_t>(nt, 1));
+    std::vector<std::vector<int> > idx(nt), dist(nt);
+    if (proj) proj->assign(nt, std::vector<orb_point_proj>());
+    for (size_t t = 0; t < nt; t++) {
+        const FusePointsTarget& S = targets[t];
+        require(S.kf && *S.kf, "FuseSearch: a target without its ResidentFrame");
+        const size_t n = S.ids.size();
+        idx[t].assign(std::max<size_t>(n, 1), -1);
+        dist[t].assign(std::max<size_t>(n, 1), -1);
+        if (proj) (*proj)[t].assign(std::max<size_t>(n, 1), orb_point_proj());
+        T[t].camera = S.camera;
+        T[t].frame = S.kf->handle();
+        T[t].inv_sigma2 = S.invLevelSigma2;
+        T[t].th = S.th;
+        T[t].n = (int)n;
+        T[t].ids = n ? S.ids.data() : nullptr;
+        T[t].best_idx = idx[t].data();
+        T[t].best_dist = dist[t].data();
+        T[t].proj_out = proj ? (*proj)[t].data() : nullptr;
+    }
+    check(orb_fuse_search_points(matcher_ctx(), points.handle(), (int)nt, T.data()), "FuseSearch(ResidentPoints)");
+    best.assign(nt, std::vector<FuseBest>());
+    for (size_t t = 0; t < nt; t++) {
+        const size_t n = targets[t].ids.size();
+        best[t].resize(n);
+        for (size_t i = 0; i < n; i++) best[t][i] = FuseBest{idx[t][i], dist[t][i]};
+        if (proj) (*proj)[t].resize(n);
+    }
 }
 
 std::vector<int> ComputeDistinctiveDescriptors(const std::vector<std::vector<const uint8_t*> >& observations) {

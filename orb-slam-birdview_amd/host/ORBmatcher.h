@@ -100,6 +100,42 @@ private:
     bool hasURight_ = false;
 };
 
+// Map points kept on the device (the C-ABI's orb_points): per slot GetWorldPos, GetNormal, the raw mfMinDistance /
+// mfMaxDistance and GetDescriptor.  Write() fills or rewrites a slot range and grows the handle; a point whose
+// position, normal, distances or descriptor changed is written again.  ORBmatcher::SearchLocalPoints and
+// FuseSearch(const ResidentPoints&, ...) project and search the slots without staging them.  Move-only; the destructor
+// frees the device memory; failures throw OrbGpuError.  It lives on the GPU of the calling thread's matcher context,
+// like a ResidentFrame.
+class ResidentPoints {
+public:
+    ResidentPoints() = default;
+    explicit ResidentPoints(int capacity);
+    ~ResidentPoints();
+    ResidentPoints(ResidentPoints&& o) noexcept;
+    ResidentPoints& operator=(ResidentPoints&& o) noexcept;
+    ResidentPoints(const ResidentPoints&) = delete;
+    ResidentPoints& operator=(const ResidentPoints&) = delete;
+
+    // slots first .. first + n - 1: pos and normal 3 n floats, the distances n floats, descriptors 32 n bytes
+    void Write(int first, int n, const float* pos, const float* normal, const float* minDistance,
+               const float* maxDistance, const uint8_t* descriptors);
+    int Capacity() const { return orb_points_capacity(h_); }
+    explicit operator bool() const { return h_ != nullptr; }
+    const orb_points* handle() const { return h_; }
+
+private:
+    orb_points* h_ = nullptr;
+};
+
+// One target keyframe of FuseSearch(const ResidentPoints&, ...): Fuse(pKF, vpMapPoints, th) with the points as slots
+struct FusePointsTarget {
+    orb_camera camera;                        // pKF's pose and intrinsics (orbgpu.h)
+    const ResidentFrame* kf = nullptr;        // pKF
+    const float* invLevelSigma2 = nullptr;    // pKF->mvInvLevelSigma2, camera.nlevels entries
+    float th = 3.0f;
+    std::vector<int> ids;                     // the slots of the points that are neither bad nor IsInKeyFrame(pKF)
+};
+
 // The members of a Frame / KeyFrame that ORBmatcher reads, as zero-copy views (cv::KeyPoint and
 // orb_keypoint share one 28-byte layout; a continuous n x 32 CV_8U Mat is n*32 bytes).  Pointers
 // may be NULL where a method does not read the member (see each method).
@@ -285,6 +321,21 @@ public:
     // ...) (:977-1100, LoopClosing::SearchAndFuse).  best[t][i] belongs to targets[t].points[i]; what follows the
     // search (:952-971) is the caller's replay.
     void FuseSearch(const std::vector<FuseTarget>& targets, bool chi2Gate, std::vector<std::vector<FuseBest> >& best);
+    // The same search (chi2 gate) with the projection on the GPU too: target t's points are the slots targets[t].ids
+    // of `points`, projected through targets[t].camera as ORBmatcher.cc:852-890 does; best[t][i] belongs to ids[i],
+    // -1 / -1 for a point the projection rejects.  proj (optional) receives the records (orb_point_proj).
+    void FuseSearch(const ResidentPoints& points, const std::vector<FusePointsTarget>& targets,
+                    std::vector<std::vector<FuseBest> >& best,
+                    std::vector<std::vector<orb_point_proj> >* proj = nullptr);
+    // Tracking::SearchLocalPoints' second loop (Tracking.cc:1635-1660): Frame::isInFrustum(pMP, viewingCosLimit) for
+    // the slots ids of `points` through camera, then SearchByProjection(F, vpMapPoints, th) over the visible ones, in
+    // one GPU call.  members: hasMapPoint (mvpMapPoints[i] && Observations() > 0; NULL: none).  F's uRight gates if it
+    // has one.  vpMapPointMatches (sized to F.N()): per Frame feature the position in ids of the point assigned to it,
+    // -1 = none.  proj (optional) receives the records: verdict 0 is isInFrustum returning true.
+    int SearchLocalPoints(const ResidentPoints& points, const orb_camera& camera, const std::vector<int>& ids,
+                          const ResidentFrame& F, const FrameData& members, const float th,
+                          const float viewingCosLimit, std::vector<int>& vpMapPointMatches,
+                          std::vector<orb_point_proj>* proj = nullptr);
     // One point of one target on the CPU with another descriptor: a point whose descriptor changed during the replay.
     FuseBest FuseSearchOne(const FuseTarget& target, int point, const uint8_t* descriptor, bool chi2Gate);
     // ORBmatcher.cc:1102-1326: both directions in one GPU call, TH_HIGH and the agreement loop.  vnMatch12[i1] = the

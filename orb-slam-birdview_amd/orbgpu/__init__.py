@@ -12,11 +12,12 @@ import numpy as np
 
 from ._lib import (VARIANT_BLUR_HALFUP, VARIANT_DEFAULT, VARIANT_NO_FMA, VARIANT_RESIZE_GENERIC,
                    VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, OrbProjFrameTarget,
-                   OrbProjTarget, KfdbNeighboursFn, check, lib)
+                   OrbProjTarget, OrbCamera, OrbFusePointsTarget, KfdbNeighboursFn, check, lib)
 
 __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError", "device_count",
            "features_in_area", "frame_grid", "Frame", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
            "PROJ_GATE_NONE", "PROJ_GATE_FUSE", "proj_queries", "project_best_host",
+           "MapPoints", "POINT_PROJ_DTYPE", "FRUSTUM_FRAME", "FRUSTUM_FUSE", "camera", "project_points_host",
            "compute_stereo_matches", "ORBVocabulary", "KeyFrameDatabase", "bow_score", "KFDB_RELOC", "KFDB_LOOP",
            "BirdORB", "cornerSubPix",
            "bird_footprint_mask", "VARIANT_DEFAULT", "VARIANT_TIE_REVERSE", "VARIANT_RESIZE_GENERIC",
@@ -34,6 +35,12 @@ PROJ_QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("r", "<f4"), ("min_lev
 assert PROJ_QUERY_DTYPE.itemsize == 36
 PROJ_BEST, PROJ_RATIO_SAME_LEVEL = 0, 1   # ORB_PROJ_*
 PROJ_GATE_NONE, PROJ_GATE_FUSE = 0, 1     # ORB_PROJ_GATE_*
+
+# orb_point_proj (include/orbgpu.h): the projection of one resident map point
+POINT_PROJ_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("invz", "<f4"), ("dist", "<f4"),
+                             ("view_cos", "<f4"), ("r", "<f4"), ("level", "<i4"), ("verdict", "<i4")])
+assert POINT_PROJ_DTYPE.itemsize == 36
+FRUSTUM_FRAME, FRUSTUM_FUSE = 0, 1        # ORB_FRUSTUM_*
 
 
 def _p(a):
@@ -392,6 +399,84 @@ class Frame:
     def close(self):
         if getattr(self, "h", None):
             lib().orb_frame_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def camera(Rcw, tcw, Ow, fx, fy, cx, cy, mbf, bounds, scale_factors, log_scale_factor):
+    """orb_camera from a Frame's / KeyFrame's members: Rcw (3x3), tcw, Ow, the intrinsics, bounds = (mnMinX, mnMaxX,
+    mnMinY, mnMaxY), mvScaleFactors and mfLogScaleFactor, all taken as float32."""
+    f32 = np.float32
+    sf = np.asarray(scale_factors, f32).ravel()
+    assert len(sf) <= 16
+    c = OrbCamera()
+    c.Rcw[:] = np.asarray(Rcw, f32).ravel().tolist()
+    c.tcw[:] = np.asarray(tcw, f32).ravel().tolist()
+    c.Ow[:] = np.asarray(Ow, f32).ravel().tolist()
+    c.fx, c.fy, c.cx, c.cy, c.mbf = (float(f32(x)) for x in (fx, fy, cx, cy, mbf))
+    c.min_x, c.max_x, c.min_y, c.max_y = (float(f32(x)) for x in bounds)
+    c.nlevels, c.log_scale_factor = len(sf), float(f32(log_scale_factor))
+    for i, x in enumerate(sf):
+        c.scale_factors[i] = float(x)
+    return c
+
+
+def _point_arrays(pos, normal, min_dist, max_dist):
+    f32 = np.float32
+    p = np.ascontiguousarray(pos, f32).reshape(-1, 3)
+    nr = np.ascontiguousarray(normal, f32).reshape(-1, 3)
+    lo, hi = np.ascontiguousarray(min_dist, f32).ravel(), np.ascontiguousarray(max_dist, f32).ravel()
+    assert len(p) == len(nr) == len(lo) == len(hi)
+    return p, nr, lo, hi
+
+
+def project_points_host(mode, cam, pos, normal, min_dist, max_dist, view_cos_limit=0.5, th=1.0):
+    """orb_project_points_host: the records of orb_project_points on the CPU, from host arrays; no context, no GPU."""
+    p, nr, lo, hi = _point_arrays(pos, normal, min_dist, max_dist)
+    out = np.zeros(len(p), POINT_PROJ_DTYPE)
+    check(lib().orb_project_points_host(int(mode), ctypes.byref(cam), float(view_cos_limit), float(th), len(p), _p(p),
+                                        _p(nr), _p(lo), _p(hi), _p(out)), "orb_project_points_host")
+    return out
+
+
+class MapPoints:
+    """Map points resident on the device (orb_points): per slot GetWorldPos, GetNormal, the raw mfMinDistance /
+    mfMaxDistance and GetDescriptor.  write() fills or rewrites a slot range (and grows the handle), project() runs
+    Frame::isInFrustum (FRUSTUM_FRAME) or Fuse's projection (FRUSTUM_FUSE) for a list of slot ids on the GPU; the
+    fused searches are ORBmatcher.SearchLocalPoints / FuseSearchPoints.  len() is the capacity.  close() frees it;
+    close it before its context."""
+
+    def __init__(self, ctx_or_matcher, capacity=0):
+        self.h = None
+        self._ctx_h = _ctx_handle(ctx_or_matcher)
+        out = ctypes.c_void_p()
+        check(lib().orb_points_create(self._ctx_h, int(capacity), ctypes.byref(out)), "orb_points_create")
+        self.h = out
+
+    def write(self, first, pos, normal, min_dist, max_dist, desc):
+        p, nr, lo, hi = _point_arrays(pos, normal, min_dist, max_dist)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        assert len(d) == len(p)
+        check(lib().orb_points_write(self.h, int(first), len(p), _p(p), _p(nr), _p(lo), _p(hi), _p(d)),
+              "orb_points_write")
+
+    def __len__(self):
+        return lib().orb_points_capacity(self.h)
+
+    def project(self, mode, cam, ids, view_cos_limit=0.5, th=1.0, ctx_or_matcher=None):
+        """orb_project_points: POINT_PROJ_DTYPE records for the slots ids, in ids order."""
+        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        out = np.zeros(len(ids), POINT_PROJ_DTYPE)
+        h = self._ctx_h if ctx_or_matcher is None else _ctx_handle(ctx_or_matcher)
+        check(lib().orb_project_points(h, self.h, int(mode), ctypes.byref(cam), float(view_cos_limit), float(th),
+                                       len(ids), _p(ids) if len(ids) else None, _p(out)), "orb_project_points")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().orb_points_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -839,6 +924,44 @@ class ORBmatcher:
         check(lib().orb_project_best_batch(self._ctx.h, int(gate), len(targets), ctypes.addressof(T.arr)),
               "orb_project_best_batch")
         return T.out
+
+    def SearchLocalPoints(self, points, cam, ids, frame, th=1.0, view_cos_limit=0.5, taken=None, use_uright=False,
+                          want_proj=True):
+        """orb_search_local_points: Tracking::SearchLocalPoints' isInFrustum loop (view_cos_limit 0.5, Tracking.cc:1641)
+        and SearchByProjection(Frame&, vector<MapPoint*>, th) over resident map points (a MapPoints, the slots ids) and
+        a resident Frame, in one call.  Returns (match_t, nmatches, proj): match_t[t] = the position in ids of the point
+        assigned to feature t (-1: none), proj = the POINT_PROJ_DTYPE records (None without want_proj)."""
+        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        tk = None if taken is None else np.ascontiguousarray(taken, np.uint8)
+        assert tk is None or len(tk) == len(frame)
+        match_t = np.full(max(len(frame), 1), -1, np.int32)
+        proj = np.zeros(len(ids), POINT_PROJ_DTYPE) if want_proj else None
+        nm = ctypes.c_int(0)
+        check(lib().orb_search_local_points(self._ctx.h, points.h, ctypes.byref(cam), float(view_cos_limit), float(th),
+                                            self.mfNNratio, len(ids), _p(ids) if len(ids) else None, frame.h, _p(tk),
+                                            int(bool(use_uright)), _p(match_t), ctypes.byref(nm), _p(proj)),
+              "orb_search_local_points")
+        return match_t[:len(frame)], nm.value, proj
+
+    def FuseSearchPoints(self, points, targets, want_proj=True):
+        """orb_fuse_search_points: the projection and search of Fuse(KeyFrame*, vector<MapPoint*>, th) for many target
+        keyframes in one call, over resident map points.  targets: dicts with camera (camera(...)), frame (a Frame),
+        inv_sigma2 (mvInvLevelSigma2), th and ids.  Returns per target (best_idx, best_dist, proj)."""
+        arr = (OrbFusePointsTarget * max(len(targets), 1))()
+        keep, out = [], []
+        for k, t in enumerate(targets):
+            ids = np.ascontiguousarray(t["ids"], np.int32).ravel()
+            inv = np.ascontiguousarray(t["inv_sigma2"], np.float32)
+            n = len(ids)
+            bi, bd = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), -1, np.int32)
+            proj = np.zeros(max(n, 1), POINT_PROJ_DTYPE) if want_proj else None
+            arr[k] = OrbFusePointsTarget(t["camera"], t["frame"].h, _p(inv), float(t["th"]), n, _p(ids), _p(bi), _p(bd),
+                                         _p(proj))
+            keep.append((ids, inv, t["frame"]))
+            out.append((bi[:n], bd[:n], None if proj is None else proj[:n]))
+        check(lib().orb_fuse_search_points(self._ctx.h, points.h, len(targets), ctypes.addressof(arr)),
+              "orb_fuse_search_points")
+        return out
 
     def Fuse(self, targets):
         """The search of Fuse(KeyFrame* pKF, const vector<MapPoint*>&, th) (ORBmatcher.cc:823-975) for every target

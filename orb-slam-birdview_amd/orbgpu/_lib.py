@@ -61,6 +61,17 @@ class OrbProjFrameTarget(ctypes.Structure):   # orb_proj_frame_target
                 ("best_idx", vp), ("best_dist", vp)]
 
 
+class OrbCamera(ctypes.Structure):   # orb_camera
+    _fields_ = [("Rcw", cf * 9), ("tcw", cf * 3), ("Ow", cf * 3), ("fx", cf), ("fy", cf), ("cx", cf), ("cy", cf),
+                ("mbf", cf), ("min_x", cf), ("max_x", cf), ("min_y", cf), ("max_y", cf), ("nlevels", ci),
+                ("log_scale_factor", cf), ("scale_factors", cf * 16)]
+
+
+class OrbFusePointsTarget(ctypes.Structure):   # orb_fuse_points_target
+    _fields_ = [("camera", OrbCamera), ("frame", vp), ("inv_sigma2", vp), ("th", cf), ("n", ci), ("ids", vp),
+                ("best_idx", vp), ("best_dist", vp), ("proj_out", vp)]
+
+
 # orb_kfdb_neighbours_fn: int (*)(void* user, int id, int* out, int cap)
 KfdbNeighboursFn = ctypes.CFUNCTYPE(ci, vp, ci, ctypes.POINTER(ci), ci)
 
@@ -125,6 +136,15 @@ SIGNATURES = {
     "orb_window_match_frame": (ci, [vp, cf, ci, ci, ci, vp, vp, vp, cf, vp, vp, ctypes.POINTER(ci)]),
     "orb_search_by_match_bird_resident": (ci, [vp, cf, ci, ci, cf, ci, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ci)]),
     "orb_project_best_frames": (ci, [vp, ci, ci, vp]),
+    "orb_points_create": (ci, [vp, ci, ctypes.POINTER(vp)]),
+    "orb_points_write": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
+    "orb_points_capacity": (ci, [vp]),
+    "orb_points_destroy": (None, [vp]),
+    "orb_project_points": (ci, [vp, vp, ci, ctypes.POINTER(OrbCamera), cf, cf, ci, vp, vp]),
+    "orb_project_points_host": (ci, [ci, ctypes.POINTER(OrbCamera), cf, cf, ci, vp, vp, vp, vp, vp]),
+    "orb_search_local_points": (ci, [vp, vp, ctypes.POINTER(OrbCamera), cf, cf, cf, ci, vp, vp, vp, ci, vp,
+                                     ctypes.POINTER(ci), vp]),
+    "orb_fuse_search_points": (ci, [vp, vp, ci, vp]),
     "orb_features_in_area": (ci, [ci, vp, cf, cf, cf, cf, cf, cf, cf, ci, ci, vp, ci]),
     "orb_compute_stereo_matches": (ci, [vp, vp, ci, vp, vp, ci, vp, vp, cf, cf, vp, vp, ctypes.POINTER(ci)]),
     "orb_stereo_batch_device": (ci, [vp, ci, cf, cf, vp, vp, vp]),
