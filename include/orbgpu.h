@@ -591,6 +591,61 @@ typedef struct orb_proj_frame_target {
 } orb_proj_frame_target;
 int orb_project_best_frames(orb_ctx* ctx, int gate, int ntargets, const orb_proj_frame_target* targets);
 
+/* ======================= UndistortKeyPoints / ComputeImageBounds; resident frames from an extraction ============= */
+
+/* Frame::UndistortKeyPoints (Frame.cc:571-603) and Frame::ComputeImageBounds (Frame.cc:605-660), which in this fork
+ * call cv::fisheye::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK).  The definition is OpenCV 3.2 fisheye.cpp
+ * on x86-64 without FMA, in double: fx, fy, cx, cy are mK's floats, k[0..3] mDistCoef's four floats in
+ * the order Tracking.cc:68-72 stores them (Camera.k1, k2, p1, p2), which the fisheye model reads as k1..k4.
+ * k[0] == 0.0f is the reference's identity path whatever k[1..3] hold: positions come back bit for bit, the bounds are
+ * 0, w, 0, h.  A NaN result is stored as 0x7FC00000 (the one decided deviation: NaN payloads differ between libms); an
+ * infinite one keeps its sign.  Only x and y of a keypoint change; its other 24 bytes are copied.
+ *   orb_undistort_points_host  the definition, on the CPU (std::tan): n (x, y) pairs in, n pairs out (xy_un may be xy).
+ *                              No context, no GPU.  Positions that are not finite go through the arithmetic.
+ *   orb_image_bounds           mnMinX, mnMaxX, mnMinY, mnMaxY of a w x h image: the four corners through the same
+ *                              function and the reference's loop, whose maxima start at numeric_limits<float>::min()
+ *                              (the smallest positive float: a maximum that would be negative or zero stays there).
+ *                              No context, no GPU.
+ *   orb_undistort_keypoints    n keypoints in host arrays, undistorted on the GPU (kps_un may be kps).
+ *   orb_undistort_keypoints_device  a whole batch in orb_extract_batch_device's output layout (frame f's records at
+ *                              d_kps + f * kp_cap, its count in d_counts[f]) in one launch; d_kps_un has the same
+ *                              layout and may be d_kps; slots past a frame's count are not written.
+ * The GPU forms return exactly the bytes of orb_undistort_points_host: the kernel computes each result from its own
+ * tan and from both ends of a guard band around it, and the few points whose results differ (a few coordinates in
+ * 10^7) are recomputed by the host function before the call returns; *n_redone (may be NULL) receives their number.
+ *   orb_frame_create_from_extract  orb_frame_create_device for RAW keypoints: one frame's descriptors, raw keypoints
+ *                              and optionally uright in device memory (e.g. a slot of orb_extract_batch_device's
+ *                              outputs) become a resident frame whose keypoints (device and host copy) are the
+ *                              undistorted ones; the grid is built from them.  The inputs are not modified.
+ *   orb_frames_create_from_batch   the same for nframes frames in orb_extract_batch_device's output layout (no
+ *                              uright): one undistort launch, one grid launch per frame, the stream synchronised
+ *                              three times whatever nframes is.  out receives nframes handles (an empty frame gets an
+ *                              empty handle); on any failure none is leaked and out is untouched.  A count above
+ *                              kp_cap is ORB_ERR_CAPACITY.
+ * All GPU forms return synchronised, on the context's stream, and follow orb_frame_create_device's rules for device,
+ * thread and lifetime.  ORB_ERR_ARG before any GPU work, outputs untouched: dist NULL; fx or fy zero or not finite;
+ * cx, cy or a k not finite; n or nframes negative (nframes above 65,535, nframes * kp_cap above INT_MAX); NULL arrays
+ * with n > 0 (nframes > 0); kp_cap < 1 with nframes > 0; orb_frame_create's grid checks; negative w or h; and for
+ * orb_undistort_keypoints a position that is not finite (positions in device arrays are not checked: they go through
+ * the arithmetic, and the grid leaves out a keypoint whose undistorted position is not finite).  n == 0 / nframes == 0
+ * is ORB_OK without a context, except that orb_frame_create_from_extract with n == 0 creates an empty handle.
+ *   orb_debug_undistort_guard  the guard band's relative half-width g for this context (0 restores the default,
+ *                              2^-46; below the default the equality with the host function is no longer assured). */
+typedef struct orb_distortion { float fx, fy, cx, cy; float k[4]; } orb_distortion;
+int orb_undistort_points_host(const orb_distortion* dist, int n, const float* xy, float* xy_un);
+int orb_image_bounds(const orb_distortion* dist, int w, int h, float* min_x, float* max_x, float* min_y, float* max_y);
+int orb_undistort_keypoints(orb_ctx* ctx, const orb_distortion* dist, int n, const orb_keypoint* kps,
+                            orb_keypoint* kps_un, int* n_redone);
+int orb_undistort_keypoints_device(orb_ctx* ctx, const orb_distortion* dist, int nframes, const orb_keypoint* d_kps,
+                                   const int* d_counts, int kp_cap, orb_keypoint* d_kps_un, int* n_redone);
+int orb_frame_create_from_extract(orb_ctx* ctx, const orb_distortion* dist, int n, const uint8_t* d_desc,
+                                  const orb_keypoint* d_kps_raw, const float* d_uright, float min_x, float min_y,
+                                  float inv_w, float inv_h, orb_frame** out);
+int orb_frames_create_from_batch(orb_ctx* ctx, const orb_distortion* dist, int nframes, const uint8_t* d_desc,
+                                 const orb_keypoint* d_kps_raw, const int* d_counts, int kp_cap, float min_x,
+                                 float min_y, float inv_w, float inv_h, orb_frame** out);
+int orb_debug_undistort_guard(orb_ctx* ctx, double g);
+
 /* ======================= Resident map points: isInFrustum and Fuse's projection ======================= */
 
 /* The query side of the projection searches, kept on the device: the same map points are projected frame after frame

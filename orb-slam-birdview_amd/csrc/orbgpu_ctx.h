@@ -181,6 +181,9 @@ struct Ctx {
     };
     std::vector<LevelThresholds> level_thr;
 
+    // k_undistort_fisheye's guard band (undistort.hip): 0 = the default, else orb_debug_undistort_guard's override
+    double undistort_guard = 0.0;
+
     int ensure_geometry(int W, int H);
     int ensure_flow(int nframes);
     int ensure_frames(int nframes);

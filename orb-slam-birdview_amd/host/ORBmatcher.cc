@@ -211,6 +211,64 @@ ResidentFrame ResidentFrame::FromDevice(orb_ctx* ctx, int n, const uint8_t* d_de
     return f;
 }
 
+ResidentFrame ResidentFrame::FromExtraction(orb_ctx* ctx, const orb_distortion& dist, int n, const uint8_t* d_descriptors,
+                                            const KeyPoint* d_keysRaw, const float* d_uRight, float minX, float maxX,
+                                            float minY, float maxY) {
+    const float invW = static_cast<float>(ORBGPU_FRAME_GRID_COLS) / static_cast<float>(maxX - minX);   // as FrameGrid
+    const float invH = static_cast<float>(ORBGPU_FRAME_GRID_ROWS) / static_cast<float>(maxY - minY);
+    ResidentFrame f;
+    check(orb_frame_create_from_extract(ctx, &dist, n, d_descriptors, d_keysRaw, d_uRight, minX, minY, invW, invH, &f.h_),
+          "ResidentFrame::FromExtraction");
+    f.n_ = n;
+    f.hasURight_ = d_uRight != nullptr;
+    return f;
+}
+
+std::vector<ResidentFrame> ResidentFrame::FromBatch(orb_ctx* ctx, const orb_distortion& dist, int nframes,
+                                                    const uint8_t* d_descriptors, const KeyPoint* d_keysRaw,
+                                                    const int* d_counts, int kp_cap, float minX, float maxX, float minY,
+                                                    float maxY) {
+    const float invW = static_cast<float>(ORBGPU_FRAME_GRID_COLS) / static_cast<float>(maxX - minX);
+    const float invH = static_cast<float>(ORBGPU_FRAME_GRID_ROWS) / static_cast<float>(maxY - minY);
+    std::vector<orb_frame*> h((size_t)std::max(nframes, 0), nullptr);
+    std::vector<ResidentFrame> out(h.size());   // (allocated before the handles exist: nothing can throw after)
+    check(orb_frames_create_from_batch(ctx, &dist, nframes, d_descriptors, d_keysRaw, d_counts, kp_cap, minX, minY, invW,
+                                       invH, h.data()),
+          "ResidentFrame::FromBatch");
+    for (size_t f = 0; f < h.size(); f++) {
+        out[f].h_ = h[f];
+        out[f].n_ = orb_frame_count(h[f]);
+    }
+    return out;
+}
+
+namespace {
+orb_distortion distortion_of(float fx, float fy, float cx, float cy, const float distCoef[4]) {
+    orb_distortion d;
+    d.fx = fx;
+    d.fy = fy;
+    d.cx = cx;
+    d.cy = cy;
+    for (int k = 0; k < 4; k++) d.k[k] = distCoef[k];
+    return d;
+}
+}  // namespace
+
+std::vector<KeyPoint> UndistortKeyPoints(float fx, float fy, float cx, float cy, const float distCoef[4],
+                                         const std::vector<KeyPoint>& keys) {
+    const orb_distortion d = distortion_of(fx, fy, cx, cy, distCoef);
+    std::vector<KeyPoint> keysUn(keys.size());
+    check(orb_undistort_keypoints(matcher_ctx(), &d, (int)keys.size(), keys.data(), keysUn.data(), nullptr),
+          "UndistortKeyPoints");
+    return keysUn;
+}
+
+void ComputeImageBounds(float fx, float fy, float cx, float cy, const float distCoef[4], int cols, int rows, float& minX,
+                        float& maxX, float& minY, float& maxY) {
+    const orb_distortion d = distortion_of(fx, fy, cx, cy, distCoef);
+    check(orb_image_bounds(&d, cols, rows, &minX, &maxX, &minY, &maxY), "ComputeImageBounds");
+}
+
 ResidentFrame::~ResidentFrame() { orb_frame_destroy(h_); }
 
 ResidentFrame::ResidentFrame(ResidentFrame&& o) noexcept : h_(o.h_), n_(o.n_), hasURight_(o.hasURight_) {

@@ -62,6 +62,16 @@ private:
     std::vector<std::vector<size_t> > cells_;   // [ix * ROWS + iy]
 };
 
+// Frame::UndistortKeyPoints (Frame.cc:571-603) on the GPU: mvKeysUn from mvKeys, mK's entries and mDistCoef's four
+// floats (cv::fisheye::undistortPoints as the reference calls it; distCoef[0] == 0 returns the keypoints unchanged).
+// The bytes are those of the library's CPU definition, orb_undistort_points_host.  Runs on the calling thread's
+// matcher context; failures throw OrbGpuError.
+std::vector<KeyPoint> UndistortKeyPoints(float fx, float fy, float cx, float cy, const float distCoef[4],
+                                         const std::vector<KeyPoint>& keys);
+// Frame::ComputeImageBounds (Frame.cc:605-660): mnMinX, mnMaxX, mnMinY, mnMaxY of a cols x rows image (CPU)
+void ComputeImageBounds(float fx, float fy, float cx, float cy, const float distCoef[4], int cols, int rows, float& minX,
+                        float& maxX, float& minY, float& maxY);
+
 // A Frame's or KeyFrame's train side kept on the device (the C-ABI's orb_frame): descriptors, undistorted keypoints
 // and optionally mvuRight are uploaded once and the library builds the grid on the GPU, so a frame that is searched
 // several times is not staged again.  Constructed like a FrameGrid, plus the arrays the searches read; the arrays
@@ -81,6 +91,18 @@ public:
     // from arrays already in the memory of ctx's GPU (e.g. a slot of orb_extract_batch_device's outputs)
     static ResidentFrame FromDevice(orb_ctx* ctx, int n, const uint8_t* d_descriptors, const KeyPoint* d_keysUn,
                                     const float* d_uRight, float minX, float minY, float widthInv, float heightInv);
+    // from a slot of orb_extract_batch_device's outputs as the extractor wrote it: n descriptors and RAW keypoints.
+    // The library undistorts them on the GPU (Frame::UndistortKeyPoints) and builds the grid from the undistorted
+    // ones; the bounds are ComputeImageBounds'.  k[0] == 0 is the reference's identity path.
+    static ResidentFrame FromExtraction(orb_ctx* ctx, const orb_distortion& dist, int n, const uint8_t* d_descriptors,
+                                        const KeyPoint* d_keysRaw, const float* d_uRight, float minX, float maxX,
+                                        float minY, float maxY);
+    // the same for all nframes slots of a batch (frame f's arrays at f * kp_cap, its count in d_counts[f]): one
+    // undistort launch for the whole batch
+    static std::vector<ResidentFrame> FromBatch(orb_ctx* ctx, const orb_distortion& dist, int nframes,
+                                                const uint8_t* d_descriptors, const KeyPoint* d_keysRaw,
+                                                const int* d_counts, int kp_cap, float minX, float maxX, float minY,
+                                                float maxY);
     ~ResidentFrame();
     ResidentFrame(ResidentFrame&& o) noexcept;
     ResidentFrame& operator=(ResidentFrame&& o) noexcept;

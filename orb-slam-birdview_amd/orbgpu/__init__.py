@@ -12,11 +12,12 @@ import numpy as np
 
 from ._lib import (VARIANT_BLUR_HALFUP, VARIANT_DEFAULT, VARIANT_NO_FMA, VARIANT_RESIZE_GENERIC,
                    VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, OrbProjFrameTarget,
-                   OrbProjTarget, OrbCamera, OrbFusePointsTarget, KfdbNeighboursFn, check, lib)
+                   OrbProjTarget, OrbCamera, OrbDistortion, OrbFusePointsTarget, KfdbNeighboursFn, check, lib)
 
 __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError", "device_count",
            "features_in_area", "frame_grid", "Frame", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
            "PROJ_GATE_NONE", "PROJ_GATE_FUSE", "proj_queries", "project_best_host",
+           "distortion", "undistort_points_host", "image_bounds", "undistort_keypoints", "undistort_guard",
            "MapPoints", "POINT_PROJ_DTYPE", "FRUSTUM_FRAME", "FRUSTUM_FUSE", "camera", "project_points_host",
            "compute_stereo_matches", "ORBVocabulary", "KeyFrameDatabase", "bow_score", "KFDB_RELOC", "KFDB_LOOP",
            "BirdORB", "cornerSubPix",
@@ -367,8 +368,64 @@ class Frame:
                      None if d_uright is None else vp(d_uright), bounds, inv, min_xy)
         return self
 
-    def _create(self, fn, ctx_or_matcher, n, desc, kps, ur, bounds, inv, min_xy):
+    @classmethod
+    def from_extraction(cls, ctx_or_matcher, dist, n, d_desc, d_kps_raw, bounds=None, inv=None, d_uright=None,
+                        min_xy=(0.0, 0.0)):
+        """A Frame from n descriptors and RAW keypoints in device memory (BatchExtractor.frame_slots(f)):
+        orb_frame_create_from_extract undistorts them on the GPU (dist: distortion(...)) and builds the grid from the
+        undistorted ones, so the extraction's output becomes a searchable frame without leaving the device.  bounds
+        is image_bounds(dist, w, h)."""
+        self = cls.__new__(cls)
+        vp = ctypes.c_void_p
+        self._create("orb_frame_create_from_extract", ctx_or_matcher, int(n), vp(d_desc), vp(d_kps_raw),
+                     None if d_uright is None else vp(d_uright), bounds, inv, min_xy, dist=dist)
+        return self
+
+    @classmethod
+    def from_batch(cls, ctx_or_matcher, dist, nframes, d_desc, d_kps_raw, d_counts, kp_cap, bounds=None, inv=None,
+                   min_xy=(0.0, 0.0)):
+        """nframes Frames from a whole batch in orb_extract_batch_device's output layout (BatchExtractor's d_desc,
+        d_kps, d_counts, kp_cap): orb_frames_create_from_batch, one undistort launch for all frames."""
+        proto = cls.__new__(cls)
+        proto.h = None
+        proto._set_grid(bounds, inv, min_xy)
+        vp = ctypes.c_void_p
+        handles = (vp * max(int(nframes), 1))()
+        fn = "orb_frames_create_from_batch"
+        check(getattr(lib(), fn)(_ctx_handle(ctx_or_matcher), ctypes.byref(dist), int(nframes), vp(d_desc),
+                                 vp(d_kps_raw), vp(d_counts), int(kp_cap), proto.min_xy[0], proto.min_xy[1],
+                                 proto.inv[0], proto.inv[1], handles), fn)
+        frames = []
+        for f in range(int(nframes)):
+            self = cls.__new__(cls)
+            self.min_xy, self.inv, self.has_uright = proto.min_xy, proto.inv, False
+            self.h = vp(handles[f])
+            self.n = lib().orb_frame_count(self.h)
+            frames.append(self)
+        return frames
+
+    def _set_grid(self, bounds, inv, min_xy):
+        assert (bounds is None) != (inv is None), "give bounds=(min_x, max_x, min_y, max_y) or inv=(inv_w, inv_h)"
+        f32 = np.float32
+        if bounds is not None:
+            min_x, max_x, min_y, max_y = bounds
+            inv_w = f32(64) / (f32(max_x) - f32(min_x))   # Frame.cc:102-103, as frame_grid()
+            inv_h = f32(48) / (f32(max_y) - f32(min_y))
+        else:
+            (min_x, min_y), (inv_w, inv_h) = min_xy, inv
+        self.min_xy, self.inv = (float(f32(min_x)), float(f32(min_y))), (float(inv_w), float(inv_h))
+
+    def _create(self, fn, ctx_or_matcher, n, desc, kps, ur, bounds, inv, min_xy, dist=None):
         self.h = None
+        if dist is not None:
+            self._set_grid(bounds, inv, min_xy)
+            self.has_uright = ur is not None
+            out = ctypes.c_void_p()
+            check(getattr(lib(), fn)(_ctx_handle(ctx_or_matcher), ctypes.byref(dist), n, desc, kps, ur, self.min_xy[0],
+                                     self.min_xy[1], self.inv[0], self.inv[1], ctypes.byref(out)), fn)
+            self.h = out
+            self.n = lib().orb_frame_count(self.h)
+            return
         assert (bounds is None) != (inv is None), "give bounds=(min_x, max_x, min_y, max_y) or inv=(inv_w, inv_h)"
         f32 = np.float32
         if bounds is not None:
@@ -403,6 +460,49 @@ class Frame:
 
     def __del__(self):
         self.close()
+
+
+def distortion(fx, fy, cx, cy, k):
+    """orb_distortion from mK's entries and mDistCoef's four floats (Camera.k1, k2, p1, p2 in Tracking.cc's order; the
+    fisheye model reads them as k1..k4), all taken as float32."""
+    k = np.asarray(k, np.float32).ravel()
+    assert len(k) == 4, "four coefficients (a fifth is out of scope: cv::fisheye::undistortPoints asserts on it)"
+    d = OrbDistortion()
+    d.fx, d.fy, d.cx, d.cy = (float(np.float32(v)) for v in (fx, fy, cx, cy))
+    d.k[:] = [float(v) for v in k]
+    return d
+
+
+def undistort_points_host(dist, xy):
+    """orb_undistort_points_host: cv::fisheye::undistortPoints as Frame::UndistortKeyPoints calls it, on the CPU (the
+    definition the GPU forms equal byte for byte).  xy: (n, 2) float32; no context, no GPU."""
+    p = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    out = np.zeros_like(p)
+    check(lib().orb_undistort_points_host(ctypes.byref(dist), len(p), _p(p), _p(out)), "orb_undistort_points_host")
+    return out
+
+
+def image_bounds(dist, w, h):
+    """orb_image_bounds: Frame::ComputeImageBounds' (mnMinX, mnMaxX, mnMinY, mnMaxY) as float32; no context, no GPU."""
+    b = [ctypes.c_float() for _ in range(4)]
+    check(lib().orb_image_bounds(ctypes.byref(dist), int(w), int(h), *[ctypes.byref(v) for v in b]), "orb_image_bounds")
+    return np.array([v.value for v in b], np.float32)
+
+
+def undistort_keypoints(ctx_or_matcher, dist, kps):
+    """orb_undistort_keypoints: Frame::UndistortKeyPoints on the GPU.  Returns (mvKeysUn, n_redone): the keypoints with
+    x, y undistorted (the bytes of undistort_points_host) and how many the host recomputed."""
+    k = np.ascontiguousarray(kps, KP_DTYPE)
+    out = np.zeros(len(k), KP_DTYPE)
+    n = ctypes.c_int(0)
+    check(lib().orb_undistort_keypoints(_ctx_handle(ctx_or_matcher), ctypes.byref(dist), len(k), _p(k), _p(out),
+                                        ctypes.byref(n)), "orb_undistort_keypoints")
+    return out, n.value
+
+
+def undistort_guard(ctx_or_matcher, g=0.0):
+    """orb_debug_undistort_guard: the guard band's relative half-width for this context (0: the default)."""
+    check(lib().orb_debug_undistort_guard(_ctx_handle(ctx_or_matcher), float(g)), "orb_debug_undistort_guard")
 
 
 def camera(Rcw, tcw, Ow, fx, fy, cx, cy, mbf, bounds, scale_factors, log_scale_factor):

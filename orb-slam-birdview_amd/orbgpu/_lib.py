@@ -67,6 +67,10 @@ class OrbCamera(ctypes.Structure):   # orb_camera
                 ("log_scale_factor", cf), ("scale_factors", cf * 16)]
 
 
+class OrbDistortion(ctypes.Structure):   # orb_distortion
+    _fields_ = [("fx", cf), ("fy", cf), ("cx", cf), ("cy", cf), ("k", cf * 4)]
+
+
 class OrbFusePointsTarget(ctypes.Structure):   # orb_fuse_points_target
     _fields_ = [("camera", OrbCamera), ("frame", vp), ("inv_sigma2", vp), ("th", cf), ("n", ci), ("ids", vp),
                 ("best_idx", vp), ("best_dist", vp), ("proj_out", vp)]
@@ -136,6 +140,16 @@ SIGNATURES = {
     "orb_window_match_frame": (ci, [vp, cf, ci, ci, ci, vp, vp, vp, cf, vp, vp, ctypes.POINTER(ci)]),
     "orb_search_by_match_bird_resident": (ci, [vp, cf, ci, ci, cf, ci, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ci)]),
     "orb_project_best_frames": (ci, [vp, ci, ci, vp]),
+    "orb_undistort_points_host": (ci, [ctypes.POINTER(OrbDistortion), ci, vp, vp]),
+    "orb_image_bounds": (ci, [ctypes.POINTER(OrbDistortion), ci, ci, ctypes.POINTER(cf), ctypes.POINTER(cf),
+                              ctypes.POINTER(cf), ctypes.POINTER(cf)]),
+    "orb_undistort_keypoints": (ci, [vp, ctypes.POINTER(OrbDistortion), ci, vp, vp, ctypes.POINTER(ci)]),
+    "orb_undistort_keypoints_device": (ci, [vp, ctypes.POINTER(OrbDistortion), ci, vp, vp, ci, vp,
+                                            ctypes.POINTER(ci)]),
+    "orb_frame_create_from_extract": (ci, [vp, ctypes.POINTER(OrbDistortion), ci, vp, vp, vp, cf, cf, cf, cf,
+                                           ctypes.POINTER(vp)]),
+    "orb_frames_create_from_batch": (ci, [vp, ctypes.POINTER(OrbDistortion), ci, vp, vp, vp, ci, cf, cf, cf, cf, vp]),
+    "orb_debug_undistort_guard": (ci, [vp, ctypes.c_double]),
     "orb_points_create": (ci, [vp, ci, ctypes.POINTER(vp)]),
     "orb_points_write": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
     "orb_points_capacity": (ci, [vp]),
