@@ -45,8 +45,8 @@ typedef enum {
     ORB_ERR_CAPACITY = -3,   /* caller buffer too small; *n receives the required count          */
     ORB_ERR_GEOMETRY = -4,   /* image too small for the pyramid (reference: division by zero UB), a side
                                 above 4096 pixels (candidates pack 12-bit coordinates), or a level whose
-                                octree node tables exceed one CU's LDS (N per level above ~2,550, i.e.
-                                nfeatures above ~11,700 at scale 1.2 / 8 levels) */
+                                octree node tables exceed one CU's LDS (N per level above 2,488: 2,496 nodes of
+                                64 bytes; about nfeatures 11,450 at scale 1.2 / 8 levels, 2,488 at one level) */
     ORB_ERR_NOMEM = -5,      /* device allocation failed                                         */
     ORB_ERR_INTERNAL = -6    /* a kernel reported an overflow of an internal bound               */
 } orb_status;

@@ -1357,6 +1357,10 @@ __device__ __forceinline__ int quad_mask(const int* qd) {
  * tables of depths R..0 in rank order.  The round loop then continues from round R (phase 2, or phase
  * 1 past depth F) exactly as before. */
 constexpr int kFfMaxDepth = 6;
+// a placed table entry: the cell's key count in the low kFfPosShift bits (C < 1 << 20 or no fast-forward), the
+// node's list position in the 12 bits above (node_cap <= kFfMaxNodes: the host check next to octree_lds_bytes)
+constexpr int kFfPosShift = 20;
+static_assert(kFfMaxNodes <= 1 << (32 - kFfPosShift), "a list position must fit above the count");
 
 // depth F of the tables: the first depth whose cells can hold N nodes (phase 1 usually switches to phase 2
 // the round before, so phase 2's first round still finds its quadrant counts in the table), at most what
@@ -1578,7 +1582,7 @@ __device__ __forceinline__ void octree_level(const Geom* __restrict__ g, const L
                 // creation order in round R is the reverse of the rank (phase 2's tie key, :684); the
                 // one-key nodes are never divided and their seq is never read
                 seqA[pos] = d == 0 ? -1 - t : d == R ? base + DR - 1 - pos : base;
-                td[c] = n | (pos << 20);
+                td[c] = (int)((uint32_t)n | ((uint32_t)pos << kFfPosShift));
                 if (d == R) ryB[pos] = (uint32_t)c;   // the node's depth-R cell (phase 2's quadrant counts)
             }
             run += tot;
@@ -1593,7 +1597,7 @@ __device__ __forceinline__ void octree_level(const Geom* __restrict__ g, const L
                 const int c = code >> (2 * (F - d));
                 const int e = d == 0 ? cntB[c] : T[ff_base(nIni, d) + c];
                 if (d == R || (e & 0xFFFFF) == 1) {
-                    node = e >> 20;
+                    node = (int)((uint32_t)e >> kFfPosShift);   // unsigned: a position >= 2048 sets the word's sign bit
                     break;
                 }
             }
@@ -1603,7 +1607,8 @@ __device__ __forceinline__ void octree_level(const Geom* __restrict__ g, const L
         // table's, so its first round needs no pass over the keys (read here, written once every read of
         // the tables is done: quad aliases them)
         if (ph2 && R + 1 <= F) {
-            constexpr int kMaxPer = 8;   // node_cap <= 8 * NT (host: octree_lds_bytes <= 160 KiB)
+            constexpr int kMaxPer = 8;   // node_cap <= 8 * NT (host: node_cap <= kFfMaxNodes, next to octree_lds_bytes)
+            static_assert(kMaxPer * NT >= kFfMaxNodes, "every node of the list is read by some thread");
             int4 qv[kMaxPer];
             const int* tq = T + ff_base(nIni, R + 1);
 #pragma unroll

@@ -212,7 +212,10 @@ int build_geometry(Ctx* c, int W, int H, Geom& g, std::vector<ResizeCoef>& coefs
     nc = (nc + 63) & ~63;
     g.node_cap = nc;
     fast_wave_layout(g);
-    if (g.fast_wave_bytes > 64 * 1024 || octree_lds_bytes(nc) > 160 * 1024) return ORB_ERR_GEOMETRY;
+    // (the LDS limit allows 2496 nodes, i.e. a level of at most 2488 features; the fast-forward's packed list
+    // positions hold up to kFfMaxNodes, and so does phase 2's table read of 8 nodes per thread at kOctreeThreads and
+    // above: the static_asserts in octree_level)
+    if (g.fast_wave_bytes > 64 * 1024 || octree_lds_bytes(nc) > 160 * 1024 || nc > kFfMaxNodes) return ORB_ERR_GEOMETRY;
     return ORB_OK;
 }
 

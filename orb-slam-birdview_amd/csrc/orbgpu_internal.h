@@ -17,6 +17,7 @@ constexpr int kMaxDim = 4096;         // candidate coordinates are packed in 12 
 constexpr int kFastTilePitch = 80;    // 16-bit elements per FAST tile row (ROI <= 66 px, prefilter window <= 74)
 constexpr int kFastMaxRoi = 66;
 constexpr int kOctreeThreads = 512;
+constexpr int kFfMaxNodes = 4096;   // k_octree's fast-forward packs a node's list position into 12 bits
 constexpr int kCandRec = 8;           // dwords per cell in d_candFirst: [corner count | first kCandFirst corners]
 constexpr int kCandFirst = kCandRec - 1;
 constexpr int kDescWin = 43;          // unblurred window: radius 18 (BRIEF) + 3 (blur taps)

@@ -399,7 +399,7 @@ def test_maximum_sizes_bit_exact(orbgpu_mod, oracle_mod, w, h, nf, kind, batch):
 
 def test_geometry_limits_are_errors(orbgpu_mod):
     """The documented limits (include/orbgpu.h): a side above 4096 pixels, and a level whose
-    octree node tables would not fit one CU's LDS (level-0 N above ~2,550: nfeatures > ~11,700 at 1.2/8)."""
+    octree node tables would not fit one CU's LDS (level-0 N above 2,488: nfeatures above about 11,450 at 1.2/8)."""
     from orbgpu._lib import OrbError
     g = orbgpu_mod.ORBextractor(1000, 1.2, 8, 20, 7)
     with pytest.raises(OrbError):

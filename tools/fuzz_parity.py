@@ -37,8 +37,9 @@ def level0_target(nf, sf, nl):
     return nf * (1 - f) / (1 - f ** nl) if nl > 1 else float(nf)
 
 
-# orbgpu.h, ORB_ERR_GEOMETRY: a level whose octree node tables exceed one CU's LDS (N per level above ~2,550)
-LDS_LEVEL_BOUND = 2500
+# orbgpu.h, ORB_ERR_GEOMETRY: a level whose octree node tables exceed one CU's LDS (N per level above 2,488:
+# 2,496 nodes of 64 bytes)
+LDS_LEVEL_BOUND = 2488
 
 
 def extract_case(s):
