@@ -745,6 +745,10 @@ void build_cells(const Geom& g, std::vector<CellDesc>& cells) {
                 d.m_nw = (int)recip20((uint32_t)nw);
                 d.runs = nruns | ((64 / nruns) << 8);
                 d.m_runs = (int)recip20((uint32_t)nruns);
+                // rows past the last full round of 64 / nruns rows: as pixel pairs, if they fit one wave
+                const int np = std::max(1, (rw - 6 + 1) / 2), trows = rh - 6 > 0 ? (rh - 6) % (64 / nruns) : 0;
+                d.tail = (trows * np <= 64 ? trows : 0) | (np << 8);
+                d.m_np = (int)recip20((uint32_t)np);
             }
     }
 }
@@ -756,7 +760,7 @@ __device__ __forceinline__ unsigned roi_off(int yy, int stride, int cb) {
 }
 
 struct FastCellT {
-    int f, cell, iniX, rw, rh, dw, dh, x0w, nw, rpr, m_nw, nruns, rpi, m_runs, out_off, xo, yo;
+    int f, cell, iniX, rw, rh, dw, dh, x0w, nw, rpr, m_nw, nruns, rpi, m_runs, ntail, np, m_np, out_off, xo, yo;
     bool valid, aligned;
     const uint8_t* base;   // ROI row 0, column 0
     int stride;
@@ -790,6 +794,9 @@ __device__ __forceinline__ FastCellT fast_cell_t(const Geom* __restrict__ g, con
     c.nruns = d.runs & 0xFF;
     c.rpi = (d.runs >> 8) & 0xFF;
     c.m_runs = d.m_runs;
+    c.ntail = d.tail & 0xFF;
+    c.np = d.tail >> 8;
+    c.m_np = d.m_np;
     return c;
 }
 
@@ -1028,10 +1035,19 @@ __device__ __forceinline__ uint32_t prefilter16(lds_cu32* w, uint32_t tt) {   //
 // Stage 1 of a cell at threshold tt: the prefilter over every domain row, survivors compacted into
 // sList in raster order (one wave prefix sum of the per-lane counts per row round, then each lane
 // writes its entries at its offset).  Returns the list length.
-template <int TQ>
+//
+// Tail rows (TAIL): a cell of 33-35 rows at two runs per row would pay a whole second row round for its last
+// 1-3 rows, with at most 6 lanes busy.  Where the rows past the last full round fit the wave as one pixel pair
+// per lane (c.ntail rows of c.np pairs, the host's choice, wave-uniform), they run in that form instead:
+// lane -> (tail row, pair) in raster order, one compass2 per lane, and the list position from two ballots
+// (the pair's low pixels, its high pixels) — no scan and no bit loop.
+template <int TQ, bool TAIL>
 __device__ __forceinline__ int prefilter_cell(const uint32_t* t32, int dh, int rpi, int lrow, bool lane_on, int lbase,
-                                              uint32_t xvalid, uint32_t tt, uint16_t* sList) {
+                                              uint32_t xvalid, uint32_t tt, uint16_t* sList, const FastCellT& c,
+                                              const uint16_t* tile, int lane) {
     int nlist = 0;
+    const int ntail = TAIL ? __builtin_amdgcn_readfirstlane(c.ntail) : 0;
+    dh -= ntail;   // the full rounds' rows (a multiple of rpi where ntail != 0)
     for (int r0 = 0; r0 < dh; r0 += rpi) {
         const int dy = r0 + lrow;
         int pm = 0;
@@ -1051,6 +1067,29 @@ __device__ __forceinline__ int prefilter_cell(const uint32_t* t32, int dh, int r
         // one iteration per set bit (survivors are sparse: the wave runs max-popcount iterations)
         for (uint32_t b = (uint32_t)pm; b; b &= b - 1) sList[pos++] = (uint16_t)(base + 2 * __builtin_ctz(b));
         nlist += __builtin_amdgcn_readlane(incl, 63);
+    }
+    if (TAIL && ntail != 0) {   // wave-uniform
+        const int np = __builtin_amdgcn_readfirstlane(c.np);
+        const int trow = (int)div20(lane, c.m_np), pp = lane - trow * np;   // tail row, pixel pair (x = 2 pp)
+        uint32_t r = 0;
+        if (trow < ntail) {
+            // the pair's dword: domain pixel (x, y) is tile element (y + 3) * TQ + x + 4
+            lds_cu32* q = (lds_cu32*)(reinterpret_cast<const uint32_t*>(tile) + ((dh + 3) * (TQ / 2) + 2)) +
+                          (trow * (TQ / 2) + pp);
+            const uint32_t l2 = q[-2], l1 = q[-1], v = q[0], r1 = q[1], r2 = q[2];
+            const uint32_t P12 = __builtin_amdgcn_alignbyte(l1, l2, 2);   // columns x - 3, x - 2
+            const uint32_t P4 = __builtin_amdgcn_alignbyte(r2, r1, 2);    // columns x + 3, x + 4
+            r = compass2(v, q[3 * (TQ / 2)], P4, q[-3 * (TQ / 2)], P12, tt);
+        }
+        const bool lo = (r & 0x8000u) != 0, hi = (int)r < 0 && 2 * pp + 1 < c.dw;   // the pair's high pixel may lie past dw
+        const unsigned long long ml = __ballot(lo), mh = __ballot(hi);
+        // raster order: every pixel of the lanes below, then the lane's own low pixel
+        const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(mh >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mh,
+                        __builtin_amdgcn_mbcnt_hi((unsigned)(ml >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ml, nlist))));
+        const int e = (dh + trow) * (2 * TQ) + 4 * pp;   // byte offset from domain pixel (0, 0), as above
+        if (lo) sList[pos] = (uint16_t)e;
+        if (hi) sList[pos + (lo ? 1 : 0)] = (uint16_t)(e + 2);
+        nlist += __popcll(ml) + __popcll(mh);
     }
     return nlist;
 }
@@ -1090,7 +1129,9 @@ __device__ __forceinline__ void fast_cell_body(const Geom* __restrict__ g, const
         // ---- stage 1: compass prefilter at th, 8 pixels per lane as 16-bit pixel pairs, survivors
         // compacted into sList by one wave scan
         const uint32_t tt = (uint32_t)th | ((uint32_t)th << 16);
-        const int nlist = prefilter_cell<TQ>(t32, dh, rpi, lrow, lane_on, 2 * lpix, xvalid, tt, sList);
+        // (the tail form is for the compact pitch's cells: at kFastTilePitch a row's pairs leave room for one row)
+        const int nlist = prefilter_cell<TQ, (TQ < kFastTilePitch)>(t32, dh, rpi, lrow, lane_on, 2 * lpix, xvalid, tt,
+                                                                    sList, c, tile, lane);
         wave_lds_sync();
         ORBGPU_STAMP(2);
 #if defined(ORBGPU_FAST_CUT) && ORBGPU_FAST_CUT == 2

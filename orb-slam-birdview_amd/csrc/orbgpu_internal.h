@@ -109,7 +109,10 @@ struct CellDesc {
     int m_nw;      // recip20(nw)
     int runs;      // prefilter: 16-pixel runs per row nruns | rows per round (64 / nruns) << 8
     int m_runs;    // recip20(nruns)
-    int pad[4];    // 64 bytes: one scalar dwordx16 load
+    int tail;      // prefilter tail: rows past the last full row round, run as one pixel pair per lane (0: none, or
+                   // they do not fit 64 lanes) | pixel pairs per row np = (dw + 1) / 2 << 8
+    int m_np;      // recip20(np)
+    int pad[2];    // 64 bytes: one scalar dwordx16 load
 };
 // q = x / n for x < 2^20 / n, from m = recip20(n) (host and device)
 __host__ __device__ inline uint32_t recip20(uint32_t n) { return ((1u << 20) + n - 1) / n; }
