@@ -290,7 +290,7 @@ __device__ __forceinline__ void resize_tile(const Geom* __restrict__ g, const Re
     const int pitch = g->L[level].pitch;
     const unsigned dcol = (unsigned)(x0 + tx);
     if (tx >= nx) return;
-    // The 4 pixels' source bytes lie within 8 bytes from o0[0] (scale factor <= ~1.6; otherwise the
+    // The 4 pixels' source bytes lie within 8 bytes from o0[0] (scale factors up to 2; otherwise the
     // byte path below): a row's 3 dwords from LDS, realigned to o0[0], give each pixel's byte pair as
     // 16-bit lanes through one v_perm, and the horizontal sum is one v_dot2 with (c0, c1).
     const int bo = o0[0];
@@ -575,7 +575,7 @@ __device__ __forceinline__ void chain_job(const Geom* __restrict__ g, const Resi
             const int q = qb + (tid & (QW - 1));
             const bool qon = q < nq;
             // the dword group's 4 pixels: source byte offsets, weights; their bytes lie within 8 from bo
-            // when the scale factor is <= ~1.6 (then 3 dwords + v_perm + v_dot2 per row, else bytes)
+            // when the scale factor is at most 2 (then 3 dwords + v_perm + v_dot2 per row, else bytes)
             int o0[4], o1[4];
             unsigned c0[4], c1[4];
 #pragma unroll

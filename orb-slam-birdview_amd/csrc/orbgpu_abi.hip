@@ -238,8 +238,8 @@ static hipError_t grow(T*& p, size_t& cap, size_t need) {
  * level base .. l-1 its pixels depend on, walked back through the resize coefficient tables (monotone:
  * a region's span is its end columns' / rows' source indices).  Regions above the base start at a
  * multiple of 4 and span a multiple of 4 columns; the base region is clipped to the level. */
-static void build_chain(const Geom& g, const std::vector<ResizeCoef>& coefs, const int* off, std::vector<ChainJob>& jobs,
-                        ChainPlan& plan, int first_base, int seg_len) {
+void build_chain(const Geom& g, const std::vector<ResizeCoef>& coefs, const int* off, std::vector<ChainJob>& jobs,
+                 ChainPlan& plan, int first_base, int seg_len) {
     jobs.clear();
     plan = ChainPlan{};
     const int nl = g.nlevels;
@@ -282,7 +282,12 @@ static void build_chain(const Geom& g, const std::vector<ResizeCoef>& coefs, con
         sg.buf_bytes = (bufb + 15) & ~15;
         sg.coef_entries = coefe;
         sg.lds_bytes = 2 * sg.buf_bytes + 16 * coefe;
-        if (sg.lds_bytes > 64 * 1024) {   // wide images keep the per-level launches
+        // A tile's regions grow with the scale factor and with the levels a segment chains, not with the image:
+        // 2560 x 1440 at 1.2 takes 15456 bytes, while at 1280 x 720 a segment of kChainSeg levels takes 63328 bytes
+        // at 1.6 and passes 64 KiB at 1.7, and at 1.9 three levels from the frame take 61840 bytes and four are
+        // refused, at 820 x 820 too (test_the_plan_is_refused_by_scale_and_depth, tests/test_pyramid_chain_host.py).
+        // Such pyramids keep the per-level launches.
+        if (sg.lds_bytes > 64 * 1024) {
             jobs.clear();
             plan = ChainPlan{};
             return;

@@ -419,6 +419,11 @@ hipError_t launch_upload_stream(const uint8_t* h_img, const uint32_t* h_flags, u
 
 // OpenCV 3.2 resize INTER_LINEAR coefficients for sw -> dw (orbgpu_abi.hip), appended to `out`
 void resize_coefs(int sw, int dw, std::vector<ResizeCoef>& out, bool vertical);
+// The few-launch pyramid's plan for geometry g (level sizes, pitches) and its coefficient tables (coefs, per-level
+// offsets off): segments of up to seg_len levels from level first_base on; plan.nseg == 0 when it does not fit the
+// LDS (orbgpu_abi.hip; tests/cpp_pyramid_chain walks its jobs on the host)
+void build_chain(const Geom& g, const std::vector<ResizeCoef>& coefs, const int* off, std::vector<ChainJob>& jobs,
+                 ChainPlan& plan, int first_base, int seg_len);
 size_t octree_lds_bytes(int node_cap);
 void fast_wave_layout(Geom& g);   // fills fast_rows/drows/list/wave_bytes from the level grids
 void build_cells(const Geom& g, std::vector<CellDesc>& cells);

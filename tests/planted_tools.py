@@ -1,5 +1,7 @@
 """What the planted-decision case files of the matchers share (tests/bow_cases.py, tests/triangulation_cases.py):
-the two-sided builder of descriptors and FeatureVectors, and the rotation-histogram pair lists.  Pure numpy."""
+the two-sided builder of descriptors and FeatureVectors, and the rotation-histogram pair lists.  Pure numpy.
+Also batch_levels, the pyramid levels of a batched extraction from a device buffer the test lays out
+(tests/test_gpu_resize_rows.py, tests/test_gpu_pyramid_small.py)."""
 import collections
 
 import numpy as np
@@ -23,6 +25,31 @@ ROT_TIED = ROT_BIN0 + [(0.0, 0.0)] * 6 + ROT_BIN1 + [(30.0, 0.0)] * 7 + [(150.0,
 ROT_TIED_EXPECTED = Rot(("rot_negative_wrap", "rot_bin_30_to_0", "rot_round_half", "maxima_first_second_tied",
                          "maxima_third_tied_first_wins", "maxima_third_at_cutoff_kept"),
                         sizes({0: 10, 1: 10, 5: 1, 12: 1}), (0, 1, 5), 1)
+
+
+def batch_levels(orbgpu_mod, frames, scale, nlevels, variant, stride, base_off=0, runs=1):
+    """Pyramid levels 1.. of every frame after each of `runs` batched extractions (the graph's capture, then replays)
+    from a device buffer with row stride `stride` that starts `base_off` bytes into its allocation: [run][frame][l - 1]."""
+    from orbgpu._lib import check, lib
+    n, h, w = frames.shape
+    e = orbgpu_mod.BatchExtractor(500, w, h, n, scale_factor=scale, nlevels=nlevels, variant=variant)
+    padded = np.full((n, h, stride), 0xA5, np.uint8)   # the pad bytes are never read: any value must do
+    padded[:, :, :w] = frames
+    host = np.full(base_off + padded.nbytes, 0xA5, np.uint8)
+    host[base_off:] = padded.reshape(-1)
+    d = e._alloc(host.nbytes)
+    try:
+        check(lib().orb_memcpy_h2d(e.h, d, host.ctypes.data, host.nbytes), "h2d")
+        out = []
+        for _ in range(runs):
+            check(lib().orb_extract_batch_device(e.h, d + base_off, n, w, h, stride * h, stride, e.d_kps, e.d_desc,
+                                                 e.d_counts, e.kp_cap), "orb_extract_batch_device")
+            e.sync()
+            out.append([[e.debug_level_image(l, f) for l in range(1, nlevels)] for f in range(n)])
+        return out
+    finally:
+        lib().orb_device_free(e.h, d)
+        e.close()
 
 
 class Builder:

@@ -14,6 +14,8 @@ tests/test_resize_rows_host.py."""
 import numpy as np
 import pytest
 
+from gpu_tools import batch_levels
+
 pytestmark = pytest.mark.gpu
 
 B = 3
@@ -22,21 +24,7 @@ RESIZE = 2   # VARIANT_RESIZE_GENERIC == ORACLE_RESIZE_GENERIC (tests/test_abi_c
 
 def _levels(orbgpu_mod, frames, scale, nlevels, variant, stride):
     """Pyramid levels 1.. of every frame after one batched extraction from a device buffer with row stride `stride`."""
-    from orbgpu._lib import check, lib
-    n, h, w = frames.shape
-    e = orbgpu_mod.BatchExtractor(500, w, h, n, scale_factor=scale, nlevels=nlevels, variant=variant)
-    padded = np.full((n, h, stride), 0xA5, np.uint8)   # the pad bytes are never read: any value must do
-    padded[:, :, :w] = frames
-    d = e._alloc(padded.nbytes)
-    try:
-        check(lib().orb_memcpy_h2d(e.h, d, padded.ctypes.data, padded.nbytes), "h2d")
-        check(lib().orb_extract_batch_device(e.h, d, n, w, h, stride * h, stride, e.d_kps, e.d_desc, e.d_counts,
-                                             e.kp_cap), "orb_extract_batch_device")
-        e.sync()
-        return [[e.debug_level_image(l, f) for l in range(1, nlevels)] for f in range(n)]
-    finally:
-        lib().orb_device_free(e.h, d)
-        e.close()
+    return batch_levels(orbgpu_mod, frames, scale, nlevels, variant, stride)[0]
 
 
 @pytest.mark.parametrize("w,h,scale,nlevels,variant,stride", [
