@@ -1276,8 +1276,10 @@ __global__ __launch_bounds__(256) void k_fast_wave(const Geom* __restrict__ g, c
     }
 }
 
-// Per-wave LDS carve of k_fast_wave.  Cells at most 36 px wide (every BASELINE config) use the
-// compact tile pitch of 48 elements, wider ones 80: a tile row holds the
+// Per-wave LDS carve of k_fast_wave.  A context whose cells are at most 36 px wide on every level uses the
+// compact tile pitch of 48 elements, any other 80.  Of the BASELINE configs, 1280 x 720 (C3-C5) is compact (cells
+// of 31-33 px); 640 x 480 at 8 levels (C1, C2) is not: its level 7 (179 x 134) has 147 px over 4 columns, cells
+// 37 px wide, so every level of it runs at pitch 80 (tests/test_fast_stage_cases.py pins both).  A tile row holds the
 // widened ROI (rw + 2 elements) and an unused tail for the next row's dword -1, a multiple of 8 elements
 // (16-byte reads), with row strides of 24 / 40 dwords (2-way LDS bank conflicts at most for the
 // prefilter's 16- and 8-byte reads).

@@ -83,7 +83,8 @@ struct Geom {
     int fast_drows;      //   detection-domain rows,
     int fast_list;       //   prefilter-survivor list entries (domain pixels)
     int fast_wave_bytes; //   bytes per wave (lead pad | 16-bit tile | survivor list)
-    int fast_compact;    //   every cell <= 36 px wide: compact tile pitch (48 elements; else kFastTilePitch)
+    int fast_compact;    //   every cell of every level <= 36 px wide: compact tile pitch (48 elements; else
+                         //   kFastTilePitch: 1280 x 720 at 8 levels is compact, 640 x 480 is not, see fast_wave_layout)
     int umax[16];        // ORBextractor.cc:454-469
     int gk[8];           // 7-tap Gaussian, sigma 2, 8-bit fixed point (getGaussianKernel x 256)
     LevelGeom L[ORBGPU_MAX_LEVELS];
