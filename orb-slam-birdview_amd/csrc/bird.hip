@@ -657,35 +657,31 @@ struct Bird {
     int max_w = 0;
 
     // device
-    BirdGeom* d_geom = nullptr;
-    int2* d_rows = nullptr;         // frows | crows | brows
-    int* d_lvlrow0 = nullptr;
-    ResizeCoef* d_rcoef = nullptr;
-    int* d_pattern = nullptr;
-    float* d_wmask = nullptr;
-    uint8_t *d_pyr = nullptr, *d_mpyr = nullptr, *d_score = nullptr, *d_blur = nullptr;
-    int *d_rowcnt = nullptr, *d_rowoff = nullptr, *d_lvlcnt = nullptr;
-    BirdCand* d_cand = nullptr;
-    size_t cand_cap = 0;            // allocated candidates (>= cand_slot * nb_cap)
+    DevBuf<BirdGeom> d_geom;
+    DevBuf<int2> d_rows;            // frows | crows | brows
+    DevBuf<int> d_lvlrow0;
+    DevBuf<ResizeCoef> d_rcoef;
+    DevBuf<int> d_pattern;
+    DevBuf<float> d_wmask;
+    DevBuf<uint8_t> d_pyr, d_mpyr, d_score, d_blur;
+    DevBuf<int> d_rowcnt, d_rowoff, d_lvlcnt;
+    DevBuf<BirdCand> d_cand;        // (cap() >= cand_slot * nb_cap)
     size_t cand_slot = 0;           // candidates per frame of this geometry (the NMS bound)
     size_t cand_guess = 16384;      // candidates downloaded with the counts (next frame: this one's + 1/8)
-    orb_keypoint* d_kps = nullptr;
-    int* d_keep = nullptr;
-    int* d_kframe = nullptr;        // batch: frame of each keypoint
-    uint8_t* d_desc = nullptr;
-    size_t kp_cap = 0;
-    float* d_pts = nullptr;
-    size_t pts_cap = 0;
-    void* h_pin = nullptr;
-    size_t pin_cap = 0;
+    DevBuf<orb_keypoint> d_kps;
+    DevBuf<int> d_keep;
+    DevBuf<int> d_kframe;           // batch: frame of each keypoint
+    DevBuf<uint8_t> d_desc;
+    size_t kp_cap = 0;              // keypoints the four buffers above hold
+    DevBuf<float> d_pts;
+    PinBuf<uint8_t> h_pin;
 
     // batch form: the pyramid, score, blur and row-count buffers hold nb_cap frames fpitch() bytes (or nr + 1
     // counts) apart, the mask pyramid mnb_cap frames; the single calls use frame 0
     int nb_cap = 0, mnb_cap = 0;
     int batch_group = 4;            // frames whose keypoints go up in one upload + angle / subpix / desc launch
                                     // (measured, DESIGN 5.2: 2 .. 8 are within 5 % of each other, 1 and 64 lose more)
-    void *h_up = nullptr, *h_res = nullptr;   // pinned: keypoint uploads (device layout), second download / results
-    size_t up_cap = 0, res_cap = 0;
+    PinBuf<uint8_t> h_up, h_res;    // pinned: keypoint uploads (device layout), second download / results
     unsigned fpitch() const { return (unsigned)pyr_bytes; }
 
     // last detect (debug view): candidates per level
@@ -698,7 +694,7 @@ struct Bird {
     int ensure_mask_frames(int n);
     int ensure_kp(size_t n);
     int ensure_pin(size_t bytes);
-    int ensure_pinned(void*& p, size_t& cap, size_t bytes);
+    int ensure_pinned(PinBuf<uint8_t>& p, size_t bytes);
     int upload(const uint8_t* img, size_t stride, const uint8_t* mask, size_t mstride, bool footprint, bool device_src,
                int frame = 0, int mask_frame = 0);
     int build_pyramid(int nl, bool with_mask, int nframes = 1, int nmasks = 1);
@@ -712,15 +708,9 @@ struct Bird {
 };
 
 void Bird::free_geom() {
-    for (void* p : {(void*)d_geom, (void*)d_rows, (void*)d_lvlrow0, (void*)d_rcoef, (void*)d_pyr, (void*)d_mpyr,
-                    (void*)d_score, (void*)d_blur, (void*)d_rowcnt, (void*)d_rowoff, (void*)d_lvlcnt})
-        if (p) (void)hipFree(p);
-    d_geom = nullptr;
-    d_rows = nullptr;
-    d_lvlrow0 = nullptr;
-    d_rcoef = nullptr;
-    d_pyr = d_mpyr = d_score = d_blur = nullptr;
-    d_rowcnt = d_rowoff = d_lvlcnt = nullptr;
+    d_geom.reset(), d_rows.reset(), d_lvlrow0.reset(), d_rcoef.reset();
+    d_pyr.reset(), d_mpyr.reset(), d_score.reset(), d_blur.reset();
+    d_rowcnt.reset(), d_rowoff.reset(), d_lvlcnt.reset();
     have_geom = false;
     nb_cap = mnb_cap = 0;
 }
@@ -728,14 +718,8 @@ void Bird::free_geom() {
 Bird::~Bird() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
-    free_geom();
-    for (void* p : {(void*)d_pattern, (void*)d_wmask, (void*)d_cand, (void*)d_kps, (void*)d_keep, (void*)d_kframe,
-                    (void*)d_desc, (void*)d_pts})
-        if (p) (void)hipFree(p);
-    for (void* p : {h_pin, h_up, h_res})
-        if (p) (void)hipHostFree(p);
     if (stream) (void)hipStreamDestroy(stream);
-}
+}   // (the buffers free themselves: the device is current, the stream was idle)
 
 // orb.cpp detectAndCompute: level sizes cvRound(cols / getScale(level)); nfeaturesPerLevel.  nb: frames
 // the buffers must hold; a geometry keeps the largest batch it has seen.
@@ -835,34 +819,25 @@ int Bird::ensure_geometry(int W, int H, int nl, int nb) {
     const size_t nr = crows.size();
     size_t ccap = 0;   // NMS survivors never touch: <= ceil(w/2) * ceil(h/2) per level
     for (int l = 0; l < nl; l++) ccap += (size_t)((G.L[l].w + 1) / 2) * ((G.L[l].h + 1) / 2);
-    if ((e = hipMalloc((void**)&d_geom, sizeof(BirdGeom))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_rows, std::max<size_t>(rows.size(), 1) * sizeof(int2))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_lvlrow0, (nl + 1) * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_rcoef, std::max<size_t>(coefs.size(), 1) * sizeof(ResizeCoef))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_pyr, (size_t)pyr_bytes * nb)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_mpyr, pyr_bytes)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_score, (size_t)pyr_bytes * nb)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_blur, (size_t)pyr_bytes * nb)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_rowcnt, (nr + 1) * nb * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_rowoff, (nr + 1) * nb * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_lvlcnt, (size_t)kBirdMaxLevels * nb * sizeof(int))) != hipSuccess)
+    if ((e = d_geom.ensure(1)) != hipSuccess || (e = d_rows.ensure(std::max<size_t>(rows.size(), 1))) != hipSuccess ||
+        (e = d_lvlrow0.ensure(nl + 1)) != hipSuccess ||
+        (e = d_rcoef.ensure(std::max<size_t>(coefs.size(), 1))) != hipSuccess ||
+        (e = d_pyr.ensure((size_t)pyr_bytes * nb)) != hipSuccess || (e = d_mpyr.ensure(pyr_bytes)) != hipSuccess ||
+        (e = d_score.ensure((size_t)pyr_bytes * nb)) != hipSuccess ||
+        (e = d_blur.ensure((size_t)pyr_bytes * nb)) != hipSuccess ||
+        (e = d_rowcnt.ensure((nr + 1) * nb)) != hipSuccess || (e = d_rowoff.ensure((nr + 1) * nb)) != hipSuccess ||
+        (e = d_lvlcnt.ensure((size_t)kBirdMaxLevels * nb)) != hipSuccess)
         return free_geom(), set_error("birdview buffers", e), ORB_ERR_NOMEM;
     cand_slot = ccap;
-    if (ccap * nb > cand_cap) {
-        if (d_cand) (void)hipFree(d_cand);
-        d_cand = nullptr;
-        cand_cap = 0;
-        if ((e = hipMalloc((void**)&d_cand, ccap * nb * sizeof(BirdCand))) != hipSuccess)
-            return free_geom(), set_error("birdview candidates", e), ORB_ERR_NOMEM;
-        cand_cap = ccap * nb;
-    }
-    if ((e = hipMemcpyAsync(d_geom, &g, sizeof(BirdGeom), hipMemcpyHostToDevice, stream)) != hipSuccess ||
+    if ((e = d_cand.ensure(ccap * nb)) != hipSuccess)
+        return free_geom(), set_error("birdview candidates", e), ORB_ERR_NOMEM;
+    if ((e = hipMemcpyAsync(d_geom.get(), &g, sizeof(BirdGeom), hipMemcpyHostToDevice, stream)) != hipSuccess ||
         (!rows.empty() &&
-         (e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int2), hipMemcpyHostToDevice, stream)) !=
+         (e = hipMemcpyAsync(d_rows.get(), rows.data(), rows.size() * sizeof(int2), hipMemcpyHostToDevice, stream)) !=
              hipSuccess) ||
-        (e = hipMemcpyAsync(d_lvlrow0, lvl_row0.data(), (nl + 1) * sizeof(int), hipMemcpyHostToDevice, stream)) !=
+        (e = hipMemcpyAsync(d_lvlrow0.get(), lvl_row0.data(), (nl + 1) * sizeof(int), hipMemcpyHostToDevice, stream)) !=
             hipSuccess ||
-        (!coefs.empty() && (e = hipMemcpyAsync(d_rcoef, coefs.data(), coefs.size() * sizeof(ResizeCoef),
+        (!coefs.empty() && (e = hipMemcpyAsync(d_rcoef.get(), coefs.data(), coefs.size() * sizeof(ResizeCoef),
                                                hipMemcpyHostToDevice, stream)) != hipSuccess) ||
         (e = hipStreamSynchronize(stream)) != hipSuccess)
         return free_geom(), set_error("birdview geometry upload", e), ORB_ERR_HIP;
@@ -877,10 +852,8 @@ int Bird::ensure_mask_frames(int n) {
     if (n <= mnb_cap) return ORB_OK;
     hipError_t e;
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return set_error("sync", e), ORB_ERR_HIP;
-    if (d_mpyr) (void)hipFree(d_mpyr);
-    d_mpyr = nullptr;
     mnb_cap = 0;
-    if ((e = hipMalloc((void**)&d_mpyr, (size_t)pyr_bytes * n)) != hipSuccess) {
+    if ((e = d_mpyr.ensure((size_t)pyr_bytes * n)) != hipSuccess) {
         // the geometry cannot stay without its mask pyramid
         return free_geom(), set_error("birdview mask pyramids", e), ORB_ERR_NOMEM;
     }
@@ -891,37 +864,24 @@ int Bird::ensure_mask_frames(int n) {
 // nothing may be in flight on the keypoint buffers when they grow
 int Bird::ensure_kp(size_t n) {
     if (n <= kp_cap && d_kps) return ORB_OK;
-    size_t cap = std::max<size_t>(n, 4096);
-    for (void* p : {(void*)d_kps, (void*)d_keep, (void*)d_kframe, (void*)d_desc})
-        if (p) (void)hipFree(p);
-    d_kps = nullptr;
-    d_keep = nullptr;
-    d_kframe = nullptr;
-    d_desc = nullptr;
+    const size_t cap = std::max<size_t>(n, 4096);
+    d_kps.reset(), d_keep.reset(), d_kframe.reset(), d_desc.reset();   // (all four go before any comes back)
     kp_cap = 0;
     hipError_t e;
-    if ((e = hipMalloc((void**)&d_kps, cap * sizeof(orb_keypoint))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_keep, cap * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_kframe, cap * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_desc, cap * 32)) != hipSuccess)
+    if ((e = d_kps.ensure(cap)) != hipSuccess || (e = d_keep.ensure(cap)) != hipSuccess ||
+        (e = d_kframe.ensure(cap)) != hipSuccess || (e = d_desc.ensure(cap * 32)) != hipSuccess)
         return set_error("birdview keypoint buffers", e), ORB_ERR_NOMEM;
     kp_cap = cap;
     return ORB_OK;
 }
 
-int Bird::ensure_pinned(void*& p, size_t& pcap, size_t bytes) {
-    if (bytes <= pcap && p) return ORB_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    pcap = 0;
-    size_t cap = std::max<size_t>(bytes, 1 << 20);
-    hipError_t e = hipHostMalloc(&p, cap);
+int Bird::ensure_pinned(PinBuf<uint8_t>& p, size_t bytes) {
+    const hipError_t e = p.ensure(bytes, 1 << 20);
     if (e != hipSuccess) return set_error("pinned staging", e), ORB_ERR_NOMEM;
-    pcap = cap;
     return ORB_OK;
 }
 
-int Bird::ensure_pin(size_t bytes) { return ensure_pinned(h_pin, pin_cap, bytes); }
+int Bird::ensure_pin(size_t bytes) { return ensure_pinned(h_pin, bytes); }
 
 // Frame.cc:320-327 footprint rectangle (doubles truncated into cv::Rect, filled, clipped)
 static void footprint_rect(int W, int H, int& x0, int& y0, int& x1, int& y1) {
@@ -945,11 +905,11 @@ int Bird::upload(const uint8_t* img, size_t stride, const uint8_t* mask, size_t 
     const hipMemcpyKind kind = device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const BirdLevel& L0 = g.L[0];
     hipError_t e;
-    if (img && (e = hipMemcpy2DAsync(d_pyr + (size_t)frame * pyr_bytes + L0.off, L0.pitch, img, stride, L0.w, L0.h, kind,
+    if (img && (e = hipMemcpy2DAsync(d_pyr.get() + (size_t)frame * pyr_bytes + L0.off, L0.pitch, img, stride, L0.w, L0.h, kind,
                                      stream)) != hipSuccess)
         return set_error("birdview image upload", e), ORB_ERR_HIP;
     if (mask) {
-        uint8_t* m0 = d_mpyr + (size_t)mask_frame * pyr_bytes + L0.off;
+        uint8_t* m0 = d_mpyr.get() + (size_t)mask_frame * pyr_bytes + L0.off;
         if ((e = hipMemcpy2DAsync(m0, L0.pitch, mask, mstride, L0.w, L0.h, kind, stream)) != hipSuccess)
             return set_error("birdview mask upload", e), ORB_ERR_HIP;
         if (footprint) {
@@ -968,7 +928,7 @@ int Bird::upload(const uint8_t* img, size_t stride, const uint8_t* mask, size_t 
 int Bird::build_pyramid(int nl, bool with_mask, int nframes, int nmasks) {
     for (int l = 1; l < nl; l++) {
         dim3 grid((g.L[l].w + 255) / 256, g.L[l].h, nframes + (with_mask ? nmasks : 0));
-        hipLaunchKernelGGL(k_bird_resize, grid, dim3(256), 0, stream, d_geom, l, d_rcoef + rcoef_off[l], d_pyr, d_mpyr,
+        hipLaunchKernelGGL(k_bird_resize, grid, dim3(256), 0, stream, d_geom.get(), l, d_rcoef.get() + rcoef_off[l], d_pyr.get(), d_mpyr.get(),
                            nframes, fpitch());
     }
     hipError_t e = hipGetLastError();
@@ -980,19 +940,19 @@ int Bird::build_pyramid(int nl, bool with_mask, int nframes, int nmasks) {
 int Bird::launch_candidates(bool with_mask, int nframes, bool per_frame_mask) {
     const int nl = g.nlevels;
     const int nf = (int)frows.size(), nc = (int)crows.size();
-    const int2* d_frows = d_rows;
-    const int2* d_crows = d_rows + nf;
+    const int2* d_frows = d_rows.get();
+    const int2* d_crows = d_rows.get() + nf;
     const int fx = (max_w - 2 * edge + 2 + 255) / 256;
     const unsigned fp = fpitch(), mfp = per_frame_mask ? fp : 0u, slot = (unsigned)cand_slot;
-    hipLaunchKernelGGL(k_bird_fast, dim3(std::max(fx, 1), nf, nframes), dim3(256), 0, stream, d_geom, d_frows, d_pyr,
-                       d_score, fp);
-    const uint8_t* mp = with_mask ? d_mpyr : nullptr;
-    hipLaunchKernelGGL(k_bird_cands<0>, dim3((nc + 3) / 4, nframes), dim3(256), 0, stream, d_geom, d_crows, nc, d_pyr,
-                       mp, d_score, d_rowcnt, (const int*)nullptr, (BirdCand*)nullptr, fp, mfp, slot);
-    hipLaunchKernelGGL(k_bird_scan, dim3(nframes), dim3(1024), 0, stream, d_rowcnt, nc, d_lvlrow0, nl, d_rowoff,
-                       d_lvlcnt);
-    hipLaunchKernelGGL(k_bird_cands<1>, dim3((nc + 3) / 4, nframes), dim3(256), 0, stream, d_geom, d_crows, nc, d_pyr,
-                       mp, d_score, (int*)nullptr, d_rowoff, d_cand, fp, mfp, slot);
+    hipLaunchKernelGGL(k_bird_fast, dim3(std::max(fx, 1), nf, nframes), dim3(256), 0, stream, d_geom.get(), d_frows, d_pyr.get(),
+                       d_score.get(), fp);
+    const uint8_t* mp = with_mask ? d_mpyr.get() : nullptr;
+    hipLaunchKernelGGL(k_bird_cands<0>, dim3((nc + 3) / 4, nframes), dim3(256), 0, stream, d_geom.get(), d_crows, nc, d_pyr.get(),
+                       mp, d_score.get(), d_rowcnt.get(), (const int*)nullptr, (BirdCand*)nullptr, fp, mfp, slot);
+    hipLaunchKernelGGL(k_bird_scan, dim3(nframes), dim3(1024), 0, stream, d_rowcnt.get(), nc, d_lvlrow0.get(), nl, d_rowoff.get(),
+                       d_lvlcnt.get());
+    hipLaunchKernelGGL(k_bird_cands<1>, dim3((nc + 3) / 4, nframes), dim3(256), 0, stream, d_geom.get(), d_crows, nc, d_pyr.get(),
+                       mp, d_score.get(), (int*)nullptr, d_rowoff.get(), d_cand.get(), fp, mfp, slot);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error("birdview FAST", e), ORB_ERR_HIP;
     return ORB_OK;
@@ -1014,11 +974,11 @@ int Bird::detect_select(bool with_mask, std::vector<HostKP>& sel, int blur_level
         if (blur_levels > 0 && (r = launch_blur(blur_levels)) != ORB_OK) return r;
         // one download of the level counts and a speculative prefix of the candidates (sized from the
         // previous frame); a second only if this frame has more
-        const size_t hdr = 64, guess = std::min(cand_guess, cand_cap);
+        const size_t hdr = 64, guess = std::min(cand_guess, d_cand.cap());
         if ((r = ensure_pin(hdr + guess * sizeof(BirdCand))) != ORB_OK) return r;
-        uint8_t* hp = (uint8_t*)h_pin;
-        if ((e = hipMemcpyAsync(hp, d_lvlcnt, nl * sizeof(int), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-            (guess && (e = hipMemcpyAsync(hp + hdr, d_cand, guess * sizeof(BirdCand), hipMemcpyDeviceToHost, stream)) !=
+        uint8_t* hp = h_pin.get();
+        if ((e = hipMemcpyAsync(hp, d_lvlcnt.get(), nl * sizeof(int), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+            (guess && (e = hipMemcpyAsync(hp + hdr, d_cand.get(), guess * sizeof(BirdCand), hipMemcpyDeviceToHost, stream)) !=
                           hipSuccess) ||
             (e = hipStreamSynchronize(stream)) != hipSuccess)
             return set_error("birdview candidate download", e), ORB_ERR_HIP;
@@ -1031,11 +991,11 @@ int Bird::detect_select(bool with_mask, std::vector<HostKP>& sel, int blur_level
         if (total > guess) {
             const size_t rest = total - guess;
             if ((r = ensure_pin(rest * sizeof(BirdCand))) != ORB_OK) return r;
-            if ((e = hipMemcpyAsync(h_pin, d_cand + guess, rest * sizeof(BirdCand), hipMemcpyDeviceToHost, stream)) !=
+            if ((e = hipMemcpyAsync(h_pin.get(), d_cand.get() + guess, rest * sizeof(BirdCand), hipMemcpyDeviceToHost, stream)) !=
                     hipSuccess ||
                 (e = hipStreamSynchronize(stream)) != hipSuccess)
                 return set_error("birdview candidates download", e), ORB_ERR_HIP;
-            std::memcpy(last_cands.data() + guess, h_pin, rest * sizeof(BirdCand));
+            std::memcpy(last_cands.data() + guess, h_pin.get(), rest * sizeof(BirdCand));
         }
         cand_guess = total + total / 8 + 256;
     } else if (blur_levels > 0) {
@@ -1076,36 +1036,36 @@ void Bird::select(const BirdCand* cands, const int* lvlcnt, std::vector<HostKP>&
 
 int Bird::launch_angle(int n) {
     if (n)
-        hipLaunchKernelGGL(k_bird_angle, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom, d_pyr, d_kps, n,
+        hipLaunchKernelGGL(k_bird_angle, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom.get(), d_pyr.get(), d_kps.get(), n,
                            (const int*)nullptr, 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_angle", e), ORB_ERR_HIP);
 }
 
 int Bird::launch_subpix(int n, bool keep) {
-    SubpixSrc s{d_pyr + g.L[0].off, g.L[0].pitch, g.L[0].w, g.L[0].h};
+    SubpixSrc s{d_pyr.get() + g.L[0].off, g.L[0].pitch, g.L[0].w, g.L[0].h};
     if (n)
-        hipLaunchKernelGGL(k_bird_subpix, dim3((n + 3) / 4), dim3(256), 0, stream, s, d_wmask,
-                           reinterpret_cast<float*>(d_kps), 7, n, 40, 0.001 * 0.001, edge, keep ? d_keep : nullptr,
+        hipLaunchKernelGGL(k_bird_subpix, dim3((n + 3) / 4), dim3(256), 0, stream, s, d_wmask.get(),
+                           reinterpret_cast<float*>(d_kps.get()), 7, n, 40, 0.001 * 0.001, edge, keep ? d_keep.get() : nullptr,
                            (const int*)nullptr, 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_subpix", e), ORB_ERR_HIP);
 }
 
 int Bird::launch_blur(int nl, int nframes) {
-    const int2* d_brows = d_rows + frows.size() + crows.size();
+    const int2* d_brows = d_rows.get() + frows.size() + crows.size();
     const int nb = brow0[nl];
     if (nb)
-        hipLaunchKernelGGL(k_bird_blur, dim3((max_w + 255) / 256, nb, nframes), dim3(256), 0, stream, d_geom, d_brows,
-                           d_pyr, d_blur, fpitch());
+        hipLaunchKernelGGL(k_bird_blur, dim3((max_w + 255) / 256, nb, nframes), dim3(256), 0, stream, d_geom.get(), d_brows,
+                           d_pyr.get(), d_blur.get(), fpitch());
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_blur", e), ORB_ERR_HIP);
 }
 
 int Bird::launch_desc(int n, bool keep) {
     if (n)
-        hipLaunchKernelGGL(k_bird_desc, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom, d_pyr, d_blur, d_pattern, d_kps,
-                           keep ? d_keep : nullptr, n, d_desc, (const int*)nullptr, 0u);
+        hipLaunchKernelGGL(k_bird_desc, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom.get(), d_pyr.get(), d_blur.get(), d_pattern.get(), d_kps.get(),
+                           keep ? d_keep.get() : nullptr, n, d_desc.get(), (const int*)nullptr, 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_desc", e), ORB_ERR_HIP);
 }
@@ -1160,11 +1120,11 @@ extern "C" orb_bird* orb_bird_create(const orb_bird_params* p, int* status) {
         }
     }
     if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipMalloc((void**)&b->d_pattern, sizeof(kPattern31))) != hipSuccess ||
-        (e = hipMalloc((void**)&b->d_wmask, sizeof(b->wmask))) != hipSuccess ||
-        (e = hipMemcpyAsync(b->d_pattern, kPattern31, sizeof(kPattern31), hipMemcpyHostToDevice, b->stream)) !=
+        (e = b->d_pattern.ensure(sizeof(kPattern31) / sizeof(int))) != hipSuccess ||
+        (e = b->d_wmask.ensure(kSubW * kSubW)) != hipSuccess ||
+        (e = hipMemcpyAsync(b->d_pattern.get(), kPattern31, sizeof(kPattern31), hipMemcpyHostToDevice, b->stream)) !=
             hipSuccess ||
-        (e = hipMemcpyAsync(b->d_wmask, b->wmask, sizeof(b->wmask), hipMemcpyHostToDevice, b->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(b->d_wmask.get(), b->wmask, sizeof(b->wmask), hipMemcpyHostToDevice, b->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(b->stream)) != hipSuccess) {
         delete b;
         set_error("orb_bird_create", e);
@@ -1214,12 +1174,12 @@ static int bird_run(orb_bird* b, bool with_mask, bool subpix_compute, orb_keypoi
     std::vector<orb_keypoint> hk(ns);
     for (int i = 0; i < ns; i++) to_kp(sel[i], hk[i]);
     hipError_t e;
-    if (ns && (e = hipMemcpyAsync(b->d_kps, hk.data(), ns * sizeof(orb_keypoint), hipMemcpyHostToDevice, b->stream)) !=
+    if (ns && (e = hipMemcpyAsync(b->d_kps.get(), hk.data(), ns * sizeof(orb_keypoint), hipMemcpyHostToDevice, b->stream)) !=
                   hipSuccess)
         return set_error("birdview keypoint upload", e), ORB_ERR_HIP;
     if ((r = b->launch_angle(ns)) != ORB_OK) return r;
     if (!subpix_compute) {
-        if (ns && ((e = hipMemcpyAsync(kps, b->d_kps, ns * sizeof(orb_keypoint), hipMemcpyDeviceToHost, b->stream)) !=
+        if (ns && ((e = hipMemcpyAsync(kps, b->d_kps.get(), ns * sizeof(orb_keypoint), hipMemcpyDeviceToHost, b->stream)) !=
                        hipSuccess ||
                    (e = hipStreamSynchronize(b->stream)) != hipSuccess))
             return set_error("birdview keypoint download", e), ORB_ERR_HIP;
@@ -1231,10 +1191,10 @@ static int bird_run(orb_bird* b, bool with_mask, bool subpix_compute, orb_keypoi
     if ((r = b->launch_desc(ns, true)) != ORB_OK) return r;
     const size_t kb = (size_t)ns * sizeof(orb_keypoint), fb = (size_t)ns * sizeof(int), db = (size_t)ns * 32;
     if ((r = b->ensure_pin(kb + fb + db + 64)) != ORB_OK) return r;
-    uint8_t* hp = (uint8_t*)b->h_pin;
-    if (ns && ((e = hipMemcpyAsync(hp, b->d_kps, kb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-               (e = hipMemcpyAsync(hp + kb, b->d_keep, fb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-               (e = hipMemcpyAsync(hp + kb + fb, b->d_desc, db, hipMemcpyDeviceToHost, b->stream)) != hipSuccess))
+    uint8_t* hp = b->h_pin.get();
+    if (ns && ((e = hipMemcpyAsync(hp, b->d_kps.get(), kb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+               (e = hipMemcpyAsync(hp + kb, b->d_keep.get(), fb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+               (e = hipMemcpyAsync(hp + kb + fb, b->d_desc.get(), db, hipMemcpyDeviceToHost, b->stream)) != hipSuccess))
         return set_error("birdview result download", e), ORB_ERR_HIP;
     if ((e = hipStreamSynchronize(b->stream)) != hipSuccess) return set_error("birdview sync", e), ORB_ERR_HIP;
     const orb_keypoint* rk = (const orb_keypoint*)hp;
@@ -1312,11 +1272,11 @@ static int bird_batch_flush(orb_bird* b, std::vector<BatchFrame>& done, int used
     int r;
     hipError_t e;
     const size_t kb = (size_t)used * sizeof(orb_keypoint), fb = (size_t)used * sizeof(int), db = (size_t)used * 32;
-    if ((r = b->ensure_pinned(b->h_res, b->res_cap, kb + fb + db + 64)) != ORB_OK) return r;
-    uint8_t* hp = (uint8_t*)b->h_res;
-    if (used && ((e = hipMemcpyAsync(hp, b->d_kps, kb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-                 (e = hipMemcpyAsync(hp + kb, b->d_keep, fb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-                 (e = hipMemcpyAsync(hp + kb + fb, b->d_desc, db, hipMemcpyDeviceToHost, b->stream)) != hipSuccess))
+    if ((r = b->ensure_pinned(b->h_res, kb + fb + db + 64)) != ORB_OK) return r;
+    uint8_t* hp = b->h_res.get();
+    if (used && ((e = hipMemcpyAsync(hp, b->d_kps.get(), kb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+                 (e = hipMemcpyAsync(hp + kb, b->d_keep.get(), fb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+                 (e = hipMemcpyAsync(hp + kb + fb, b->d_desc.get(), db, hipMemcpyDeviceToHost, b->stream)) != hipSuccess))
         return set_error("birdview result download", e), ORB_ERR_HIP;
     if ((e = hipStreamSynchronize(b->stream)) != hipSuccess) return set_error("birdview sync", e), ORB_ERR_HIP;
     const orb_keypoint* rk = (const orb_keypoint*)hp;
@@ -1364,13 +1324,13 @@ static int bird_batch_run(orb_bird* b, int B, int nmasks, orb_keypoint* kps, uin
         const size_t slot = b->cand_slot, guess = std::min(b->cand_guess, slot);
         const size_t hdr = ((size_t)B * kBirdMaxLevels * sizeof(int) + 63) & ~(size_t)63;
         if ((r = b->ensure_pin(hdr + (size_t)B * guess * sizeof(BirdCand))) != ORB_OK) return r;
-        uint8_t* hp = (uint8_t*)b->h_pin;
-        if ((e = hipMemcpyAsync(hp, b->d_lvlcnt, (size_t)B * kBirdMaxLevels * sizeof(int), hipMemcpyDeviceToHost,
+        uint8_t* hp = b->h_pin.get();
+        if ((e = hipMemcpyAsync(hp, b->d_lvlcnt.get(), (size_t)B * kBirdMaxLevels * sizeof(int), hipMemcpyDeviceToHost,
                                 b->stream)) != hipSuccess)
             return set_error("birdview count download", e), ORB_ERR_HIP;
         const BirdCand* pre = (const BirdCand*)(hp + hdr);
         for (int f = 0; f < B && guess; f++)
-            if ((e = hipMemcpyAsync((void*)(pre + f * guess), b->d_cand + f * slot, guess * sizeof(BirdCand),
+            if ((e = hipMemcpyAsync((void*)(pre + f * guess), b->d_cand.get() + f * slot, guess * sizeof(BirdCand),
                                     hipMemcpyDeviceToHost, b->stream)) != hipSuccess)
                 return set_error("birdview candidate download", e), ORB_ERR_HIP;
         if ((e = hipStreamSynchronize(b->stream)) != hipSuccess)
@@ -1388,13 +1348,13 @@ static int bird_batch_run(orb_bird* b, int B, int nmasks, orb_keypoint* kps, uin
             max_total = std::max(max_total, total[f]);
         }
         if (rest_total) {
-            if ((r = b->ensure_pinned(b->h_res, b->res_cap, rest_total * sizeof(BirdCand))) != ORB_OK) return r;
-            BirdCand* hr = (BirdCand*)b->h_res;
+            if ((r = b->ensure_pinned(b->h_res, rest_total * sizeof(BirdCand))) != ORB_OK) return r;
+            BirdCand* hr = (BirdCand*)b->h_res.get();
             size_t ro = 0;
             for (int f = 0; f < B; f++)
                 if (total[f] > guess) {
                     const size_t rest = total[f] - guess;
-                    if ((e = hipMemcpyAsync(hr + ro, b->d_cand + f * slot + guess, rest * sizeof(BirdCand),
+                    if ((e = hipMemcpyAsync(hr + ro, b->d_cand.get() + f * slot + guess, rest * sizeof(BirdCand),
                                             hipMemcpyDeviceToHost, b->stream)) != hipSuccess)
                         return set_error("birdview candidates download", e), ORB_ERR_HIP;
                     ro += rest;
@@ -1419,8 +1379,8 @@ static int bird_batch_run(orb_bird* b, int B, int nmasks, orb_keypoint* kps, uin
     }
 
     // selection frame by frame; each full group goes up and through its kernels behind the host
-    orb_keypoint* up_k = (orb_keypoint*)b->h_up;
-    int* up_f = (int*)((uint8_t*)b->h_up + b->kp_cap * sizeof(orb_keypoint));
+    orb_keypoint* up_k = (orb_keypoint*)b->h_up.get();
+    int* up_f = (int*)(b->h_up.get() + b->kp_cap * sizeof(orb_keypoint));
     std::vector<BatchFrame> done;
     std::vector<HostKP> sel;
     int used = 0, g0 = 0, gframes = 0;
@@ -1431,20 +1391,20 @@ static int bird_batch_run(orb_bird* b, int B, int nmasks, orb_keypoint* kps, uin
         const int n = used - g0;
         if (n) {
             hipError_t le;
-            if ((le = hipMemcpyAsync(b->d_kps + g0, up_k + g0, (size_t)n * sizeof(orb_keypoint), hipMemcpyHostToDevice,
+            if ((le = hipMemcpyAsync(b->d_kps.get() + g0, up_k + g0, (size_t)n * sizeof(orb_keypoint), hipMemcpyHostToDevice,
                                      b->stream)) != hipSuccess ||
-                (le = hipMemcpyAsync(b->d_kframe + g0, up_f + g0, (size_t)n * sizeof(int), hipMemcpyHostToDevice,
+                (le = hipMemcpyAsync(b->d_kframe.get() + g0, up_f + g0, (size_t)n * sizeof(int), hipMemcpyHostToDevice,
                                      b->stream)) != hipSuccess)
                 return set_error("birdview keypoint upload", le), ORB_ERR_HIP;
             const dim3 grid((n + 3) / 4), block(256);
-            const int* kf = b->d_kframe + g0;
-            hipLaunchKernelGGL(k_bird_angle, grid, block, 0, b->stream, b->d_geom, b->d_pyr, b->d_kps + g0, n, kf, fp);
-            SubpixSrc s{b->d_pyr + L0.off, L0.pitch, L0.w, L0.h};
-            hipLaunchKernelGGL(k_bird_subpix, grid, block, 0, b->stream, s, b->d_wmask,
-                               reinterpret_cast<float*>(b->d_kps + g0), 7, n, 40, 0.001 * 0.001, b->edge, b->d_keep + g0,
+            const int* kf = b->d_kframe.get() + g0;
+            hipLaunchKernelGGL(k_bird_angle, grid, block, 0, b->stream, b->d_geom.get(), b->d_pyr.get(), b->d_kps.get() + g0, n, kf, fp);
+            SubpixSrc s{b->d_pyr.get() + L0.off, L0.pitch, L0.w, L0.h};
+            hipLaunchKernelGGL(k_bird_subpix, grid, block, 0, b->stream, s, b->d_wmask.get(),
+                               reinterpret_cast<float*>(b->d_kps.get() + g0), 7, n, 40, 0.001 * 0.001, b->edge, b->d_keep.get() + g0,
                                kf, fp);
-            hipLaunchKernelGGL(k_bird_desc, grid, block, 0, b->stream, b->d_geom, b->d_pyr, b->d_blur, b->d_pattern,
-                               b->d_kps + g0, b->d_keep + g0, n, b->d_desc + (size_t)g0 * 32, kf, fp);
+            hipLaunchKernelGGL(k_bird_desc, grid, block, 0, b->stream, b->d_geom.get(), b->d_pyr.get(), b->d_blur.get(), b->d_pattern.get(),
+                               b->d_kps.get() + g0, b->d_keep.get() + g0, n, b->d_desc.get() + (size_t)g0 * 32, kf, fp);
             if ((le = hipGetLastError()) != hipSuccess) return set_error("birdview keypoint kernels", le), ORB_ERR_HIP;
         }
         g0 = used;
@@ -1462,10 +1422,10 @@ static int bird_batch_run(orb_bird* b, int B, int nmasks, orb_keypoint* kps, uin
                 return r;
             used = g0 = 0;
             if ((r = b->ensure_kp(ns)) != ORB_OK ||
-                (r = b->ensure_pinned(b->h_up, b->up_cap, b->kp_cap * (sizeof(orb_keypoint) + sizeof(int)))) != ORB_OK)
+                (r = b->ensure_pinned(b->h_up, b->kp_cap * (sizeof(orb_keypoint) + sizeof(int)))) != ORB_OK)
                 return r;
-            up_k = (orb_keypoint*)b->h_up;
-            up_f = (int*)((uint8_t*)b->h_up + b->kp_cap * sizeof(orb_keypoint));
+            up_k = (orb_keypoint*)b->h_up.get();
+            up_f = (int*)(b->h_up.get() + b->kp_cap * sizeof(orb_keypoint));
         }
         for (int i = 0; i < ns; i++) {
             to_kp(sel[i], up_k[used + i]);
@@ -1509,7 +1469,7 @@ static int bird_batch_reserve(orb_bird* b, int B, int w, int h, int nmasks) {
     if ((r = b->ensure_geometry(w, h, b->nlevels, B)) != ORB_OK) return r;
     if ((r = b->ensure_mask_frames(nmasks)) != ORB_OK) return r;
     if ((r = b->ensure_kp((size_t)B * ((size_t)b->nfeatures + 64))) != ORB_OK) return r;
-    return b->ensure_pinned(b->h_up, b->up_cap, b->kp_cap * (sizeof(orb_keypoint) + sizeof(int)));
+    return b->ensure_pinned(b->h_up, b->kp_cap * (sizeof(orb_keypoint) + sizeof(int)));
 }
 
 extern "C" int orb_bird_extract_batch_device(orb_bird* b, int nframes, const uint8_t* d_imgs, int w, int h,
@@ -1526,8 +1486,8 @@ extern "C" int orb_bird_extract_batch_device(orb_bird* b, int nframes, const uin
     if ((r = bird_batch_reserve(b, nframes, w, h, nmasks)) != ORB_OK) return r;
     int x0, y0, x1, y1;
     footprint_rect(w, h, x0, y0, x1, y1);
-    hipLaunchKernelGGL(k_bird_ingest, dim3((w + 255) / 256, h, nframes + nmasks), dim3(256), 0, b->stream, b->d_geom,
-                       d_imgs, stride, frame_pitch, d_masks, mask_stride, mask_frame_pitch, b->d_pyr, b->d_mpyr, nframes,
+    hipLaunchKernelGGL(k_bird_ingest, dim3((w + 255) / 256, h, nframes + nmasks), dim3(256), 0, b->stream, b->d_geom.get(),
+                       d_imgs, stride, frame_pitch, d_masks, mask_stride, mask_frame_pitch, b->d_pyr.get(), b->d_mpyr.get(), nframes,
                        b->fpitch(), x0, y0, x1, y1);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error("k_bird_ingest", e), ORB_ERR_HIP;
@@ -1610,11 +1570,11 @@ extern "C" int orb_bird_compute(orb_bird* b, const uint8_t* img, int w, int h, s
     if ((r = b->upload(img, stride, nullptr, 0, false, false)) != ORB_OK) return r;
     if ((r = b->build_pyramid(nl, false)) != ORB_OK) return r;
     hipError_t he;
-    if ((he = hipMemcpyAsync(b->d_kps, v.data(), m * sizeof(orb_keypoint), hipMemcpyHostToDevice, b->stream)) !=
+    if ((he = hipMemcpyAsync(b->d_kps.get(), v.data(), m * sizeof(orb_keypoint), hipMemcpyHostToDevice, b->stream)) !=
         hipSuccess)
         return set_error("birdview keypoint upload", he), ORB_ERR_HIP;
     if ((r = b->launch_blur(nl)) != ORB_OK || (r = b->launch_desc(m, false)) != ORB_OK) return r;
-    if ((he = hipMemcpyAsync(desc, b->d_desc, (size_t)m * 32, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+    if ((he = hipMemcpyAsync(desc, b->d_desc.get(), (size_t)m * 32, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
         (he = hipStreamSynchronize(b->stream)) != hipSuccess)
         return set_error("birdview descriptor download", he), ORB_ERR_HIP;
     return ORB_OK;
@@ -1632,24 +1592,17 @@ extern "C" int orb_corner_subpix(orb_bird* b, const uint8_t* img, int w, int h, 
     if (!n) return ORB_OK;
     if ((r = b->ensure_geometry(w, h, b->nlevels)) != ORB_OK && (r = b->ensure_geometry(w, h, 1)) != ORB_OK) return r;
     hipError_t e;
-    if ((size_t)n * 2 > b->pts_cap) {
-        if (b->d_pts) (void)hipFree(b->d_pts);
-        b->d_pts = nullptr;
-        b->pts_cap = 0;
-        if ((e = hipMalloc((void**)&b->d_pts, (size_t)n * 2 * sizeof(float))) != hipSuccess)
-            return set_error("subpix points", e), ORB_ERR_NOMEM;
-        b->pts_cap = (size_t)n * 2;
-    }
+    if ((e = b->d_pts.ensure((size_t)n * 2)) != hipSuccess) return set_error("subpix points", e), ORB_ERR_NOMEM;
     if ((r = b->upload(img, stride, nullptr, 0, false, false)) != ORB_OK) return r;
     const int iters = std::min(std::max(max_iter, 1), 100);
     const double ep = std::max(eps, 0.);
-    SubpixSrc s{b->d_pyr + b->g.L[0].off, b->g.L[0].pitch, w, h};
-    if ((e = hipMemcpyAsync(b->d_pts, pts, (size_t)n * 8, hipMemcpyHostToDevice, b->stream)) != hipSuccess)
+    SubpixSrc s{b->d_pyr.get() + b->g.L[0].off, b->g.L[0].pitch, w, h};
+    if ((e = hipMemcpyAsync(b->d_pts.get(), pts, (size_t)n * 8, hipMemcpyHostToDevice, b->stream)) != hipSuccess)
         return set_error("subpix upload", e), ORB_ERR_HIP;
-    hipLaunchKernelGGL(k_bird_subpix, dim3((n + 3) / 4), dim3(256), 0, b->stream, s, b->d_wmask, b->d_pts, 2, n, iters,
+    hipLaunchKernelGGL(k_bird_subpix, dim3((n + 3) / 4), dim3(256), 0, b->stream, s, b->d_wmask.get(), b->d_pts.get(), 2, n, iters,
                        ep * ep, b->edge, (int*)nullptr, (const int*)nullptr, 0u);
     if ((e = hipGetLastError()) != hipSuccess ||
-        (e = hipMemcpyAsync(pts, b->d_pts, (size_t)n * 8, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(pts, b->d_pts.get(), (size_t)n * 8, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(b->stream)) != hipSuccess)
         return set_error("k_bird_subpix", e), ORB_ERR_HIP;
     return ORB_OK;
@@ -1675,7 +1628,7 @@ extern "C" int orb_bird_debug_level(orb_bird* b, int level, uint8_t* out, int* w
     *h = L.h;
     if (!out) return ORB_OK;
     (void)hipSetDevice(b->device);
-    hipError_t e = hipMemcpy2DAsync(out, L.w, b->d_pyr + L.off, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, b->stream);
+    hipError_t e = hipMemcpy2DAsync(out, L.w, b->d_pyr.get() + L.off, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, b->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     return e == hipSuccess ? ORB_OK : (set_error("orb_bird_debug_level", e), ORB_ERR_HIP);
 }

@@ -88,15 +88,9 @@ extern "C" int orb_distinctive_descriptors(orb_ctx* h, int nmp, const int* offse
     const size_t A = 256;
     auto al = [&](size_t x) { return (x + A - 1) & ~(A - 1); };
     const size_t need = al((size_t)(nmp + 1) * 4) + al((size_t)std::max(total, 1) * 32) + al((size_t)nmp * 4);
-    if (need > c->scratch_cap || !c->d_scratch) {
-        if (c->d_scratch) (void)hipFree(c->d_scratch);
-        c->d_scratch = nullptr;
-        c->scratch_cap = 0;
-        if ((e = hipMalloc((void**)&c->d_scratch, need)) != hipSuccess) return set_error("scratch", e), ORB_ERR_NOMEM;
-        c->scratch_cap = need;
-    }
-    int* d_off = reinterpret_cast<int*>(c->d_scratch);
-    uint8_t* d_desc = c->d_scratch + al((size_t)(nmp + 1) * 4);
+    if ((e = Arena{c}.reserve(need)) != hipSuccess) return set_error("scratch", e), ORB_ERR_NOMEM;
+    int* d_off = reinterpret_cast<int*>(c->d_scratch.get());
+    uint8_t* d_desc = c->d_scratch.get() + al((size_t)(nmp + 1) * 4);
     int* d_best = reinterpret_cast<int*>(d_desc + al((size_t)std::max(total, 1) * 32));
     if ((e = hipMemcpyAsync(d_off, offsets, (size_t)(nmp + 1) * 4, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
         (total && (e = hipMemcpyAsync(d_desc, desc, (size_t)total * 32, hipMemcpyHostToDevice, c->stream)) !=

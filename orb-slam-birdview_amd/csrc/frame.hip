@@ -156,19 +156,16 @@ int frame_create(const char* fn, Ctx* c, int n, const uint8_t* desc, const orb_k
         set_error(what, e);
         // copies already queued write into F's allocation and F's host keypoints: they end before either is released
         (void)hipStreamSynchronize(c->stream);
-        if (F->d_base) (void)hipFree(F->d_base);
         delete F;
         return st;
     };
-    if ((e = hipMalloc((void**)&F->d_base, total)) != hipSuccess) {
-        F->d_base = nullptr;
-        return fail("orb_frame allocation", ORB_ERR_NOMEM);
-    }
-    F->d_desc = F->d_base + o_desc;
-    F->d_kps = reinterpret_cast<const orb_keypoint*>(F->d_base + o_kps);
-    F->d_ur = F->has_ur ? reinterpret_cast<const float*>(F->d_base + o_ur) : nullptr;
-    F->d_coff = reinterpret_cast<const int*>(F->d_base + o_coff);
-    F->d_cidx = reinterpret_cast<const int*>(F->d_base + o_cidx);
+    if ((e = F->d_base.ensure(total)) != hipSuccess) return fail("orb_frame allocation", ORB_ERR_NOMEM);
+    uint8_t* const base = F->d_base.get();
+    F->d_desc = base + o_desc;
+    F->d_kps = reinterpret_cast<const orb_keypoint*>(base + o_kps);
+    F->d_ur = F->has_ur ? reinterpret_cast<const float*>(base + o_ur) : nullptr;
+    F->d_coff = reinterpret_cast<const int*>(base + o_coff);
+    F->d_cidx = reinterpret_cast<const int*>(base + o_cidx);
     // k_frame_grid's working space is the context's scratch arena, free again once this call has synchronised.
     // reserve() frees and reallocates the arena when it has to grow (hipFree waits for the device, so queued work that
     // reads the old arena ends first): like every user of the arena this relies on no caller keeping a pointer into it
@@ -184,18 +181,17 @@ int frame_create(const char* fn, Ctx* c, int n, const uint8_t* desc, const orb_k
     }
     if (n > 0) {
         if (src_kind == hipMemcpyHostToDevice) std::memcpy(F->kps.data(), kps, nn * sizeof(orb_keypoint));
-        if ((e = hipMemcpyAsync(F->d_base + o_desc, desc, nn * 32, src_kind, c->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(F->d_base + o_kps, kps, nn * sizeof(orb_keypoint), src_kind, c->stream)) != hipSuccess ||
-            (uright && (e = hipMemcpyAsync(F->d_base + o_ur, uright, nn * 4, src_kind, c->stream)) != hipSuccess))
+        if ((e = hipMemcpyAsync(base + o_desc, desc, nn * 32, src_kind, c->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(base + o_kps, kps, nn * sizeof(orb_keypoint), src_kind, c->stream)) != hipSuccess ||
+            (uright && (e = hipMemcpyAsync(base + o_ur, uright, nn * 4, src_kind, c->stream)) != hipSuccess))
             return fail("orb_frame copy", ORB_ERR_HIP);
         if (src_kind == hipMemcpyDeviceToDevice &&
             (e = hipMemcpyAsync(F->kps.data(), kps, nn * sizeof(orb_keypoint), hipMemcpyDeviceToHost, c->stream)) !=
                 hipSuccess)
             return fail("orb_frame keypoints to the host", ORB_ERR_HIP);
     }
-    if ((e = launch_frame_grid(F->d_kps, n, ProjGrid{min_x, min_y, inv_w, inv_h},
-                               reinterpret_cast<int*>(F->d_base + o_coff), reinterpret_cast<int*>(F->d_base + o_cidx),
-                               d_work, c->stream)) != hipSuccess)
+    if ((e = launch_frame_grid(F->d_kps, n, ProjGrid{min_x, min_y, inv_w, inv_h}, reinterpret_cast<int*>(base + o_coff),
+                               reinterpret_cast<int*>(base + o_cidx), d_work, c->stream)) != hipSuccess)
         return fail("k_frame_grid", ORB_ERR_HIP);
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail("orb_frame synchronise", ORB_ERR_HIP);
     for (int i = 0; i < n; i++) {   // (orb_fuse_search_points checks them against its camera's nlevels per call)
@@ -228,7 +224,9 @@ int orb_frame_create_device(orb_ctx* h, int n, const uint8_t* d_desc, const orb_
 
 void orb_frame_destroy(orb_frame* F) {
     if (!F) return;
-    if (F->d_base && hipSetDevice(F->device) == hipSuccess) (void)hipFree(F->d_base);
+    // the allocation is freed even where the device cannot be made current: hipFree takes a pointer, not the
+    // current device
+    (void)hipSetDevice(F->device);
     delete F;
 }
 

@@ -24,12 +24,11 @@
 struct orb_kfdb {
     int device = 0;
     // the pool: word ids ascending and values, entry after entry in add order
-    int* d_words = nullptr;
-    double* d_vals = nullptr;
+    orbgpu::DevBuf<int> d_words;
+    orbgpu::DevBuf<double> d_vals;
     size_t pool_cap = 0, pool_used = 0, pool_dead = 0;   // in words
     // per slot (offset, length) on the device; length -1: erased.  Uploaded before a query when it has changed
-    int2* d_ent = nullptr;
-    size_t ent_cap = 0;
+    orbgpu::DevBuf<int2> d_ent;
     bool ent_dirty = false;
     std::vector<int2> ent;        // the host's copy, authoritative
     std::vector<int> slot_id;     // per slot: the id add returned
@@ -160,15 +159,6 @@ double l1_score(int n1, const int* w1, const double* v1, int n2, const int* w2, 
     return -score / 2.0;
 }
 
-void kfdb_free_device(orb_kfdb* db) {
-    if (db->d_words) (void)hipFree(db->d_words);
-    if (db->d_vals) (void)hipFree(db->d_vals);
-    if (db->d_ent) (void)hipFree(db->d_ent);
-    db->d_words = nullptr;
-    db->d_vals = nullptr;
-    db->d_ent = nullptr;
-}
-
 // A pool of at least `need` words holding the live entries packed in slot order: growth (by doubling) and compaction
 // are the same copy.  Runs of adjacent live entries move as one device-to-device copy.  Synchronises.
 int kfdb_repack(const char* fn, Ctx* c, orb_kfdb* db, size_t need) {
@@ -176,13 +166,11 @@ int kfdb_repack(const char* fn, Ctx* c, orb_kfdb* db, size_t need) {
     while (cap < need) cap *= 2;
     if (cap > (size_t)INT_MAX) return set_error((std::string(fn) + ": pool above 2^31 words").c_str(), hipSuccess),
                                       ORB_ERR_CAPACITY;
-    int* nw = nullptr;
-    double* nv = nullptr;
+    DevBuf<int> nw;   // the new pool: the handle's once the copy has succeeded, freed on every return before
+    DevBuf<double> nv;
     hipError_t e;
-    if ((e = hipMalloc((void**)&nw, cap * 4)) != hipSuccess || (e = hipMalloc((void**)&nv, cap * 8)) != hipSuccess) {
-        if (nw) (void)hipFree(nw);
+    if ((e = nw.ensure(cap)) != hipSuccess || (e = nv.ensure(cap)) != hipSuccess)
         return set_error((std::string(fn) + ": pool allocation").c_str(), e), ORB_ERR_NOMEM;
-    }
     std::vector<int2> nent;
     std::vector<int> nid;
     nent.reserve(db->ent.size());
@@ -190,9 +178,10 @@ int kfdb_repack(const char* fn, Ctx* c, orb_kfdb* db, size_t need) {
     size_t used = 0, run_src = 0, run_dst = 0, run_len = 0;
     auto flush = [&]() {
         if (run_len == 0 || e != hipSuccess) return;
-        if ((e = hipMemcpyAsync(nw + run_dst, db->d_words + run_src, run_len * 4, hipMemcpyDeviceToDevice, c->stream)) ==
-            hipSuccess)
-            e = hipMemcpyAsync(nv + run_dst, db->d_vals + run_src, run_len * 8, hipMemcpyDeviceToDevice, c->stream);
+        if ((e = hipMemcpyAsync(nw.get() + run_dst, db->d_words.get() + run_src, run_len * 4, hipMemcpyDeviceToDevice,
+                                c->stream)) == hipSuccess)
+            e = hipMemcpyAsync(nv.get() + run_dst, db->d_vals.get() + run_src, run_len * 8, hipMemcpyDeviceToDevice,
+                               c->stream);
         run_len = 0;
     };
     e = hipSuccess;
@@ -212,15 +201,9 @@ int kfdb_repack(const char* fn, Ctx* c, orb_kfdb* db, size_t need) {
     flush();
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) {
-        (void)hipFree(nw);
-        (void)hipFree(nv);
-        return set_error((std::string(fn) + ": pool copy").c_str(), e), ORB_ERR_HIP;
-    }
-    if (db->d_words) (void)hipFree(db->d_words);
-    if (db->d_vals) (void)hipFree(db->d_vals);
-    db->d_words = nw;
-    db->d_vals = nv;
+    if (e != hipSuccess) return set_error((std::string(fn) + ": pool copy").c_str(), e), ORB_ERR_HIP;
+    db->d_words.swap(nw);   // (the old pools leave with nw and nv)
+    db->d_vals.swap(nv);
     db->pool_cap = cap;
     db->pool_used = used;
     db->pool_dead = 0;
@@ -276,7 +259,7 @@ int orb_kfdb_create(orb_ctx* h, orb_kfdb** out) {
 
 void orb_kfdb_destroy(orb_kfdb* db) {
     if (!db) return;
-    if (hipSetDevice(db->device) == hipSuccess) kfdb_free_device(db);
+    (void)hipSetDevice(db->device);   // (freed even where this fails: hipFree takes a pointer, not the current device)
     delete db;
 }
 
@@ -301,9 +284,9 @@ int orb_kfdb_add(orb_ctx* h, orb_kfdb* db, int nbow, const int* words, const dou
     }
     if (nbow > 0) {
         // the caller's arrays are pageable: the copies are staged and the stream synchronised before they are released
-        hipError_t e = hipMemcpyAsync(db->d_words + db->pool_used, words, (size_t)nbow * 4, hipMemcpyHostToDevice, c->stream);
+        hipError_t e = hipMemcpyAsync(db->d_words.get() + db->pool_used, words, (size_t)nbow * 4, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(db->d_vals + db->pool_used, values, (size_t)nbow * 8, hipMemcpyHostToDevice, c->stream);
+            e = hipMemcpyAsync(db->d_vals.get() + db->pool_used, values, (size_t)nbow * 8, hipMemcpyHostToDevice, c->stream);
         const hipError_t es = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) e = es;
         if (e != hipSuccess) return set_error("orb_kfdb_add: upload", e), ORB_ERR_HIP;
@@ -369,14 +352,9 @@ int orb_kfdb_query(orb_ctx* h, orb_kfdb* db, int nbow, const int* words, const d
     if ((st = kfdb_compact_if_due(fn, c, db)) != ORB_OK) return st;
     const size_t ns = db->ent.size();
     hipError_t e;
-    if (ns > db->ent_cap) {
-        if (db->d_ent) (void)hipFree(db->d_ent);
-        db->d_ent = nullptr;
-        db->ent_cap = 0;
-        const size_t want = std::max<size_t>(2 * ns, 256);
-        if ((e = hipMalloc((void**)&db->d_ent, want * sizeof(int2))) != hipSuccess)
+    if (ns > db->d_ent.cap()) {
+        if ((e = db->d_ent.ensure(2 * ns, 256)) != hipSuccess)
             return set_error("orb_kfdb_query: entry table", e), ORB_ERR_NOMEM;
-        db->ent_cap = want;
         db->ent_dirty = true;
     }
     try {
@@ -395,7 +373,7 @@ int orb_kfdb_query(orb_ctx* h, orb_kfdb* db, int nbow, const int* words, const d
     sg.put(o_qw, words, (size_t)nbow * 4);
     sg.put(o_qv, values, (size_t)nbow * 8);
     if (db->ent_dirty) {
-        if ((e = hipMemcpyAsync(db->d_ent, db->ent.data(), ns * sizeof(int2), hipMemcpyHostToDevice, c->stream)) !=
+        if ((e = hipMemcpyAsync(db->d_ent.get(), db->ent.data(), ns * sizeof(int2), hipMemcpyHostToDevice, c->stream)) !=
             hipSuccess)
             return set_error("orb_kfdb_query: entry table upload", e), ORB_ERR_HIP;
     }
@@ -405,13 +383,13 @@ int orb_kfdb_query(orb_ctx* h, orb_kfdb* db, int nbow, const int* words, const d
     }
     const int blocks = (int)std::min<size_t>((ns + kKfdbWaves - 1) / kKfdbWaves, kKfdbMaxBlocks);
     if (nbow <= kKfdbQueryLdsWords)
-        hipLaunchKernelGGL(k_kfdb_query<true>, dim3(blocks), dim3(kKfdbThreads), (size_t)nbow * 12, c->stream, db->d_words,
-                           db->d_vals, db->d_ent, (int)ns, sg.di<int>(o_qw), sg.di<double>(o_qv), nbow, sg.h<int>(o_cnt),
-                           sg.h<int>(o_first), sg.h<double>(o_score));
+        hipLaunchKernelGGL(k_kfdb_query<true>, dim3(blocks), dim3(kKfdbThreads), (size_t)nbow * 12, c->stream,
+                           db->d_words.get(), db->d_vals.get(), db->d_ent.get(), (int)ns, sg.di<int>(o_qw),
+                           sg.di<double>(o_qv), nbow, sg.h<int>(o_cnt), sg.h<int>(o_first), sg.h<double>(o_score));
     else
-        hipLaunchKernelGGL(k_kfdb_query<false>, dim3(blocks), dim3(kKfdbThreads), 0, c->stream, db->d_words, db->d_vals,
-                           db->d_ent, (int)ns, sg.di<int>(o_qw), sg.di<double>(o_qv), nbow, sg.h<int>(o_cnt),
-                           sg.h<int>(o_first), sg.h<double>(o_score));
+        hipLaunchKernelGGL(k_kfdb_query<false>, dim3(blocks), dim3(kKfdbThreads), 0, c->stream, db->d_words.get(),
+                           db->d_vals.get(), db->d_ent.get(), (int)ns, sg.di<int>(o_qw), sg.di<double>(o_qv), nbow,
+                           sg.h<int>(o_cnt), sg.h<int>(o_first), sg.h<double>(o_score));
     e = hipGetLastError();
     const hipError_t es = hipStreamSynchronize(c->stream);   // also when the launch failed: the uploads read db->ent
     if (e != hipSuccess) return set_error("k_kfdb_query", e), ORB_ERR_HIP;

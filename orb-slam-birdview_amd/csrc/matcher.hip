@@ -666,18 +666,14 @@ int orb_hamming_top2_frames_device(orb_ctx* h, const uint8_t* d_desc, const int*
             want[2 * p + 1] = t_frames[p];
         }
         const size_t bytes = (size_t)npairs * sizeof(int2);
-        if (bytes > c->dpairs_cap || !c->d_pairs) {
+        constexpr size_t kPairsFloor = 4096 / sizeof(int2);
+        if ((size_t)npairs > c->d_pairs.cap() || !c->d_pairs) {
             c->pairs_last.clear();   // d_pairs is about to be replaced: its old contents are no longer cached
-            if (c->d_pairs) {
-                // (a launch queued earlier may still read the old buffer)
-                if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("sync", e), ORB_ERR_HIP;
-                (void)hipFree(c->d_pairs);
-            }
-            c->d_pairs = nullptr;
-            c->dpairs_cap = 0;
-            if ((e = hipMalloc((void**)&c->d_pairs, std::max<size_t>(bytes, 4096))) != hipSuccess)
+            // (a launch queued earlier may still read the old buffer)
+            if (c->d_pairs && (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+                return set_error("sync", e), ORB_ERR_HIP;
+            if ((e = c->d_pairs.ensure(npairs, kPairsFloor)) != hipSuccess)
                 return set_error("hipMalloc pairs", e), ORB_ERR_NOMEM;
-            c->dpairs_cap = std::max<size_t>(bytes, 4096);
         }
         // staged through two pinned slots used in turn: a slot is rewritten only after the event recorded behind
         // its previous upload has completed (the call returns before its copy runs)
@@ -687,17 +683,11 @@ int orb_hamming_top2_frames_device(orb_ctx* h, const uint8_t* d_desc, const int*
             return set_error("pairs staging event", e), ORB_ERR_HIP;
         if (!c->pairs_ev[sl] && (e = hipEventCreateWithFlags(&c->pairs_ev[sl], hipEventDisableTiming)) != hipSuccess)
             return set_error("pairs staging event", e), ORB_ERR_HIP;
-        if (bytes > c->pairs_cap[sl]) {
-            if (c->h_pairs[sl]) (void)hipHostFree(c->h_pairs[sl]);
-            c->h_pairs[sl] = nullptr;
-            c->pairs_cap[sl] = 0;
-            const size_t cap = std::max<size_t>(bytes, 4096);
-            if ((e = hipHostMalloc((void**)&c->h_pairs[sl], cap, hipHostMallocDefault)) != hipSuccess)
-                return set_error("pairs pinned staging", e), ORB_ERR_NOMEM;
-            c->pairs_cap[sl] = cap;
-        }
-        std::memcpy(c->h_pairs[sl], want.data(), bytes);
-        if ((e = hipMemcpyAsync(c->d_pairs, c->h_pairs[sl], bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+        if ((e = c->h_pairs[sl].ensure(npairs, kPairsFloor)) != hipSuccess)
+            return set_error("pairs pinned staging", e), ORB_ERR_NOMEM;
+        std::memcpy(c->h_pairs[sl].get(), want.data(), bytes);
+        if ((e = hipMemcpyAsync(c->d_pairs.get(), c->h_pairs[sl].get(), bytes, hipMemcpyHostToDevice, c->stream)) !=
+                hipSuccess ||
             (e = hipEventRecord(c->pairs_ev[sl], c->stream)) != hipSuccess) {
             c->pairs_last.clear();   // the copy may or may not be queued: d_pairs' contents are unknown
             return set_error("upload pairs", e), ORB_ERR_HIP;
@@ -709,8 +699,7 @@ int orb_hamming_top2_frames_device(orb_ctx* h, const uint8_t* d_desc, const int*
     if ((e = a.reserve(Arena::align((size_t)npairs * ns * kp_cap * sizeof(uint2)) + 512)) != hipSuccess)
         return set_error("scratch", e), ORB_ERR_NOMEM;
     uint2* part = a.take<uint2>((size_t)npairs * ns * kp_cap);
-    Top2Batch tb{d_desc, d_desc, kp_cap, kp_cap, d_counts, 0, 0, reinterpret_cast<const int2*>(c->d_pairs), 0, kp_cap,
-                 0, 0};
+    Top2Batch tb{d_desc, d_desc, kp_cap, kp_cap, d_counts, 0, 0, c->d_pairs.get(), 0, kp_cap, 0, 0};
     if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
     e = launch_hamming_top2_batch(tb, npairs, kp_cap, kp_cap, d_best, d_best_idx, d_second, part, c->stream);
     if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 0, c->stream);

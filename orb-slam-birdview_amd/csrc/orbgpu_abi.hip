@@ -220,16 +220,7 @@ int build_geometry(Ctx* c, int W, int H, Geom& g, std::vector<ResizeCoef>& coefs
 }
 
 /* ---------------- buffers ---------------- */
-template <class T>
-static hipError_t grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void**)&p, std::max<size_t>(need, 256) * sizeof(T));
-    if (e == hipSuccess) cap = std::max<size_t>(need, 256);
-    return e;
-}
+constexpr size_t kGrowFloor = 256;   // elements: the extractor's buffers are never allocated smaller
 
 /* The few-launch pyramid's plan (k_pyramid_chain): the levels in segments of up to kChainSeg, one
  * launch each, every level of a segment computed from the segment's base level (the frame, or the
@@ -308,17 +299,17 @@ int Ctx::ensure_geometry(int W, int H) {
         return st;
     }
     hipError_t e;
-    if ((e = grow(d_geom, geom_cap, 1)) != hipSuccess) return set_error("hipMalloc geom", e), ORB_ERR_NOMEM;
-    if ((e = grow(d_rcoef, rcoef_cap, coefs.size())) != hipSuccess) return set_error("hipMalloc coef", e), ORB_ERR_NOMEM;
+    if ((e = d_geom.ensure(1, kGrowFloor)) != hipSuccess) return set_error("hipMalloc geom", e), ORB_ERR_NOMEM;
+    if ((e = d_rcoef.ensure(coefs.size(), kGrowFloor)) != hipSuccess) return set_error("hipMalloc coef", e), ORB_ERR_NOMEM;
     std::vector<CellDesc> cells;
     build_cells(g, cells);
-    if ((e = grow(d_cells, cells_cap, cells.size())) != hipSuccess) return set_error("hipMalloc cells", e), ORB_ERR_NOMEM;
-    if ((e = hipMemcpyAsync(d_cells, cells.data(), cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice, stream)) !=
+    if ((e = d_cells.ensure(cells.size(), kGrowFloor)) != hipSuccess) return set_error("hipMalloc cells", e), ORB_ERR_NOMEM;
+    if ((e = hipMemcpyAsync(d_cells.get(), cells.data(), cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice, stream)) !=
         hipSuccess)
         return set_error("upload cells", e), ORB_ERR_HIP;
-    if ((e = hipMemcpyAsync(d_geom, &g, sizeof g, hipMemcpyHostToDevice, stream)) != hipSuccess)
+    if ((e = hipMemcpyAsync(d_geom.get(), &g, sizeof g, hipMemcpyHostToDevice, stream)) != hipSuccess)
         return set_error("upload geom", e), ORB_ERR_HIP;
-    if ((e = hipMemcpyAsync(d_rcoef, coefs.data(), coefs.size() * sizeof(ResizeCoef), hipMemcpyHostToDevice,
+    if ((e = hipMemcpyAsync(d_rcoef.get(), coefs.data(), coefs.size() * sizeof(ResizeCoef), hipMemcpyHostToDevice,
                             stream)) != hipSuccess)
         return set_error("upload coefs", e), ORB_ERR_HIP;
     // the host path's plan (one frame in flight: levels 1..7 from the frame in segments of kChainSeg) and, for
@@ -330,10 +321,9 @@ int Ctx::ensure_geometry(int W, int H) {
         if (which == 1 && kSmallChainBase <= 0) break;
         build_chain(g, coefs, off, cjobs, pl, which ? kSmallChainBase : 0, which ? ORBGPU_MAX_LEVELS : kChainSeg);
         if (!pl.nseg) continue;
-        ChainJob*& dj = which ? d_chain2 : d_chain;
-        size_t& cap = which ? chain2_cap : chain_cap;
-        if ((e = grow(dj, cap, cjobs.size())) != hipSuccess) return set_error("hipMalloc chain", e), ORB_ERR_NOMEM;
-        if ((e = hipMemcpyAsync(dj, cjobs.data(), cjobs.size() * sizeof(ChainJob), hipMemcpyHostToDevice, stream)) !=
+        DevBuf<ChainJob>& dj = which ? d_chain2 : d_chain;
+        if ((e = dj.ensure(cjobs.size(), kGrowFloor)) != hipSuccess) return set_error("hipMalloc chain", e), ORB_ERR_NOMEM;
+        if ((e = hipMemcpyAsync(dj.get(), cjobs.data(), cjobs.size() * sizeof(ChainJob), hipMemcpyHostToDevice, stream)) !=
             hipSuccess)
             return set_error("upload chain", e), ORB_ERR_HIP;
         if (which == 0) chain_jobs_host = cjobs;
@@ -351,24 +341,24 @@ int Ctx::ensure_geometry(int W, int H) {
 int Ctx::ensure_frames(int nframes) {
     const Geom& g = geom;
     hipError_t e;
-    const bool fresh_err = d_err == nullptr;
+    const bool fresh_err = !d_err;
     const size_t nl = g.nlevels;
-    if ((e = grow(d_pyr, pyr_cap, (size_t)nframes * g.pyr_bytes)) != hipSuccess ||
-        (e = grow(d_cands, cands_cap, (size_t)nframes * g.ncand)) != hipSuccess ||
-        (e = grow(d_candFirst, candfirst_cap, (size_t)nframes * g.ncells * kCandRec)) != hipSuccess ||
-        (e = grow(d_keys, keys_cap, (size_t)nframes * nl * g.max_level_cand)) != hipSuccess ||
-        (e = grow(d_knode, knode_cap, (size_t)nframes * nl * g.max_level_cand)) != hipSuccess ||
-        (e = grow(d_lvlKps, lvlkps_cap, (size_t)nframes * g.nkpcap)) != hipSuccess ||
-        (e = grow(d_lvlCount, lvlc_cap, (size_t)nframes * nl)) != hipSuccess ||
-        (e = grow(d_err, err_cap, 2)) != hipSuccess) {
+    if ((e = d_pyr.ensure((size_t)nframes * g.pyr_bytes, kGrowFloor)) != hipSuccess ||
+        (e = d_cands.ensure((size_t)nframes * g.ncand, kGrowFloor)) != hipSuccess ||
+        (e = d_candFirst.ensure((size_t)nframes * g.ncells * kCandRec, kGrowFloor)) != hipSuccess ||
+        (e = d_keys.ensure((size_t)nframes * nl * g.max_level_cand, kGrowFloor)) != hipSuccess ||
+        (e = d_knode.ensure((size_t)nframes * nl * g.max_level_cand, kGrowFloor)) != hipSuccess ||
+        (e = d_lvlKps.ensure((size_t)nframes * g.nkpcap, kGrowFloor)) != hipSuccess ||
+        (e = d_lvlCount.ensure((size_t)nframes * nl, kGrowFloor)) != hipSuccess ||
+        (e = d_err.ensure(2, kGrowFloor)) != hipSuccess) {
         set_error("device allocation for the extractor", e);
         return ORB_ERR_NOMEM;
     }
-    if (fast_stamps && (e = grow(d_stamps, stamps_cap, (size_t)nframes * (g.ncells * 8 + g.nlevels * 32 + g.nkpcap * 8))) != hipSuccess)
+    if (fast_stamps && (e = d_stamps.ensure((size_t)nframes * (g.ncells * 8 + g.nlevels * 32 + g.nkpcap * 8), kGrowFloor)) != hipSuccess)
         return set_error("stamps", e), ORB_ERR_NOMEM;
     // the overflow flag is read by orb_sync even before the first extraction (every extraction zeroes
     // it in its first kernel)
-    if (fresh_err && (e = hipMemsetAsync(d_err, 0, 2 * sizeof(int), stream)) != hipSuccess)
+    if (fresh_err && (e = hipMemsetAsync(d_err.get(), 0, 2 * sizeof(int), stream)) != hipSuccess)
         return set_error("memset", e), ORB_ERR_HIP;
     return ORB_OK;
 }
@@ -390,18 +380,18 @@ int Ctx::ensure_flow(int nframes) {
     flow_chain_plan = use_chain ? chain : ChainPlan{};
     hipError_t e;
     // (a launch queued earlier may still read the old task table or counters)
-    if ((tasks.size() > flow_cap || (size_t)pl.nctr > flow_ctr_cap) && (e = hipStreamSynchronize(stream)) != hipSuccess)
+    if ((tasks.size() > d_flow.cap() || (size_t)pl.nctr > d_flow_ctr.cap()) && (e = hipStreamSynchronize(stream)) != hipSuccess)
         return set_error("sync", e), ORB_ERR_HIP;
-    if ((e = grow(d_flow, flow_cap, tasks.size())) != hipSuccess) return set_error("hipMalloc flow tasks", e), ORB_ERR_NOMEM;
-    const bool fresh = (size_t)pl.nctr > flow_ctr_cap || !d_flow_ctr;
-    if ((e = grow(d_flow_ctr, flow_ctr_cap, (size_t)pl.nctr)) != hipSuccess)
+    if ((e = d_flow.ensure(tasks.size(), kGrowFloor)) != hipSuccess) return set_error("hipMalloc flow tasks", e), ORB_ERR_NOMEM;
+    const bool fresh = (size_t)pl.nctr > d_flow_ctr.cap() || !d_flow_ctr;
+    if ((e = d_flow_ctr.ensure((size_t)pl.nctr, kGrowFloor)) != hipSuccess)
         return set_error("hipMalloc flow counters", e), ORB_ERR_NOMEM;
-    if (fresh && (e = hipMemsetAsync(d_flow_ctr, 0, flow_ctr_cap * sizeof(int), stream)) != hipSuccess)
+    if (fresh && (e = hipMemsetAsync(d_flow_ctr.get(), 0, d_flow_ctr.cap() * sizeof(int), stream)) != hipSuccess)
         return set_error("memset flow counters", e), ORB_ERR_HIP;
-    if ((e = hipMemcpyAsync(d_flow, tasks.data(), tasks.size() * sizeof(FlowTask), hipMemcpyHostToDevice, stream)) !=
+    if ((e = hipMemcpyAsync(d_flow.get(), tasks.data(), tasks.size() * sizeof(FlowTask), hipMemcpyHostToDevice, stream)) !=
         hipSuccess)
         return set_error("upload flow tasks", e), ORB_ERR_HIP;
-    if (flow_stamps && (e = grow(d_flow_stamps, flow_stamps_cap, (size_t)pl.ntasks * 4)) != hipSuccess)
+    if (flow_stamps && (e = d_flow_stamps.ensure((size_t)pl.ntasks * 4, kGrowFloor)) != hipSuccess)
         return set_error("hipMalloc flow stamps", e), ORB_ERR_NOMEM;
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return set_error("sync", e), ORB_ERR_HIP;
     flow = pl;
@@ -412,23 +402,23 @@ int Ctx::ensure_flow(int nframes) {
 
 ExtractBuffers Ctx::buffers() const {
     ExtractBuffers b;
-    b.d_geom = d_geom;
-    b.d_rcoef = d_rcoef;
-    b.d_cells = d_cells;
+    b.d_geom = d_geom.get();
+    b.d_rcoef = d_rcoef.get();
+    b.d_cells = d_cells.get();
     std::memcpy(b.rcoef_off, rcoef_off, sizeof rcoef_off);
-    b.d_chain = d_chain;
+    b.d_chain = d_chain.get();
     b.chain = chain;
-    b.d_pyr = d_pyr;
-    b.d_cands = d_cands;
-    b.d_candFirst = d_candFirst;
-    b.d_keys = d_keys;
-    b.d_knode = d_knode;
-    b.d_lvlKps = d_lvlKps;
-    b.d_lvlCount = d_lvlCount;
-    b.d_err = d_err;
+    b.d_pyr = d_pyr.get();
+    b.d_cands = d_cands.get();
+    b.d_candFirst = d_candFirst.get();
+    b.d_keys = d_keys.get();
+    b.d_knode = d_knode.get();
+    b.d_lvlKps = d_lvlKps.get();
+    b.d_lvlCount = d_lvlCount.get();
+    b.d_err = d_err.get();
     b.zero_err = 1;
     b.err_host = nullptr;
-    b.d_stamps = fast_stamps ? d_stamps : nullptr;
+    b.d_stamps = fast_stamps ? d_stamps.get() : nullptr;
     b.fork_s2 = nullptr;
     b.ev_fork = b.ev_join = nullptr;
     b.d_flow = nullptr;
@@ -459,34 +449,34 @@ int Ctx::run_extract(const uint8_t* d_frames, int nframes, long long frame_pitch
     // frame in flight (the host path); batches of a frame or two (C5 at one frame per GPU) take the small plan
     if (!latency) {
         bufs.chain = chain_small;
-        bufs.d_chain = d_chain2;
+        bufs.d_chain = d_chain2.get();
     }
     // small batches: the dataflow launch (stamps are per-kernel diagnostics: the per-kernel launches)
     if (!latency && nframes <= flow_max_frames && !fast_stamps) {
         const int st = ensure_flow(nframes);
         if (st != ORB_OK) return st;
         if (flow_ok) {
-            bufs.d_flow = d_flow;
-            bufs.d_flow_ctr = d_flow_ctr;
+            bufs.d_flow = d_flow.get();
+            bufs.d_flow_ctr = d_flow_ctr.get();
             bufs.flow = flow;
             bufs.flow_chain = flow_chain_plan;
-            bufs.d_chain = d_chain;   // (the chain tasks' jobs: the host-path plan, levels from the frame)
+            bufs.d_chain = d_chain.get();   // (the chain tasks' jobs: the host-path plan, levels from the frame)
             // the kernel reads its arguments from device memory: uploaded when they differ from the last call's
             // (stream-ordered behind the launches still reading the old ones; a pageable copy of 0.2 KB returns once
             // the runtime has staged it)
-            if (!d_flow_args && (e = hipMalloc((void**)&d_flow_args, sizeof(FlowArgs))) != hipSuccess)
+            if ((e = d_flow_args.ensure(1)) != hipSuccess)
                 return set_error("hipMalloc flow args", e), ORB_ERR_NOMEM;
-            bufs.d_flow_stamps = flow_stamps ? d_flow_stamps : nullptr;
+            bufs.d_flow_stamps = flow_stamps ? d_flow_stamps.get() : nullptr;
             const FlowArgs A = flow_args(bufs, d_frames, frame_pitch, row_stride, nframes, d_kps, d_desc, d_counts, kp_cap);
             if (std::memcmp(&A, &h_flow_args, sizeof A) != 0 || !flow_args_valid) {
-                if ((e = hipMemcpyAsync(d_flow_args, &A, sizeof A, hipMemcpyHostToDevice, stream)) != hipSuccess) {
+                if ((e = hipMemcpyAsync(d_flow_args.get(), &A, sizeof A, hipMemcpyHostToDevice, stream)) != hipSuccess) {
                     flow_args_valid = false;
                     return set_error("upload flow args", e), ORB_ERR_HIP;
                 }
                 h_flow_args = A;
                 flow_args_valid = true;
             }
-            bufs.d_flow_args = d_flow_args;
+            bufs.d_flow_args = d_flow_args.get();
         }
     }
     // one frame in flight (ORBGPU_FORK=1): level 0's FAST -> octree on a second stream beside the pyramid
@@ -510,9 +500,9 @@ int Ctx::run_extract(const uint8_t* d_frames, int nframes, long long frame_pitch
         const std::array<uintptr_t, 24> key = {
             (uintptr_t)d_frames, (uintptr_t)nframes, (uintptr_t)frame_pitch, (uintptr_t)row_stride, (uintptr_t)d_kps,
             (uintptr_t)d_desc, (uintptr_t)d_counts, (uintptr_t)kp_cap, (uintptr_t)geom.W, (uintptr_t)geom.H,
-            (uintptr_t)geom_serial, (uintptr_t)d_geom, (uintptr_t)d_rcoef, (uintptr_t)d_cells, (uintptr_t)d_pyr,
-            (uintptr_t)d_cands, (uintptr_t)d_candFirst, (uintptr_t)d_keys, (uintptr_t)d_knode, (uintptr_t)d_lvlKps,
-            (uintptr_t)d_lvlCount, (uintptr_t)bufs.d_err, (uintptr_t)stream,
+            (uintptr_t)geom_serial, (uintptr_t)bufs.d_geom, (uintptr_t)bufs.d_rcoef, (uintptr_t)bufs.d_cells,
+            (uintptr_t)bufs.d_pyr, (uintptr_t)bufs.d_cands, (uintptr_t)bufs.d_candFirst, (uintptr_t)bufs.d_keys,
+            (uintptr_t)bufs.d_knode, (uintptr_t)bufs.d_lvlKps, (uintptr_t)bufs.d_lvlCount, (uintptr_t)bufs.d_err, (uintptr_t)stream,
             (uintptr_t)bufs.chain.nseg ^ ((uintptr_t)err_host << 4) ^ ((uintptr_t)(bufs.fork_s2 != nullptr) << 3) ^
                 ((uintptr_t)bufs.d_flow << 8) ^ ((uintptr_t)bufs.flow.ntasks << 1) ^ ((uintptr_t)bufs.flow.blocks << 20)};
         if (!gexec || key != gkey) {
@@ -645,26 +635,15 @@ void orb_destroy(orb_ctx* h) {
         (void)hipEventDestroy(pr.b);
         (void)hipEventDestroy(pr.e);
     }
-    void* bufs[] = {c->d_flow, c->d_flow_ctr, c->d_flow_args, c->d_flow_stamps, c->d_cells, c->d_stamps, c->d_geom, c->d_rcoef, c->d_chain, c->d_chain2, c->d_pyr, c->d_cands, c->d_candFirst, c->d_keys, c->d_knode,
-                    c->d_lvlKps, c->d_lvlCount, c->d_err, c->d_in,
-                    c->d_scratch, c->d_peer, c->d_pairs};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-    if (c->h_mstage) (void)hipHostFree(c->h_mstage);
-    if (c->h_img) (void)hipHostFree(c->h_img);
-    if (c->h_flags) (void)hipHostFree(c->h_flags);
-    for (int i = 0; i < 2; i++) {
-        if (c->h_pairs[i]) (void)hipHostFree(c->h_pairs[i]);
+    for (int i = 0; i < 2; i++)
         if (c->pairs_ev[i]) (void)hipEventDestroy(c->pairs_ev[i]);
-    }
     if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    delete c;
+    delete c;   // (the device and pinned buffers free themselves: the device is current, the stream idle)
 }
 
 int orb_scale_tables(const orb_ctx* h, float* scale, float* inv_scale, float* sigma2, float* inv_sigma2,
@@ -715,7 +694,7 @@ int orb_sync(orb_ctx* h) {
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return set_error("hipStreamSynchronize", e), ORB_ERR_HIP;
     int err[2] = {0, 0};
-    if (c->d_err && (e = hipMemcpy(err, c->d_err, sizeof err, hipMemcpyDeviceToHost)) != hipSuccess)
+    if (c->d_err && (e = hipMemcpy(err, c->d_err.get(), sizeof err, hipMemcpyDeviceToHost)) != hipSuccess)
         return set_error("read error flag", e), ORB_ERR_HIP;
     if (err[0] | err[1]) {
         set_error((err[1] & 4) ? "dataflow launch: a task's wait timed out (outputs invalid)"
@@ -739,51 +718,35 @@ int orb_extract(orb_ctx* h, const uint8_t* img, int w, int hgt, size_t stride, o
     const int kcap = c->geom.nkpcap;
     const size_t kbytes = ((size_t)kcap * sizeof(orb_keypoint) + 63) & ~(size_t)63;   // descriptors 64-B aligned
     const size_t need = 16 + kbytes + (size_t)kcap * 32;
-    if ((e = grow(c->d_in, c->in_cap, pitch * hgt)) != hipSuccess) return set_error("device allocation", e), ORB_ERR_NOMEM;
+    if ((e = c->d_in.ensure(pitch * hgt, kGrowFloor)) != hipSuccess) return set_error("device allocation", e), ORB_ERR_NOMEM;
     // every allocation before the first launch: with the streamed upload the upload kernel queued below polls for
     // the host copy that follows it, so nothing in between may block on the stream (hipHostFree / hipFree do)
-    if (need > c->pinned_cap) {
-        if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-        c->h_pinned = nullptr;
-        c->pinned_cap = 0;
-        // mapped + coherent (fine-grained) explicitly: k_describe stores the outputs straight into this block and
-        // the host reads them after hipStreamSynchronize, with no D2H copy in between
-        if ((e = hipHostMalloc(&c->h_pinned, need, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
-            return set_error("pinned staging", e), ORB_ERR_NOMEM;
-        c->pinned_cap = need;
-    }
+    // mapped + coherent (fine-grained): k_describe stores the outputs straight into this block and the host reads
+    // them after hipStreamSynchronize, with no D2H copy in between
+    if ((e = c->h_pinned.ensure(need)) != hipSuccess) return set_error("pinned staging", e), ORB_ERR_NOMEM;
     constexpr int kBands = 16;   // (h_flags[kBands .. 63]: [63] = the upload kernel's timeout flag)
     const int band_rows = (hgt + kBands - 1) / kBands, nbands = (hgt + band_rows - 1) / band_rows;
     if (c->upload_stream) {
-        if (pitch * hgt > c->himg_cap) {
-            if (c->h_img) (void)hipHostFree(c->h_img);
-            c->h_img = nullptr;
-            c->himg_cap = 0;
-            if ((e = hipHostMalloc((void**)&c->h_img, pitch * hgt, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
-                return set_error("pinned image staging", e), ORB_ERR_NOMEM;
-            c->himg_cap = pitch * hgt;
-        }
+        if ((e = c->h_img.ensure(pitch * hgt)) != hipSuccess) return set_error("pinned image staging", e), ORB_ERR_NOMEM;
         if (!c->h_flags) {
-            if ((e = hipHostMalloc((void**)&c->h_flags, 64 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent)) !=
-                hipSuccess)
-                return set_error("pinned upload flags", e), ORB_ERR_NOMEM;
-            std::memset(c->h_flags, 0, 64 * sizeof(uint32_t));
+            if ((e = c->h_flags.ensure(64)) != hipSuccess) return set_error("pinned upload flags", e), ORB_ERR_NOMEM;
+            std::memset(c->h_flags.get(), 0, 64 * sizeof(uint32_t));
         }
         if (++c->upload_seq == 0) c->upload_seq = 1;   // (flags start at 0)
         // the upload kernel first; the host copy raising the band flags follows (below), then the extraction launches
-        if ((e = launch_upload_stream(c->h_img, c->h_flags, c->upload_seq, c->d_in, (int)pitch, hgt, nbands, band_rows,
-                                      c->h_flags + 63, c->stream)) != hipSuccess)
+        if ((e = launch_upload_stream(c->h_img.get(), c->h_flags.get(), c->upload_seq, c->d_in.get(), (int)pitch, hgt,
+                                      nbands, band_rows, c->h_flags.get() + 63, c->stream)) != hipSuccess)
             return set_error("upload kernel", e), ORB_ERR_HIP;
     } else {
         // pageable 2-D upload (measured faster than a host copy into pinned staging + one DMA: 0.149 vs 0.168
         // ms per C3 frame end to end, tools/host_latency; profiles/r03/latency_probe_upload.json)
-        if ((e = hipMemcpy2DAsync(c->d_in, pitch, img, stride, w, hgt, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+        if ((e = hipMemcpy2DAsync(c->d_in.get(), pitch, img, stride, w, hgt, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
             return set_error("upload image", e), ORB_ERR_HIP;
     }
     // output block [count | overflow flag | 8 B pad | keypoints | descriptors] in pinned, host-coherent
     // memory: k_describe writes the keypoints, descriptors and count straight into it (and copies the
     // octree's overflow flag), so no download follows the kernels
-    uint8_t* hp = static_cast<uint8_t*>(c->h_pinned);
+    uint8_t* hp = c->h_pinned.get();
     int* hcnt = reinterpret_cast<int*>(hp);
     orb_keypoint* hk = reinterpret_cast<orb_keypoint*>(hp + 16);
     uint8_t* hd = hp + 16 + kbytes;
@@ -793,15 +756,15 @@ int orb_extract(orb_ctx* h, const uint8_t* img, int w, int hgt, size_t stride, o
         // launches: the upload kernel pulls each band over PCIe while the host copies the next
         for (int b = 0; b < nbands; b++) {
             const int r0 = b * band_rows, r1 = std::min(hgt, r0 + band_rows);
-            for (int r = r0; r < r1; r++) std::memcpy(c->h_img + (size_t)r * pitch, img + (size_t)r * stride, (size_t)w);
-            __atomic_store_n(c->h_flags + b, c->upload_seq, __ATOMIC_RELEASE);
+            for (int r = r0; r < r1; r++) std::memcpy(c->h_img.get() + (size_t)r * pitch, img + (size_t)r * stride, (size_t)w);
+            __atomic_store_n(c->h_flags.get() + b, c->upload_seq, __ATOMIC_RELEASE);
         }
     }
-    st = c->run_extract(c->d_in, 1, (long long)pitch * hgt, (int)pitch, hk, hd, hcnt, kcap, nullptr, true, hcnt + 1);
+    st = c->run_extract(c->d_in.get(), 1, (long long)pitch * hgt, (int)pitch, hk, hd, hcnt, kcap, nullptr, true, hcnt + 1);
     if (st != ORB_OK) return st;
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("extract", e), ORB_ERR_HIP;
-    if (c->upload_stream && __atomic_load_n(c->h_flags + 63, __ATOMIC_ACQUIRE)) {
-        c->h_flags[63] = 0;
+    if (c->upload_stream && __atomic_load_n(c->h_flags.get() + 63, __ATOMIC_ACQUIRE)) {
+        c->h_flags.get()[63] = 0;
         return set_error("streamed image upload timed out", hipSuccess), ORB_ERR_INTERNAL;
     }
     if (hcnt[1]) {
@@ -834,7 +797,7 @@ static int level_view(Ctx* c, int frame, int level, uint8_t* dst, int* w, int* h
         e = hipMemcpy2DAsync(dst, L.w, c->last_frames + frame * c->last_frame_pitch, c->last_row_stride, L.w, L.h,
                              hipMemcpyDeviceToHost, c->stream);
     else
-        e = hipMemcpy2DAsync(dst, L.w, c->d_pyr + frame * c->geom.pyr_bytes + L.pyr_off, L.pitch, L.w, L.h,
+        e = hipMemcpy2DAsync(dst, L.w, c->d_pyr.get() + frame * c->geom.pyr_bytes + L.pyr_off, L.pitch, L.w, L.h,
                              hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return set_error("download level", e), ORB_ERR_HIP;
@@ -864,13 +827,13 @@ int orb_debug_fast_stamps(orb_ctx* h, uint64_t* out, int cap) {
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
     if (c->flow_stamps && c->d_flow_stamps) {   // the dataflow launch's per-task stamps
-        const int n = std::min((int)c->flow_stamps_cap, cap);
-        hipError_t e = hipMemcpy(out, c->d_flow_stamps, (size_t)n * 8, hipMemcpyDeviceToHost);
+        const int n = std::min((int)c->d_flow_stamps.cap(), cap);
+        hipError_t e = hipMemcpy(out, c->d_flow_stamps.get(), (size_t)n * 8, hipMemcpyDeviceToHost);
         return e == hipSuccess ? n : ORB_ERR_HIP;
     }
     if (!c->fast_stamps || !c->d_stamps) return 0;
-    const int n = std::min((int)c->stamps_cap, cap);
-    hipError_t e = hipMemcpy(out, c->d_stamps, (size_t)n * 8, hipMemcpyDeviceToHost);
+    const int n = std::min((int)c->d_stamps.cap(), cap);
+    hipError_t e = hipMemcpy(out, c->d_stamps.get(), (size_t)n * 8, hipMemcpyDeviceToHost);
     return e == hipSuccess ? n : ORB_ERR_HIP;
 }
 
@@ -879,15 +842,15 @@ int orb_debug_sincosf(orb_ctx* h, const float* x, int n, float* s, float* c) {
     CTX_GUARD(ctx);
     if (n < 0 || (n > 0 && (!x || !s || !c))) return set_error("orb_debug_sincosf: bad arguments", hipSuccess), ORB_ERR_ARG;
     if (n == 0) return ORB_OK;
-    float* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, (size_t)n * 12);
+    DevBuf<float> buf;
+    hipError_t e = buf.ensure((size_t)n * 3);
     if (e != hipSuccess) return set_error("hipMalloc", e), ORB_ERR_NOMEM;
+    float* d = buf.get();
     if ((e = hipMemcpyAsync(d, x, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream)) == hipSuccess &&
         (e = launch_debug_sincosf(d, n, d + n, d + 2 * (size_t)n, ctx->stream)) == hipSuccess &&
         (e = hipMemcpyAsync(s, d + n, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream)) == hipSuccess &&
         (e = hipMemcpyAsync(c, d + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream)) == hipSuccess)
         e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     return e == hipSuccess ? ORB_OK : (set_error("orb_debug_sincosf", e), ORB_ERR_HIP);
 }
 
@@ -907,9 +870,9 @@ int orb_debug_candidates(orb_ctx* h, int frame, int level, int* out, int cap) {
     std::vector<uint32_t> slots((size_t)L.cand_cap), rec((size_t)ncl * kCandRec);   // [count | first corners]
     hipError_t e;
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess ||
-        (e = hipMemcpy(rec.data(), c->d_candFirst + ((size_t)frame * c->geom.ncells + L.cell_base) * kCandRec,
+        (e = hipMemcpy(rec.data(), c->d_candFirst.get() + ((size_t)frame * c->geom.ncells + L.cell_base) * kCandRec,
                        rec.size() * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess ||
-        (e = hipMemcpy(slots.data(), c->d_cands + (size_t)frame * c->geom.ncand + L.cand_base,
+        (e = hipMemcpy(slots.data(), c->d_cands.get() + (size_t)frame * c->geom.ncand + L.cand_base,
                        slots.size() * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess)
         return set_error("download candidates", e), ORB_ERR_HIP;
     int n = 0;
@@ -936,9 +899,9 @@ int orb_debug_level_keypoints(orb_ctx* h, int frame, int level, int* out, int ca
     std::vector<uint32_t> v((size_t)L.kp_cap);
     hipError_t e;
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess ||
-        (e = hipMemcpy(&n, c->d_lvlCount + (size_t)frame * c->geom.nlevels + level, sizeof(int),
+        (e = hipMemcpy(&n, c->d_lvlCount.get() + (size_t)frame * c->geom.nlevels + level, sizeof(int),
                        hipMemcpyDeviceToHost)) != hipSuccess ||
-        (e = hipMemcpy(v.data(), c->d_lvlKps + (size_t)frame * c->geom.nkpcap + L.kp_base, v.size() * 4,
+        (e = hipMemcpy(v.data(), c->d_lvlKps.get() + (size_t)frame * c->geom.nkpcap + L.kp_base, v.size() * 4,
                        hipMemcpyDeviceToHost)) != hipSuccess)
         return set_error("download level keypoints", e), ORB_ERR_HIP;
     if (n > cap) return -n - 1;

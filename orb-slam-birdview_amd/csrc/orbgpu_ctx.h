@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "buf.h"
 #include "orbgpu_internal.h"
 
 namespace orbgpu {
@@ -25,6 +26,29 @@ inline int arg_error(const char* fn, const std::string& why) {
         if (_e != hipSuccess) return orbgpu::set_error("hipSetDevice", _e), ORB_ERR_HIP;  \
     }
 
+// Buf's memory policies: device memory, pinned host memory with the default flags, and pinned host memory the kernels
+// store into directly (mapped + coherent: the host reads it after a stream synchronisation, with no D2H copy)
+struct DeviceMem {
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+struct MappedMem {
+    static hipError_t alloc(void** p, size_t bytes) {
+        return hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+    }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T>
+using DevBuf = Buf<T, DeviceMem>;
+template <class T>
+using PinBuf = Buf<T, PinnedMem>;
+template <class T>
+using MapBuf = Buf<T, MappedMem>;
+
 struct ProfPair {
     int id;
     hipEvent_t b, e;
@@ -36,8 +60,7 @@ struct Ctx {
     int num_cu = 256;
     bool fast_stamps = false;     // ORBGPU_FAST_STAMPS=1: the kernels record phase timestamps (diagnostic)
     bool stereo_stage = false;    // ORBGPU_STEREO_STAGE=1: stereo stages the right side as for a peer GPU (test)
-    unsigned long long* d_stamps = nullptr;
-    size_t stamps_cap = 0;
+    DevBuf<unsigned long long> d_stamps;
     hipStream_t stream = nullptr;
     // the host path's second stream and fork / join events (Ctx::run_extract latency mode; ORBGPU_FORK=1: on.  Off by
     // default: 0.1154-0.1198 ms per C3 frame forked against 0.1074 ms in one stream, profiles/r04/v3_host_path.txt)
@@ -57,53 +80,37 @@ struct Ctx {
     bool have_geom = false;
     Geom geom{};
     int rcoef_off[ORBGPU_MAX_LEVELS]{};
-    Geom* d_geom = nullptr;
-    size_t geom_cap = 0;
-    ResizeCoef* d_rcoef = nullptr;
-    size_t rcoef_cap = 0;
-    ChainJob* d_chain = nullptr;   // the one-launch pyramid's jobs (small batches)
-    size_t chain_cap = 0;
+    DevBuf<Geom> d_geom;
+    DevBuf<ResizeCoef> d_rcoef;
+    DevBuf<ChainJob> d_chain;   // the one-launch pyramid's jobs (small batches)
     ChainPlan chain{};
     std::vector<ChainJob> chain_jobs_host;   // (the dataflow launch's chain tasks index them)
-    ChainJob* d_chain2 = nullptr;  // the small-batch plan (levels past kSmallChainBase in one launch)
-    size_t chain2_cap = 0;
+    DevBuf<ChainJob> d_chain2;  // the small-batch plan (levels past kSmallChainBase in one launch)
     ChainPlan chain_small{};
-    CellDesc* d_cells = nullptr;
-    size_t cells_cap = 0;
+    DevBuf<CellDesc> d_cells;
 
-    // extractor work buffers (capacities in elements)
-    uint8_t* d_pyr = nullptr;
-    size_t pyr_cap = 0;
-    uint32_t* d_cands = nullptr;
-    size_t cands_cap = 0;
-    uint32_t* d_candFirst = nullptr;
-    size_t candfirst_cap = 0;
-    uint32_t* d_keys = nullptr;
-    size_t keys_cap = 0;
-    uint16_t* d_knode = nullptr;
-    size_t knode_cap = 0;
-    uint32_t* d_lvlKps = nullptr;
-    size_t lvlkps_cap = 0;
-    int* d_lvlCount = nullptr;
-    size_t lvlc_cap = 0;
-    int* d_err = nullptr;
-    size_t err_cap = 0;
+    // extractor work buffers
+    DevBuf<uint8_t> d_pyr;
+    DevBuf<uint32_t> d_cands;
+    DevBuf<uint32_t> d_candFirst;
+    DevBuf<uint32_t> d_keys;
+    DevBuf<uint16_t> d_knode;
+    DevBuf<uint32_t> d_lvlKps;
+    DevBuf<int> d_lvlCount;
+    DevBuf<int> d_err;
 
     // host-image path (orb_extract)
-    uint8_t* d_in = nullptr;
-    size_t in_cap = 0;
+    DevBuf<uint8_t> d_in;
     // streamed upload (k_upload_stream; off by default, ORBGPU_UPLOAD=1 turns it on; off = the pageable
     // hipMemcpy2DAsync): the image's pinned host-coherent staging copy and the per-band flags the host raises (call
     // sequence numbers)
     bool upload_stream = false;
-    uint8_t* h_img = nullptr;
-    size_t himg_cap = 0;
-    uint32_t* h_flags = nullptr;
+    MapBuf<uint8_t> h_img;
+    MapBuf<uint32_t> h_flags;
     uint32_t upload_seq = 0;
     // orb_extract's outputs [count | flag | pad | keypoints | descriptors]: host-coherent pinned memory the
     // kernels write directly (no download)
-    void* h_pinned = nullptr;
-    size_t pinned_cap = 0;
+    MapBuf<uint8_t> h_pinned;
 
     // orb_search_for_triangulation's host lists, kept across calls (capacity reused: a call is ~30 us, and its
     // dozens of small allocations were a measurable part of it)
@@ -111,23 +118,18 @@ struct Ctx {
     std::vector<int> tri_hist[30];
     // orb_hamming_top2_frames_device: the pair list on the device (re-uploaded only when it changes), the list it
     // holds, and two pinned staging slots used in turn
-    int* d_pairs = nullptr;
-    size_t dpairs_cap = 0;
+    DevBuf<int2> d_pairs;
     std::vector<int> pairs_last;
-    int* h_pairs[2] = {nullptr, nullptr};
-    size_t pairs_cap[2] = {0, 0};
+    PinBuf<int2> h_pairs[2];
     hipEvent_t pairs_ev[2] = {nullptr, nullptr};
     int pairs_slot = 0;
     // matcher scratch arena (bytes)
-    uint8_t* d_scratch = nullptr;
-    size_t scratch_cap = 0;
+    DevBuf<uint8_t> d_scratch;
     // pinned mirror of the matcher arena: a call's inputs are packed here at the device offsets and go up
     // in one DMA, its outputs come back in one (matcher.hip Stage)
-    uint8_t* h_mstage = nullptr;
-    size_t mstage_cap = 0;
+    MapBuf<uint8_t> h_mstage;
     // the right extractor's frame + pyramid when it runs on another GPU (orb_compute_stereo_matches)
-    uint8_t* d_peer = nullptr;
-    size_t peer_cap = 0;
+    DevBuf<uint8_t> d_peer;
 
     // last batch (for the mvImagePyramid view and debug reads)
     const uint8_t* last_frames = nullptr;
@@ -158,18 +160,15 @@ struct Ctx {
     // counters it waits on
     int flow_max_frames = 0;
     int flow_blocks = 0;            // workgroups per launch (ORBGPU_FLOW_BLOCKS; 0: the default, kFlowDefaultBlocks)
-    FlowTask* d_flow = nullptr;
-    size_t flow_cap = 0;
-    int* d_flow_ctr = nullptr;
-    size_t flow_ctr_cap = 0;
+    DevBuf<FlowTask> d_flow;
+    DevBuf<int> d_flow_ctr;
     FlowPlan flow{};
     ChainPlan flow_chain_plan{};
-    FlowArgs* d_flow_args = nullptr;   // the last uploaded arguments (h_flow_args mirrors them)
+    DevBuf<FlowArgs> d_flow_args;  // the last uploaded arguments (h_flow_args mirrors them)
     FlowArgs h_flow_args{};
     bool flow_args_valid = false;
     bool flow_stamps = false;       // ORBGPU_FLOW_STAMPS=1: per-task timestamps (orb_debug_fast_stamps returns them)
-    unsigned long long* d_flow_stamps = nullptr;
-    size_t flow_stamps_cap = 0;
+    DevBuf<unsigned long long> d_flow_stamps;
     unsigned flow_serial = 0;       // geom_serial the plan was built for
     bool flow_ok = false;           // flow holds a plan for (flow_serial, flow.nframes)
 
@@ -201,19 +200,11 @@ struct Arena {
     Ctx* c;
     size_t off = 0;
     static size_t align(size_t x) { return (x + 255) & ~(size_t)255; }
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= c->scratch_cap && c->d_scratch) return hipSuccess;
-        if (c->d_scratch) (void)hipFree(c->d_scratch);
-        c->d_scratch = nullptr;
-        c->scratch_cap = 0;
-        hipError_t e = hipMalloc((void**)&c->d_scratch, bytes);
-        if (e == hipSuccess) c->scratch_cap = bytes;
-        return e;
-    }
+    hipError_t reserve(size_t bytes) { return c->d_scratch.ensure(bytes); }
     template <class T>
     T* take(size_t n) {
         off = align(off);
-        T* p = (T*)(c->d_scratch + off);
+        T* p = (T*)(c->d_scratch.get() + off);
         off += std::max<size_t>(n, 1) * sizeof(T);
         return p;
     }
@@ -246,42 +237,31 @@ struct Stage {
         hipError_t e = a.reserve(need);
         if (e != hipSuccess) return set_error("matcher scratch", e), ORB_ERR_NOMEM;
         const size_t hneed = (mirror_end ? mirror_end : Arena::align(off)) + 4096;
-        if (hneed > c->mstage_cap || !c->h_mstage) {
-            if (c->h_mstage) (void)hipHostFree(c->h_mstage);
-            c->h_mstage = nullptr;
-            c->mstage_cap = 0;
-            const size_t cap = std::max<size_t>(hneed, 1 << 20);
-            // mapped + coherent explicitly: the matcher kernels store their results straight into this mirror
-            // and the host reads them after the stream synchronisation, with no D2H copy
-            if ((e = hipHostMalloc((void**)&c->h_mstage, cap, hipHostMallocMapped | hipHostMallocCoherent)) !=
-                hipSuccess)
-                return set_error("matcher pinned staging", e), ORB_ERR_NOMEM;
-            c->mstage_cap = cap;
-        }
+        // (mapped + coherent: the matcher kernels store their results straight into this mirror)
+        if ((e = c->h_mstage.ensure(hneed, 1 << 20)) != hipSuccess)
+            return set_error("matcher pinned staging", e), ORB_ERR_NOMEM;
         return ORB_OK;
     }
     template <class T>
-    T* h(size_t o) const { return reinterpret_cast<T*>(c->h_mstage + o); }   // outputs (host view)
+    T* h(size_t o) const { return reinterpret_cast<T*>(c->h_mstage.get() + o); }   // outputs (host view)
     template <class T>
-    T* d(size_t o) const { return reinterpret_cast<T*>(c->d_scratch + o); }
+    T* d(size_t o) const { return reinterpret_cast<T*>(c->d_scratch.get() + o); }
     template <class T>
-    T* hi(size_t o) const { return reinterpret_cast<T*>(c->h_mstage + o); }   // inputs, written by the host
+    T* hi(size_t o) const { return reinterpret_cast<T*>(c->h_mstage.get() + o); }   // inputs, written by the host
     template <class T>
     T* di(size_t o) const {   // inputs, as the kernels read them
-        return zc ? reinterpret_cast<T*>(c->h_mstage + o) : d<T>(o);
+        return zc ? reinterpret_cast<T*>(c->h_mstage.get() + o) : d<T>(o);
     }
     void put(size_t o, const void* src, size_t bytes) const {   // an input region's content (nothing: src may be NULL)
         if (bytes) std::memcpy(hi<uint8_t>(o), src, bytes);
     }
     hipError_t up(size_t from, size_t to) const {
         if (zc) return hipSuccess;   // the kernels read the pinned mirror itself
-        return to > from ? hipMemcpyAsync(c->d_scratch + from, c->h_mstage + from, to - from, hipMemcpyHostToDevice,
-                                          c->stream)
+        return to > from ? hipMemcpyAsync(d<uint8_t>(from), h<uint8_t>(from), to - from, hipMemcpyHostToDevice, c->stream)
                          : hipSuccess;
     }
     hipError_t down(size_t from, size_t to) const {
-        return to > from ? hipMemcpyAsync(c->h_mstage + from, c->d_scratch + from, to - from, hipMemcpyDeviceToHost,
-                                          c->stream)
+        return to > from ? hipMemcpyAsync(h<uint8_t>(from), d<uint8_t>(from), to - from, hipMemcpyDeviceToHost, c->stream)
                          : hipSuccess;
     }
 };
@@ -297,7 +277,7 @@ struct orb_frame {
     int n = 0;
     bool has_ur = false;
     float min_x = 0, min_y = 0, inv_w = 0, inv_h = 0;
-    uint8_t* d_base = nullptr;
+    orbgpu::DevBuf<uint8_t> d_base;
     const uint8_t* d_desc = nullptr;
     const orb_keypoint* d_kps = nullptr;
     const float* d_ur = nullptr;   // NULL: created without uright

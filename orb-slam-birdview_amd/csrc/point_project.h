@@ -105,7 +105,7 @@ __host__ __device__ inline orb_point_proj project_point(int mode, const PointCam
 struct orb_points {
     int device = 0;
     int cap = 0;
-    uint8_t* d_base = nullptr;
+    orbgpu::DevBuf<uint8_t> d_base;
     const orbgpu::PointGeo* d_geo = nullptr;
     const uint8_t* d_desc = nullptr;
 };

@@ -134,11 +134,12 @@ namespace {
 size_t points_desc_off(size_t cap) { return Arena::align(cap * sizeof(PointGeo)); }
 size_t points_bytes(size_t cap) { return points_desc_off(cap) + cap * 32; }
 
-void points_bind(orb_points* P, uint8_t* base, int cap) {
-    P->d_base = base;
+// P adopts base (allocated for cap slots, or for one where cap is 0); base leaves with P's previous allocation
+void points_bind(orb_points* P, DevBuf<uint8_t>& base, int cap) {
+    P->d_base.swap(base);
     P->cap = cap;
-    P->d_geo = reinterpret_cast<const PointGeo*>(base);
-    P->d_desc = base + points_desc_off((size_t)cap);
+    P->d_geo = reinterpret_cast<const PointGeo*>(P->d_base.get());
+    P->d_desc = P->d_base.get() + points_desc_off((size_t)cap);
 }
 
 }  // namespace
@@ -157,8 +158,8 @@ int orb_points_create(orb_ctx* h, int capacity, orb_points** out) {
     orb_points* P = new (std::nothrow) orb_points();
     if (!P) return set_error("orb_points", hipSuccess), ORB_ERR_NOMEM;
     P->device = c->device;
-    uint8_t* base = nullptr;
-    const hipError_t e = hipMalloc((void**)&base, points_bytes((size_t)std::max(capacity, 1)));
+    DevBuf<uint8_t> base;
+    const hipError_t e = base.ensure(points_bytes((size_t)std::max(capacity, 1)));
     if (e != hipSuccess) {
         delete P;
         return set_error("orb_points allocation", e), ORB_ERR_NOMEM;
@@ -189,17 +190,15 @@ int orb_points_write(orb_points* P, int first, int n, const float* pos, const fl
         // at least doubled; hipFree waits for the device, so queued work that reads the old allocation ends first
         const long long want = std::max<long long>(need, 2LL * P->cap);
         const int cap = (int)std::min<long long>(want, INT_MAX);
-        uint8_t* base = nullptr;
-        if ((e = hipMalloc((void**)&base, points_bytes((size_t)cap))) != hipSuccess)
+        DevBuf<uint8_t> base;
+        if ((e = base.ensure(points_bytes((size_t)cap))) != hipSuccess)
             return set_error("orb_points growth", e), ORB_ERR_NOMEM;
         if (P->cap > 0 &&
-            ((e = hipMemcpy(base, P->d_geo, (size_t)P->cap * sizeof(PointGeo), hipMemcpyDeviceToDevice)) != hipSuccess ||
-             (e = hipMemcpy(base + points_desc_off((size_t)cap), P->d_desc, (size_t)P->cap * 32,
-                            hipMemcpyDeviceToDevice)) != hipSuccess)) {
-            (void)hipFree(base);
+            ((e = hipMemcpy(base.get(), P->d_geo, (size_t)P->cap * sizeof(PointGeo), hipMemcpyDeviceToDevice)) !=
+                 hipSuccess ||
+             (e = hipMemcpy(base.get() + points_desc_off((size_t)cap), P->d_desc, (size_t)P->cap * 32,
+                            hipMemcpyDeviceToDevice)) != hipSuccess))
             return set_error("orb_points growth copy", e), ORB_ERR_HIP;
-        }
-        (void)hipFree(P->d_base);
         points_bind(P, base, cap);
     }
     std::vector<PointGeo> geo;
@@ -212,9 +211,9 @@ int orb_points_write(orb_points* P, int first, int n, const float* pos, const fl
         geo[i] = PointGeo{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], normal[3 * i], normal[3 * i + 1],
                           normal[3 * i + 2], min_dist[i], max_dist[i]};
     // plain hipMemcpy from pageable memory: both have completed on the device when they return
-    if ((e = hipMemcpy(P->d_base + (size_t)first * sizeof(PointGeo), geo.data(), (size_t)n * sizeof(PointGeo),
+    if ((e = hipMemcpy(P->d_base.get() + (size_t)first * sizeof(PointGeo), geo.data(), (size_t)n * sizeof(PointGeo),
                        hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(P->d_base + points_desc_off((size_t)P->cap) + (size_t)first * 32, desc, (size_t)n * 32,
+        (e = hipMemcpy(P->d_base.get() + points_desc_off((size_t)P->cap) + (size_t)first * 32, desc, (size_t)n * 32,
                        hipMemcpyHostToDevice)) != hipSuccess)
         return set_error("orb_points_write", e), ORB_ERR_HIP;
     if ((e = hipDeviceSynchronize()) != hipSuccess) return set_error("orb_points_write synchronise", e), ORB_ERR_HIP;
@@ -225,7 +224,9 @@ int orb_points_capacity(const orb_points* P) { return P ? P->cap : 0; }
 
 void orb_points_destroy(orb_points* P) {
     if (!P) return;
-    if (P->d_base && hipSetDevice(P->device) == hipSuccess) (void)hipFree(P->d_base);
+    // the allocation is freed even where the device cannot be made current: hipFree takes a pointer, not the
+    // current device
+    (void)hipSetDevice(P->device);
     delete P;
 }
 

@@ -398,8 +398,9 @@ int orb_compute_stereo_matches(orb_ctx* left, orb_ctx* right, int nL, const orb_
     float* h_d = st.h<float>(o_d);
     int* h_nm = st.h<int>(o_nm);
     int* d_s = st.d<int>(o_s);
-    StereoSide SL{cl->last_frames, cl->last_frame_pitch, cl->last_row_stride, cl->d_pyr, 0, 0, d_kL, d_dL, d_cnt, 0};
-    StereoSide SR{cr->last_frames, cr->last_frame_pitch, cr->last_row_stride, cr->d_pyr, 0, 0, d_kR, d_dR, d_cnt + 1, 0};
+    StereoSide SL{cl->last_frames, cl->last_frame_pitch, cl->last_row_stride, cl->d_pyr.get(), 0, 0, d_kL, d_dL, d_cnt, 0};
+    StereoSide SR{cr->last_frames, cr->last_frame_pitch, cr->last_row_stride, cr->d_pyr.get(), 0, 0, d_kR, d_dR, d_cnt + 1,
+                  0};
     // Left and right extractors on different GPUs (one GPU per camera stream, BASELINE C4): the window
     // search reads the right image and pyramid, so they move to the left device over xGMI first
     // (hipMemcpyPeerAsync: the right frame's level 0 and its pyramid slot, ~2.9 MB at 1280x720).
@@ -407,13 +408,7 @@ int orb_compute_stereo_matches(orb_ctx* left, orb_ctx* right, int nL, const orb_
     if (cl->device != cr->device || cl->stereo_stage) {
         const size_t f0 = (size_t)cr->last_frame_pitch, pb = (size_t)cr->geom.pyr_bytes;
         const size_t sneed = ((f0 + 255) & ~(size_t)255) + pb;
-        if (sneed > cl->peer_cap || !cl->d_peer) {
-            if (cl->d_peer) (void)hipFree(cl->d_peer);
-            cl->d_peer = nullptr;
-            cl->peer_cap = 0;
-            if ((e = hipMalloc((void**)&cl->d_peer, sneed)) != hipSuccess) return set_error("stereo peer staging", e), ORB_ERR_NOMEM;
-            cl->peer_cap = sneed;
-        }
+        if ((e = cl->d_peer.ensure(sneed)) != hipSuccess) return set_error("stereo peer staging", e), ORB_ERR_NOMEM;
         if (cl->device != cr->device) {
             int can = 0;
             if (hipDeviceCanAccessPeer(&can, cl->device, cr->device) == hipSuccess && can) {
@@ -422,16 +417,16 @@ int orb_compute_stereo_matches(orb_ctx* left, orb_ctx* right, int nL, const orb_
                 (void)hipGetLastError();
             }
         }
-        uint8_t* sf = cl->d_peer;
-        uint8_t* sp = cl->d_peer + ((f0 + 255) & ~(size_t)255);
+        uint8_t* sf = cl->d_peer.get();
+        uint8_t* sp = sf + ((f0 + 255) & ~(size_t)255);
         if ((e = hipMemcpyPeerAsync(sf, cl->device, cr->last_frames, cr->device, f0, cl->stream)) != hipSuccess ||
-            (pb && (e = hipMemcpyPeerAsync(sp, cl->device, cr->d_pyr, cr->device, pb, cl->stream)) != hipSuccess))
+            (pb && (e = hipMemcpyPeerAsync(sp, cl->device, cr->d_pyr.get(), cr->device, pb, cl->stream)) != hipSuccess))
             return set_error("stereo peer copy", e), ORB_ERR_HIP;
         SR.frames = sf;
         SR.pyr = sp;
     }
     if (cl->prof_on) Ctx::marker(cl, ORB_K_STEREO, 1, cl->stream);
-    e = launch_stereo(cl->d_geom, cl->geom, SL, SR, 1, mb, mbf, h_u, h_d, d_s, scap, h_nm, cl->stream);
+    e = launch_stereo(cl->d_geom.get(), cl->geom, SL, SR, 1, mb, mbf, h_u, h_d, d_s, scap, h_nm, cl->stream);
     if (cl->prof_on) Ctx::marker(cl, ORB_K_STEREO, 0, cl->stream);
     if (e != hipSuccess) return set_error("stereo kernels", e), ORB_ERR_HIP;
     if ((e = hipStreamSynchronize(cl->stream)) != hipSuccess) return set_error("stereo sync", e), ORB_ERR_HIP;
@@ -455,20 +450,14 @@ int orb_stereo_batch_device(orb_ctx* h, int npairs, float mb, float mbf, float* 
         return set_error("orb_stereo_batch_device: kp_cap above 16,777,215", hipSuccess), ORB_ERR_ARG;
     const size_t need = stereo_scratch_ints(c->geom, npairs, cap) * 4 + 256;
     hipError_t e;
-    if (need > c->scratch_cap || !c->d_scratch) {
-        if (c->d_scratch) (void)hipFree(c->d_scratch);
-        c->d_scratch = nullptr;
-        c->scratch_cap = 0;
-        if ((e = hipMalloc((void**)&c->d_scratch, need)) != hipSuccess) return set_error("stereo scratch", e), ORB_ERR_NOMEM;
-        c->scratch_cap = need;
-    }
-    StereoSide SL{c->last_frames, c->last_frame_pitch, c->last_row_stride, c->d_pyr, 0, 2, c->last_kps, c->last_desc,
+    if ((e = Arena{c}.reserve(need)) != hipSuccess) return set_error("stereo scratch", e), ORB_ERR_NOMEM;
+    StereoSide SL{c->last_frames, c->last_frame_pitch, c->last_row_stride, c->d_pyr.get(), 0, 2, c->last_kps, c->last_desc,
                   c->last_counts, cap};
     StereoSide SR = SL;
     SR.frame0 = 1;
     if (c->prof_on) Ctx::marker(c, ORB_K_STEREO, 1, c->stream);
-    e = launch_stereo(c->d_geom, c->geom, SL, SR, npairs, mb, mbf, d_uright, d_depth, (int*)c->d_scratch, cap,
-                      d_nmatched, c->stream);
+    e = launch_stereo(c->d_geom.get(), c->geom, SL, SR, npairs, mb, mbf, d_uright, d_depth, (int*)c->d_scratch.get(),
+                      cap, d_nmatched, c->stream);
     if (c->prof_on) Ctx::marker(c, ORB_K_STEREO, 0, c->stream);
     if (e != hipSuccess) return set_error("stereo kernels", e), ORB_ERR_HIP;
     return ORB_OK;

@@ -238,15 +238,14 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
             const size_t o_kps = Arena::align(nn * 32), o_ur = Arena::align(o_kps + nn * sizeof(orb_keypoint)),
                          o_coff = Arena::align(o_ur + nn * 4),
                          o_cidx = Arena::align(o_coff + (size_t)(kFrameGridCells + 1) * 4);
-            if ((e = hipMalloc((void**)&H->d_base, Arena::align(o_cidx + nn * 4))) != hipSuccess) {
-                H->d_base = nullptr;
+            if ((e = H->d_base.ensure(Arena::align(o_cidx + nn * 4))) != hipSuccess)
                 return fail("orb_frame allocation", ORB_ERR_NOMEM);
-            }
-            H->d_desc = H->d_base;
-            H->d_kps = reinterpret_cast<const orb_keypoint*>(H->d_base + o_kps);
-            H->d_ur = H->has_ur ? reinterpret_cast<const float*>(H->d_base + o_ur) : nullptr;
-            H->d_coff = reinterpret_cast<const int*>(H->d_base + o_coff);
-            H->d_cidx = reinterpret_cast<const int*>(H->d_base + o_cidx);
+            uint8_t* const base = H->d_base.get();
+            H->d_desc = base;
+            H->d_kps = reinterpret_cast<const orb_keypoint*>(base + o_kps);
+            H->d_ur = H->has_ur ? reinterpret_cast<const float*>(base + o_ur) : nullptr;
+            H->d_coff = reinterpret_cast<const int*>(base + o_coff);
+            H->d_cidx = reinterpret_cast<const int*>(base + o_cidx);
             try {
                 H->kps.resize(nn);
             } catch (const std::bad_alloc&) {
@@ -292,7 +291,7 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
         const size_t nn = (size_t)H->n;
         int* d_work = a.take<int>(2 * nn);
         if (nn > 0 &&
-            ((e = hipMemcpyAsync(H->d_base, d_desc + (size_t)f * kp_cap * 32, nn * 32, hipMemcpyDeviceToDevice,
+            ((e = hipMemcpyAsync(H->d_base.get(), d_desc + (size_t)f * kp_cap * 32, nn * 32, hipMemcpyDeviceToDevice,
                                  c->stream)) != hipSuccess ||
              (e = hipMemcpyAsync(const_cast<orb_keypoint*>(H->d_kps), d_un + (size_t)f * kp_cap,
                                  nn * sizeof(orb_keypoint), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess ||

@@ -22,12 +22,12 @@
 struct orb_vocab {
     int device;
     int k, L, scoring, weighting, nnodes, nwords;
-    int* d_cbeg = nullptr;        // per node: first child slot
-    int* d_ccnt = nullptr;        // per node: #children (0 = leaf)
-    int* d_child = nullptr;       // per child slot: node id
-    uint8_t* d_cdesc = nullptr;   // per child slot: 32-byte descriptor
-    int* d_word = nullptr;        // per node: word id (-1 for internal nodes)
-    float* d_weight = nullptr;    // per node: weight (stored as float in the file)
+    orbgpu::DevBuf<int> d_cbeg;        // per node: first child slot
+    orbgpu::DevBuf<int> d_ccnt;        // per node: #children (0 = leaf)
+    orbgpu::DevBuf<int> d_child;       // per child slot: node id
+    orbgpu::DevBuf<uint8_t> d_cdesc;   // per child slot: 32-byte descriptor
+    orbgpu::DevBuf<int> d_word;        // per node: word id (-1 for internal nodes)
+    orbgpu::DevBuf<float> d_weight;    // per node: weight (stored as float in the file)
 };
 
 namespace orbgpu {
@@ -81,9 +81,6 @@ using namespace orbgpu;
 static void vocab_free(orb_vocab* v) {
     if (!v) return;
     (void)hipSetDevice(v->device);
-    void* bufs[] = {v->d_cbeg, v->d_ccnt, v->d_child, v->d_cdesc, v->d_word, v->d_weight};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
     delete v;
 }
 
@@ -157,20 +154,18 @@ int orb_vocab_load(orb_ctx* h, const char* path, orb_vocab** out) {
     v->nnodes = nn;
     v->nwords = nwords;
     hipError_t e;
-    if ((e = hipMalloc((void**)&v->d_cbeg, nn * 4)) != hipSuccess || (e = hipMalloc((void**)&v->d_ccnt, nn * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&v->d_child, child.size() * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&v->d_cdesc, cdesc.size())) != hipSuccess ||
-        (e = hipMalloc((void**)&v->d_word, nn * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&v->d_weight, nn * 4)) != hipSuccess) {
+    if ((e = v->d_cbeg.ensure(nn)) != hipSuccess || (e = v->d_ccnt.ensure(nn)) != hipSuccess ||
+        (e = v->d_child.ensure(child.size())) != hipSuccess || (e = v->d_cdesc.ensure(cdesc.size())) != hipSuccess ||
+        (e = v->d_word.ensure(nn)) != hipSuccess || (e = v->d_weight.ensure(nn)) != hipSuccess) {
         vocab_free(v);
         return set_error("orb_vocab_load: device allocation", e), ORB_ERR_NOMEM;
     }
-    if ((e = hipMemcpy(v->d_cbeg, cbeg.data(), nn * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(v->d_ccnt, ccnt.data(), nn * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(v->d_child, child.data(), child.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(v->d_cdesc, cdesc.data(), cdesc.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(v->d_word, word.data(), nn * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(v->d_weight, weight.data(), nn * 4, hipMemcpyHostToDevice)) != hipSuccess) {
+    if ((e = hipMemcpy(v->d_cbeg.get(), cbeg.data(), nn * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(v->d_ccnt.get(), ccnt.data(), nn * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(v->d_child.get(), child.data(), child.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(v->d_cdesc.get(), cdesc.data(), cdesc.size(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(v->d_word.get(), word.data(), nn * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(v->d_weight.get(), weight.data(), nn * 4, hipMemcpyHostToDevice)) != hipSuccess) {
         vocab_free(v);
         return set_error("orb_vocab_load: upload", e), ORB_ERR_HIP;
     }
@@ -209,9 +204,10 @@ int orb_vocab_transform(orb_ctx* h, const orb_vocab* v, const uint8_t* desc, int
     std::memcpy(st.hi<uint8_t>(o_desc), desc, (size_t)n * 32);
     hipError_t e = st.up(o_desc, o_w);
     if (e != hipSuccess) return set_error("vocab upload", e), ORB_ERR_HIP;
-    hipLaunchKernelGGL(k_vocab_transform, dim3((n + 255) / 256, 1), dim3(256), 0, c->stream, v->d_cbeg, v->d_ccnt,
-                       v->d_child, v->d_cdesc, v->d_word, v->d_weight, st.di<uint8_t>(o_desc), nullptr, n, 0,
-                       v->L - levelsup, st.h<int>(o_w), st.h<float>(o_wt), st.h<uint32_t>(o_nd));
+    hipLaunchKernelGGL(k_vocab_transform, dim3((n + 255) / 256, 1), dim3(256), 0, c->stream, v->d_cbeg.get(),
+                       v->d_ccnt.get(), v->d_child.get(), v->d_cdesc.get(), v->d_word.get(), v->d_weight.get(),
+                       st.di<uint8_t>(o_desc), nullptr, n, 0, v->L - levelsup, st.h<int>(o_w), st.h<float>(o_wt),
+                       st.h<uint32_t>(o_nd));
     if ((e = hipGetLastError()) != hipSuccess) return set_error("vocab kernel", e), ORB_ERR_HIP;
     // the kernel writes [word | weight | node] straight into the pinned mirror: no D2H command
     (void)o_end;
@@ -232,9 +228,10 @@ int orb_vocab_transform_batch_device(orb_ctx* h, const orb_vocab* v, int nframes
         return set_error("orb_vocab_transform_batch_device: no such frames in the last batch", hipSuccess),
                ORB_ERR_ARG;
     const int cap = c->last_kp_cap;
-    hipLaunchKernelGGL(k_vocab_transform, dim3((cap + 255) / 256, nframes), dim3(256), 0, c->stream, v->d_cbeg,
-                       v->d_ccnt, v->d_child, v->d_cdesc, v->d_word, v->d_weight, c->last_desc, c->last_counts, 0,
-                       (long long)cap, v->L - levelsup, d_word, d_weight, d_node);
+    hipLaunchKernelGGL(k_vocab_transform, dim3((cap + 255) / 256, nframes), dim3(256), 0, c->stream,
+                       v->d_cbeg.get(), v->d_ccnt.get(), v->d_child.get(), v->d_cdesc.get(), v->d_word.get(),
+                       v->d_weight.get(), c->last_desc, c->last_counts, 0, (long long)cap, v->L - levelsup, d_word,
+                       d_weight, d_node);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("vocab kernel", e), ORB_ERR_HIP);
 }

@@ -74,8 +74,8 @@ def test_host_path_pitch_is_dword_aligned():
     body = src[src.index("int orb_extract("):]
     body = body[:body.index("\n}\n")]
     assert re.search(r"const size_t pitch = \(\(size_t\)w \+ 63\) & ~\(size_t\)63;", body)
-    assert re.search(r"run_extract\(c->d_in, 1, \(long long\)pitch \* hgt, \(int\)pitch,", body)
-    assert "hipMemcpy2DAsync(c->d_in, pitch, img, stride, w, hgt" in body
+    assert re.search(r"run_extract\(c->d_in\.get\(\), 1, \(long long\)pitch \* hgt, \(int\)pitch,", body)
+    assert "hipMemcpy2DAsync(c->d_in.get(), pitch, img, stride, w, hgt" in body
 
 
 @pytest.mark.gpu
