@@ -739,9 +739,10 @@ void build_cells(const Geom& g, std::vector<CellDesc>& cells) {
                 d.xoyo = (3 + cj * L.wCell) | ((3 + ci * L.hCell) << 16);
                 d.pitch = L.pitch;
                 d.pyr_off = (int)L.pyr_off;
-                const int x0w = iniX >> 2, nw = std::max(1, ((iniX + rw + 3) >> 2) - x0w);
+                // ROI row as groups of four pixels from column -1 on (fast_roi_issue's format loads)
+                const int nw = std::max(1, (rw + 1 + 3) >> 2);
                 const int nruns = std::max(1, (rw - 6 + 15) / 16);   // 16-pixel prefilter runs
-                d.roi = nw | ((64 / nw) << 8) | (x0w << 16);
+                d.roi = nw | ((64 / nw) << 8);
                 d.m_nw = (int)recip20((uint32_t)nw);
                 d.runs = nruns | ((64 / nruns) << 8);
                 d.m_runs = (int)recip20((uint32_t)nruns);
@@ -760,7 +761,7 @@ __device__ __forceinline__ unsigned roi_off(int yy, int stride, int cb) {
 }
 
 struct FastCellT {
-    int f, cell, iniX, rw, rh, dw, dh, x0w, nw, rpr, m_nw, nruns, rpi, m_runs, ntail, np, m_np, out_off, xo, yo;
+    int f, cell, iniX, rw, rh, dw, dh, nw, rpr, m_nw, nruns, rpi, m_runs, ntail, np, m_np, out_off, xo, yo;
     bool valid, aligned;
     const uint8_t* base;   // ROI row 0, column 0
     int stride;
@@ -789,7 +790,6 @@ __device__ __forceinline__ FastCellT fast_cell_t(const Geom* __restrict__ g, con
     c.aligned = ((reinterpret_cast<uintptr_t>(lp) | (uintptr_t)c.stride) & 3) == 0;
     c.nw = d.roi & 0xFF;
     c.rpr = (d.roi >> 8) & 0xFF;
-    c.x0w = d.roi >> 16;
     c.m_nw = d.m_nw;
     c.nruns = d.runs & 0xFF;
     c.rpi = (d.runs >> 8) & 0xFF;
@@ -872,12 +872,40 @@ __device__ __forceinline__ uint32_t compass2(uint32_t v, uint32_t p0, uint32_t p
 #define ORBGPU_STAMP(k)
 #endif
 
-// ROI dwords of a cell (aligned levels) issued into registers, so that the next cell's loads are in
-// flight while the current one is processed.  lane = (row yy0 = lane / nw, dword ww = lane % nw);
+// ROI pixels of a cell (aligned levels) issued into registers, so that the next cell's loads are in
+// flight while the current one is processed.  Each load is a D16 format load of four bytes through a
+// descriptor with data format 8_8_8_8 / UINT: the memory pipeline widens them to the tile's 16-bit pixel
+// pairs (b0 | b1 << 16, b2 | b3 << 16), at any byte offset and at the cache policy CP
+// (tools/format_load_probe.hip, profiles/r12/format_load_probe.txt).  The descriptor starts one byte before
+// the ROI's column 0, so that a lane's four bytes are two whole dwords of the tile (see fast_roi_store).
+// lane = (row yy0 = lane / nw, group ww = lane % nw) with nw = ceil((rw + 1) / 4) groups of four bytes per row;
 // round k takes row yy0 + k * rpr (rpr = 64 / nw rows per round): the lane's offset is computed once
-// and each round adds a wave-uniform row step to the voffset of a buffer load whose descriptor (SGPRs)
-// starts at the ROI's first dword.  Rows past the ROI and lanes past rpr rows are out of the
-// descriptor's range (read 0).  Rows from 8 * rpr on (tall cells) are loaded by fast_roi_store.
+// and each round adds a wave-uniform row step to the voffset.  Rows past the ROI and lanes past rpr rows are
+// out of the descriptor's range (read 0: the range check takes the whole element).  Rows from 8 * rpr on (tall
+// cells) are loaded by fast_roi_store.
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+// buffer_load_format_d16_xyzw (no clang builtin selects it; the compiler tracks its vmcnt as for any load)
+// (fragile by nature: the asm label is the intrinsic's mangled name, which a compiler release may change, and `aux` is
+// an immediate operand that becomes one only once the callers are inlined, so an -O0 build does not compile this)
+__device__ half4_t raw_buffer_load_format_d16x4(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int aux)
+    __asm("llvm.amdgcn.raw.ptr.buffer.load.format.v4f16");
+// descriptor word 3: DST_SEL x, y, z, w (bits 0..11), NUM_FORMAT UINT = 4 (12..14), DATA_FORMAT 8_8_8_8 = 10 (15..18)
+constexpr int kRsrcU8x4 = 0xFAC | (4 << 12) | (10 << 15);
+
+// a constant held in an SGPR (a VOP3 takes no literal on gfx9: left to itself the compiler re-materialises one
+// per use with a v_mov)
+__device__ __forceinline__ uint32_t sgpr_const(uint32_t x) {
+    uint32_t r;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "i"(x));
+    return r;
+}
+
+template <int CP>
+__device__ __forceinline__ u32x2_t load_u8x4_as_u16(__amdgpu_buffer_rsrc_t rsrc, int voffset) {
+    return __builtin_bit_cast(u32x2_t, raw_buffer_load_format_d16x4(rsrc, voffset, 0, CP));
+}
+
 struct RoiLanes {
     int yy0, ww, rpr, off;
     __amdgpu_buffer_rsrc_t rsrc;
@@ -890,103 +918,50 @@ __device__ __forceinline__ RoiLanes roi_lanes(const FastCellT& c, int lane) {
     r.yy0 = (int)div20(lane, c.m_nw);
     r.ww = lane - (int)__umul24((unsigned)r.yy0, (unsigned)nw);
     r.off = (int)roi_off(r.yy0, stride, 4 * r.ww);
-    // the cell is wave-uniform (readfirstlane returns int: zero-extend both halves)
-    const uint64_t pb = reinterpret_cast<uint64_t>(c.base + 4 * c.x0w);
+    // the cell is wave-uniform (readfirstlane returns int: zero-extend both halves); iniX >= kMinBorder, so the
+    // byte before column 0 is a pixel of the same row
+    const uint64_t pb = reinterpret_cast<uint64_t>(c.base + c.iniX - 1);
     const uint64_t pu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(pb >> 32)) << 32) |
                         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)pb);
-    r.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(pu), 0, (c.rh - 1) * stride + 4 * nw, 0x00020000);
+    r.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(pu), 0, (c.rh - 1) * stride + 4 * nw, kRsrcU8x4);
     return r;
-}
-
-__device__ __forceinline__ bool roi_row_ok(const FastCellT& c, const RoiLanes& r, int k) {
-    return r.yy0 < r.rpr && r.yy0 + k * r.rpr < c.rh;
 }
 
 template <int CP = 0>
-__device__ __forceinline__ void fast_roi_issue(const FastCellT& c, int lane, uint32_t (&v)[8]) {
+__device__ __forceinline__ void fast_roi_issue(const FastCellT& c, int lane, u32x2_t (&v)[8]) {
     const RoiLanes r = roi_lanes(c, lane);
-    // rows past the ROI lie past the descriptor's num_records ((rh - 1) * stride + 4 nw <= rh * stride
-    // + 4 ww) and read 0 without a per-row test: the row step goes into voffset, which the range check
+    // rows past the ROI lie past the descriptor's num_records ((rh - 1) * stride + 4 nw < rh * stride
+    // + 4 ww + 4) and read 0 without a per-row test: the row step goes into voffset, which the range check
     // covers (soffset would not be checked); lanes past rpr rows start out of range
     const int off = r.yy0 < r.rpr ? r.off : 0x40000000;
 #pragma unroll
-    for (int k = 0; k < 8; k++)
-        v[k] = __builtin_amdgcn_raw_buffer_load_b32(r.rsrc, off + k * r.rpr * c.stride, 0, CP);
+    for (int k = 0; k < 8; k++) v[k] = load_u8x4_as_u16<CP>(r.rsrc, off + k * r.rpr * c.stride);
 }
 
 // ROI -> 16-bit LDS tile (rows TQ elements apart): ROI column c at element c + 1, so that every
-// prefilter window starts on a 16-byte boundary (see prefilter16).  The bytes are widened as they are
-// stored.  ROI column c is byte c + B of the loaded row (B = the ROI's byte offset in its first dword),
-// so a lane's dword (bytes 4 ww .. 4 ww + 3) goes to elements 4 ww - B + 1 .. 4 ww - B + 4, i.e. the
-// pixel pairs at dwords 2 ww - (B >> 1) and + 1 are (b0, b1), (b2, b3) for B odd and (prev b3, b0),
-// (b1, b2) for B even — prev = the row's previous dword, lane - 1's (DPP wave_shr), and the row's last
-// dword also stores (b3, 0).  Dword -1 of row 0 lies in the carve's 16-byte lead pad, that of a later row
-// in the previous row's unused tail (TQ >= rw + 6).  Rows of a tall ROI past the prefetched ones are
-// loaded here; a level whose base / stride is not dword aligned is stored per byte.
-__device__ __forceinline__ uint32_t dpp_prev_lane(uint32_t v) {   // lane - 1's value (lane 0: 0)
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);
-}
-
-// v_perm selectors as SGPRs (a VOP3 takes no literal on gfx9: left to itself the compiler re-materialises
-// one per store with a v_mov)
-struct WidenSel {
-    uint32_t lo, hi;
-};
-__device__ __forceinline__ uint32_t sgpr_const(uint32_t x) {
-    uint32_t r;
-    asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "i"(x));
-    return r;
-}
-
-template <bool ODD>
-__device__ __forceinline__ void widen_store(uint32_t* q, uint32_t v, uint32_t pv, bool last, const WidenSel& S) {
-    if (ODD) {   // (b0, b1), (b2, b3)
-        q[0] = __builtin_amdgcn_perm(0u, v, S.lo);
-        q[1] = __builtin_amdgcn_perm(0u, v, S.hi);
-    } else {     // (prev b3, b0), (b1, b2) [, (b3, 0)]
-        q[0] = __builtin_amdgcn_perm(v, pv, S.lo);
-        q[1] = __builtin_amdgcn_perm(0u, v, S.hi);
-        if (last) q[2] = v >> 24;
-    }
-}
-
-// the prefetched rows (round k: ROI row yy0 + k * rpr) and, for a tall ROI, the rows past them
-template <int TQ, bool ODD, int CP>
-__device__ __forceinline__ void widen_rows(const FastCellT& c, const RoiLanes& r, const uint32_t (&v)[8], uint32_t* t32,
-                                           int B, bool last) {
-    const WidenSel S = ODD ? WidenSel{sgpr_const(0x0c010c00u), sgpr_const(0x0c030c02u)}
-                           : WidenSel{sgpr_const(0x0c040c03u), sgpr_const(0x0c020c01u)};
-    uint32_t* t = t32 + (r.yy0 * (TQ / 2) + 2 * r.ww - (B >> 1));
-    const bool on = r.yy0 < r.rpr;
-    const int rpr = __builtin_amdgcn_readfirstlane(r.rpr), rh = __builtin_amdgcn_readfirstlane(c.rh);
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const int k0 = k * rpr;
-        if (k0 >= rh) break;   // wave-uniform
-        const uint32_t pv = ODD ? 0u : dpp_prev_lane(v[k]);
-        if (on && r.yy0 + k0 < rh) widen_store<ODD>(t + k0 * (TQ / 2), v[k], pv, last, S);
-    }
-    if (on)
-        for (int yy = r.yy0 + 8 * rpr; yy < rh; yy += rpr) {   // lanes of one row iterate together
-            uint32_t w;
-            if constexpr (CP != 0) w = __builtin_amdgcn_raw_buffer_load_b32(r.rsrc, (int)roi_off(yy, c.stride, 4 * r.ww), 0, CP);
-            else w = *reinterpret_cast<const uint32_t*>(c.base + roi_off(yy, c.stride, (c.x0w + r.ww) * 4));
-            const uint32_t pw = ODD ? 0u : dpp_prev_lane(w);
-            widen_store<ODD>(t32 + (yy * (TQ / 2) + 2 * r.ww - (B >> 1)), w, pw, last, S);
-        }
-}
-
+// prefilter window starts on a 16-byte boundary (see prefilter16).  A lane's four pixels, ROI columns
+// 4 ww - 1 .. 4 ww + 2, arrive widened and go to elements 4 ww .. 4 ww + 3 as one 8-byte store.  Element 0 (the
+// pixel left of the ROI) and the elements from rw + 1 to 4 nw - 1 (pixels right of it, nw <= (rw + 4) / 4 <
+// TQ / 4) are not read for any decision.  Rows of a tall ROI past the prefetched ones are loaded here; a level
+// whose base / stride is not dword aligned is stored per byte.
 // (CP: the unaligned byte path below reads only the caller's frame, level 0, never handed-off pyramid bytes: the
 // pyramid levels are 64-byte aligned rows in a 256-byte aligned slot)
 template <int TQ, int CP = 0>
-__device__ __forceinline__ void fast_roi_store(const FastCellT& c, int lane, const uint32_t (&v)[8], uint16_t* tile) {
-    uint32_t* t32 = reinterpret_cast<uint32_t*>(tile);
+__device__ __forceinline__ void fast_roi_store(const FastCellT& c, int lane, const u32x2_t (&v)[8], uint16_t* tile) {
     if (c.aligned) {
         const RoiLanes r = roi_lanes(c, lane);
-        const int B = c.iniX & 3;
-        const bool last = r.ww == __builtin_amdgcn_readfirstlane(c.nw) - 1;
-        if (B & 1) widen_rows<TQ, true, CP>(c, r, v, t32, B, last);
-        else widen_rows<TQ, false, CP>(c, r, v, t32, B, last);
+        u32x2_t* t = reinterpret_cast<u32x2_t*>(tile) + (r.yy0 * (TQ / 4) + r.ww);
+        const bool on = r.yy0 < r.rpr;
+        const int rpr = __builtin_amdgcn_readfirstlane(r.rpr), rh = __builtin_amdgcn_readfirstlane(c.rh);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {   // the prefetched rows (round k: ROI row yy0 + k * rpr)
+            const int k0 = k * rpr;
+            if (k0 >= rh) break;   // wave-uniform
+            if (on && r.yy0 + k0 < rh) t[k0 * (TQ / 4)] = v[k];
+        }
+        if (on)
+            for (int yy = r.yy0 + 8 * rpr; yy < rh; yy += rpr)   // a tall ROI's rows past them
+                t[(yy - r.yy0) * (TQ / 4)] = load_u8x4_as_u16<CP>(r.rsrc, (int)roi_off(yy, c.stride, 4 * r.ww));
         return;
     }
     const uint32_t mrw = recip20(c.rw);
@@ -1002,7 +977,6 @@ __device__ __forceinline__ void fast_roi_store(const FastCellT& c, int lane, con
 // the centre pairs (x0 + 2j, x0 + 2j + 1) at dwords j + 2 and the pairs at columns -3 / +3 (odd
 // elements) as one v_alignbyte each; rows -3 / +3 are two 8-byte reads each.  No byte unpacking.
 typedef const uint32_t __attribute__((address_space(3))) lds_cu32;
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 typedef const u32x2_t __attribute__((address_space(3))) lds_cu32x2;
 typedef const uint32x4_t __attribute__((address_space(3))) lds_cu32x4;
 
@@ -1240,13 +1214,13 @@ __global__ __launch_bounds__(256) void k_fast_wave(const Geom* __restrict__ g, c
     const int item0 = (blk * (int)(blockDim.x >> 6) + wv) * ipw;   // ipw = items per wave, 2 (1 for latency)
     if (item0 >= total) return;   // whole wave; nothing below uses a block barrier
     const int wb = g->fast_wave_bytes;
-    // 16-bit pixel tile, TQ per row, after a 16-byte lead pad (fast_roi_store's dword -1 of row 0)
+    // 16-bit pixel tile, TQ per row, after a 16-byte lead pad
     uint16_t* tile = reinterpret_cast<uint16_t*>(smem + (size_t)wv * wb + 16);
     uint16_t* sList = reinterpret_cast<uint16_t*>(smem + (size_t)wv * wb + ((g->fast_rows * TQ * 2 + 32 + 15) & ~15));
     const bool has1 = ipw == 2 && item0 + 1 < total;
     const FastCellT c0 = fast_cell_t(g, cells, item0, frames, framePitch, rowStride, pyr, cbeg, cnum);
     const FastCellT c1 = fast_cell_t(g, cells, has1 ? item0 + 1 : item0, frames, framePitch, rowStride, pyr, cbeg, cnum);
-    uint32_t v0[8], v1[8];
+    u32x2_t v0[8], v1[8];
     if (c0.valid && c0.aligned) fast_roi_issue(c0, lane, v0);
     if (has1 && c1.valid && c1.aligned) fast_roi_issue(c1, lane, v1);
     if (err && blockIdx.x == 0 && threadIdx.x == 0) {   // k_octree's overflow flag (set after this kernel)
@@ -1280,7 +1254,7 @@ __global__ __launch_bounds__(256) void k_fast_wave(const Geom* __restrict__ g, c
 // compact tile pitch of 48 elements, any other 80.  Of the BASELINE configs, 1280 x 720 (C3-C5) is compact (cells
 // of 31-33 px); 640 x 480 at 8 levels (C1, C2) is not: its level 7 (179 x 134) has 147 px over 4 columns, cells
 // 37 px wide, so every level of it runs at pitch 80 (tests/test_fast_stage_cases.py pins both).  A tile row holds the
-// widened ROI (rw + 2 elements) and an unused tail for the next row's dword -1, a multiple of 8 elements
+// widened ROI (element 0 and rw + 1: the pixels beside it) and an unused tail, a multiple of 8 elements
 // (16-byte reads), with row strides of 24 / 40 dwords (2-way LDS bank conflicts at most for the
 // prefilter's 16- and 8-byte reads).
 // Prefilter windows of pixels past the domain may read into the next row: those bits are masked.
@@ -2923,7 +2897,7 @@ __device__ __forceinline__ void flow_fast(const FlowArgs* __restrict__ Ap, int l
         if (lane == 0) flow_st(cntOut, 0);
         return;
     }
-    uint32_t v[8];
+    u32x2_t v[8];
     if (c.aligned) fast_roi_issue<kCpSc1>(c, lane, v);
     fast_roi_store<TQ, kCpSc1>(c, lane, v, tile);
     fast_cell_body<TQ, kCpSc1>(g, c, lane, tile, sList, Ap->cands, candFirst, cntOut, nullptr, 0);
