@@ -774,6 +774,89 @@ int orb_compute_stereo_matches(orb_ctx* left, orb_ctx* right, int nL, const orb_
 int orb_stereo_batch_device(orb_ctx* ctx, int npairs, float mb, float mbf, float* d_uright, float* d_depth,
                             int* d_nmatched);
 
+/* ======================= Colour input: cvtColor to gray (Tracking::GrabImage*) ======================= */
+
+/* The first lines of Tracking::GrabImageStereo / RGBD / Monocular / MonocularWithBirdview (Tracking.cc:172-198,
+ * :212-230, :242-257, :276-307): cvtColor(im, mImGray, CV_RGB2GRAY / BGR2GRAY / RGBA2GRAY / BGRA2GRAY), for the left,
+ * right and birdview images alike.  The definition is OpenCV 3.2 RGB2Gray<uchar> on x86-64 without IPP (DESIGN.md
+ * §3.3):  Y = (4899 R + 9617 G + 1868 B + 8192) >> 14;  alpha is ignored.  There is no variant bit for it.
+ * Pixels are interleaved 8-bit, 3 or 4 bytes each in the order the code names; rows are src_stride / dst_stride bytes
+ * apart; any base alignment and any stride (multiples of 4 or not) are accepted.  Only [row, row + w * channels) of
+ * the source is read and only [row, row + w) of the destination written: padding bytes stay untouched.
+ *   orb_to_gray_host    the definition, on the CPU.  No context, no GPU.
+ *   orb_to_gray_device  nframes frames in device memory in one launch (k_to_gray), asynchronous on the context's
+ *                       stream: frame f at d_src + f * src_frame_pitch -> d_dst + f * dst_frame_pitch.  d_dst is what
+ *                       orb_extract_batch_device consumes (same stream: no synchronisation in between).  The birdview
+ *                       object has a STREAM OF ITS OWN: call orb_sync before d_dst goes to orb_bird_extract_device or
+ *                       orb_bird_extract_batch_device.
+ *   orb_extract_color   orb_extract for a host colour image: the colour image is uploaded, converted on the device and
+ *                       goes through orb_extract's single-frame chain unchanged.  orb_get_level(ctx, 0, ...) afterwards
+ *                       returns the gray image (mImGray).  Empty image (w == 0 || h == 0 || img == NULL): ORB_OK, the
+ *                       outputs untouched; capacity as orb_extract.
+ * ORB_ERR_ARG before any GPU work, outputs untouched: an unknown code; NULL arrays with a non-empty image; a negative
+ * size or nframes; a source stride below w * channels or a destination stride below w; a side above 4096; with
+ * nframes > 1 a frame pitch below (h - 1) * stride + the row's bytes.  nframes == 0, w == 0 or h == 0: ORB_OK,
+ * nothing touched. */
+enum { ORB_COLOR_RGB = 0, ORB_COLOR_BGR = 1, ORB_COLOR_RGBA = 2, ORB_COLOR_BGRA = 3 };
+int orb_to_gray_host(int code, const uint8_t* src, int w, int h, size_t src_stride, uint8_t* dst, size_t dst_stride);
+int orb_to_gray_device(orb_ctx* ctx, int code, const uint8_t* d_src, int nframes, int w, int h, size_t src_frame_pitch,
+                       size_t src_row_stride, uint8_t* d_dst, size_t dst_frame_pitch, size_t dst_row_stride);
+int orb_extract_color(orb_ctx* ctx, int code, const uint8_t* img, int w, int h, size_t stride, orb_keypoint* kps,
+                      int cap, int* n, uint8_t* desc);
+
+/* ======================= Frame::ComputeStereoFromRGBD (the RGB-D Frame constructor) ======================= */
+
+/* void Frame::ComputeStereoFromRGBD(const cv::Mat& imDepth)  Frame.cc:839-860, with Tracking::GrabImageRGBD's
+ * imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) (Tracking.cc:229-230) folded in.  For keypoint i:
+ *   col = (int)kp.pt.x, row = (int)kp.pt.y of the RAW keypoint (Mat::at<float>(float, float) truncates toward zero);
+ *   d = (float)depth[row][col] * factor            (convertTo's float work type with beta 0: one rounding);
+ *   d > 0:  mvDepth[i] = d,  mvuRight[i] = kpU.pt.x - mbf / d   (the UNDISTORTED x; the float division first);
+ *   else:   both stay -1.  NaN, 0, -0 and negatives fail d > 0; +inf passes and gives uright = kpU.pt.x.
+ * The converted image is never materialised: only the n gathered values are converted, each bit-equal to the converted
+ * image's value, so a raw 16-bit map goes up at 2 bytes per pixel.  A CV_32F map with factor 1 is the same expression.
+ * THE ONE DECIDED DEVIATION: the reference indexes outside the image by undefined behaviour only.  Here a keypoint
+ * whose raw position is not finite or truncates outside [0, w) x [0, h) gets -1 / -1 in the device forms, and is
+ * ORB_ERR_ARG (outputs untouched) in the host-array form.
+ *   orb_stereo_from_rgbd_host    the definition, on the CPU, map and keypoints in host memory; no context, no GPU.  It
+ *                                is also the right call for ONE frame whose keypoints are already on the host:
+ *                                uploading a depth map to gather a thousand values is not a win.
+ *   orb_stereo_from_rgbd_device  a batch in orb_extract_batch_device's output layout, everything in device memory:
+ *                                frame f's map at map->data + f * map->frame_pitch, its raw / undistorted keypoints at
+ *                                d_kps_raw / d_kps_un + f * kp_cap (they may be the same array), its count in
+ *                                d_counts[f]; outputs at d_uright / d_depth[f * kp_cap + i], d_nvalid[f] = keypoints
+ *                                with a depth (d_nvalid may be NULL).  One launch (k_rgbd_depth), asynchronous on the
+ *                                context's stream.  Slots past a frame's count are not written; a count above kp_cap is
+ *                                read as kp_cap.
+ *   orb_frames_create_from_batch_rgbd  the RGB-D Frame constructor after extraction (Frame.cc:145-200) in one call:
+ *                                orb_frames_create_from_batch's undistort launch with its guard-band redo, then the
+ *                                depth launch on the undistorted keypoints, then the grids; every handle carries its
+ *                                uright (use_uright = 1 works).  d_uright / d_depth (nframes * kp_cap floats each, the
+ *                                layout above) receive mvuRight / mvDepth; either may be NULL.  Failure, synchronisation
+ *                                and argument rules are orb_frames_create_from_batch's.
+ * A map's elements are aligned: data, row_stride and frame_pitch are multiples of the element size (2 or 4), as
+ * cv::Mat's are.  ORB_ERR_ARG before any GPU work, outputs untouched: map NULL; an unknown type; factor or mbf not
+ * finite; w or h negative or above 4096; row_stride below w * element size; with nframes > 1 a frame_pitch below
+ * row_stride * h; a misaligned map; n or nframes negative; NULL arrays (map->data included) with n > 0 / nframes > 0;
+ * and what orb_frames_create_from_batch refuses.  n == 0 / nframes == 0: ORB_OK (*nvalid = 0). */
+enum { ORB_DEPTH_U16 = 0, ORB_DEPTH_F32 = 1 };
+typedef struct orb_depth_map {
+    const void* data;      /* host memory (orb_stereo_from_rgbd_host) or device memory */
+    int type;              /* ORB_DEPTH_U16 | ORB_DEPTH_F32 */
+    int w, h;
+    size_t row_stride;     /* bytes */
+    size_t frame_pitch;    /* bytes between the maps of a batch (one map: not read) */
+    float factor;          /* mDepthMapFactor (Tracking.cc:144-148: already inverted, e.g. 1.0f / 5000.0f) */
+} orb_depth_map;
+int orb_stereo_from_rgbd_host(const orb_depth_map* map, float mbf, int n, const orb_keypoint* kps,
+                              const orb_keypoint* kps_un, float* uright, float* depth, int* nvalid);
+int orb_stereo_from_rgbd_device(orb_ctx* ctx, const orb_depth_map* map, float mbf, int nframes,
+                                const orb_keypoint* d_kps_raw, const orb_keypoint* d_kps_un, const int* d_counts,
+                                int kp_cap, float* d_uright, float* d_depth, int* d_nvalid);
+int orb_frames_create_from_batch_rgbd(orb_ctx* ctx, const orb_distortion* dist, const orb_depth_map* map, float mbf,
+                                      int nframes, const uint8_t* d_desc, const orb_keypoint* d_kps_raw,
+                                      const int* d_counts, int kp_cap, float min_x, float min_y, float inv_w,
+                                      float inv_h, float* d_uright, float* d_depth, orb_frame** out);
+
 /* ======================= DBoW2 vocabulary transform ======================= */
 
 typedef struct orb_vocab orb_vocab;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "orbgpu_ctx.h"
+#include "rgbd.h"
 
 namespace orbgpu {
 
@@ -724,9 +725,24 @@ int orb_extract(orb_ctx* h, const uint8_t* img, int w, int hgt, size_t stride, o
     // mapped + coherent (fine-grained): k_describe stores the outputs straight into this block and the host reads
     // them after hipStreamSynchronize, with no D2H copy in between
     if ((e = c->h_pinned.ensure(need)) != hipSuccess) return set_error("pinned staging", e), ORB_ERR_NOMEM;
+    // orb_extract_color (rgbd.hip) comes through here with its code in the context: img is then a colour image
+    const int color = c->host_color;
+    const bool streamed = c->upload_stream && color < 0;   // (a colour image always takes the plain upload)
     constexpr int kBands = 16;   // (h_flags[kBands .. 63]: [63] = the upload kernel's timeout flag)
     const int band_rows = (hgt + kBands - 1) / kBands, nbands = (hgt + band_rows - 1) / band_rows;
-    if (c->upload_stream) {
+    if (color >= 0) {
+        // the colour image into the scratch arena (rows padded to 64 bytes, so k_to_gray's dword path holds for
+        // every row), converted into d_in on the same stream: the chain below sees a gray frame as from the upload
+        const size_t cbytes = (size_t)w * color_channels(color), cpitch = (cbytes + 63) & ~(size_t)63;
+        Arena a{c};
+        if ((e = a.reserve(cpitch * hgt + 256)) != hipSuccess) return set_error("colour staging", e), ORB_ERR_NOMEM;
+        uint8_t* d_color = a.take<uint8_t>(cpitch * hgt);
+        if ((e = hipMemcpy2DAsync(d_color, cpitch, img, stride, cbytes, hgt, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+            return set_error("upload colour image", e), ORB_ERR_HIP;
+        if ((e = launch_to_gray(color, d_color, 1, w, hgt, cpitch * hgt, cpitch, c->d_in.get(), pitch * hgt, pitch,
+                                c->stream)) != hipSuccess)
+            return set_error("k_to_gray", e), ORB_ERR_HIP;
+    } else if (streamed) {
         if ((e = c->h_img.ensure(pitch * hgt)) != hipSuccess) return set_error("pinned image staging", e), ORB_ERR_NOMEM;
         if (!c->h_flags) {
             if ((e = c->h_flags.ensure(64)) != hipSuccess) return set_error("pinned upload flags", e), ORB_ERR_NOMEM;
@@ -750,7 +766,7 @@ int orb_extract(orb_ctx* h, const uint8_t* img, int w, int hgt, size_t stride, o
     int* hcnt = reinterpret_cast<int*>(hp);
     orb_keypoint* hk = reinterpret_cast<orb_keypoint*>(hp + 16);
     uint8_t* hd = hp + 16 + kbytes;
-    if (c->upload_stream) {
+    if (streamed) {
         // the host half of the streamed upload, band by band, each band's flag raised after its bytes (x86 stores
         // are ordered; the release store keeps the compiler from sinking the copy past it).  Before the extraction
         // launches: the upload kernel pulls each band over PCIe while the host copies the next
@@ -763,7 +779,7 @@ int orb_extract(orb_ctx* h, const uint8_t* img, int w, int hgt, size_t stride, o
     st = c->run_extract(c->d_in.get(), 1, (long long)pitch * hgt, (int)pitch, hk, hd, hcnt, kcap, nullptr, true, hcnt + 1);
     if (st != ORB_OK) return st;
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("extract", e), ORB_ERR_HIP;
-    if (c->upload_stream && __atomic_load_n(c->h_flags.get() + 63, __ATOMIC_ACQUIRE)) {
+    if (streamed && __atomic_load_n(c->h_flags.get() + 63, __ATOMIC_ACQUIRE)) {
         c->h_flags.get()[63] = 0;
         return set_error("streamed image upload timed out", hipSuccess), ORB_ERR_INTERNAL;
     }

@@ -101,6 +101,8 @@ struct Ctx {
 
     // host-image path (orb_extract)
     DevBuf<uint8_t> d_in;
+    // >= 0 only while orb_extract_color runs orb_extract: the ORB_COLOR_* code of the colour image it passes
+    int host_color = -1;
     // streamed upload (k_upload_stream; off by default, ORBGPU_UPLOAD=1 turns it on; off = the pageable
     // hipMemcpy2DAsync): the image's pinned host-coherent staging copy and the per-band flags the host raises (call
     // sequence numbers)

@@ -83,4 +83,26 @@ __host__ __device__ inline void undistort_project(const Distortion& D, const Und
 void undistort_point_host(const Distortion& D, float x, float y, uint32_t& ox, uint32_t& oy);
 #endif
 
+// The argument checks the entry points over extraction slots share (nullptr: accepted; else the reason)
+const char* distortion_fault(const orb_distortion* d);
+const char* grid_fault(float min_x, float min_y, float inv_w, float inv_h);   // orb_frame_create's grid checks
+const char* batch_fault(int nframes, int kp_cap);
+
+// Frame::ComputeStereoFromRGBD between the undistort step and the grids (rgbd.hip): the depth maps (device memory),
+// mbf, and where mvuRight / mvDepth of the batch go (nframes * kp_cap floats each; nullptr: working space)
+struct RgbdStep {
+    orb_depth_map map;
+    float mbf;
+    float* d_uright;
+    float* d_depth;
+};
+
+// The creators of resident frames from extraction slots: orb_frame_create_from_extract (d_counts nullptr, one frame of
+// n_single keypoints, d_uright optional), orb_frames_create_from_batch and, with rgbd, orb_frames_create_from_batch_rgbd
+// (every handle's uright is then the depth launch's).  Arguments are checked by the caller.
+int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int nframes, const uint8_t* d_desc,
+                        const orb_keypoint* d_raw, const int* d_counts, int n_single, int kp_cap, const float* d_uright,
+                        float min_x, float min_y, float inv_w, float inv_h, orb_frame** out,
+                        const RgbdStep* rgbd = nullptr);
+
 }  // namespace orbgpu

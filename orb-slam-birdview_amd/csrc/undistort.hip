@@ -6,6 +6,7 @@
 #include <limits>
 #include <new>
 
+#include "rgbd.h"
 #include "undistort.h"
 
 namespace orbgpu {
@@ -84,8 +85,6 @@ __global__ __launch_bounds__(kUndistortThreads) void k_undistort_patch(const Und
     dst[1] = p.y;
 }
 
-namespace {
-
 const char* distortion_fault(const orb_distortion* d) {
     if (!d) return "dist NULL";
     if (!std::isfinite(d->fx) || !std::isfinite(d->fy) || d->fx == 0.0f || d->fy == 0.0f)
@@ -111,6 +110,8 @@ const char* batch_fault(int nframes, int kp_cap) {
     if ((long long)nframes * (long long)kp_cap > (long long)INT_MAX) return "nframes * kp_cap above INT_MAX";
     return nullptr;
 }
+
+namespace {
 
 double guard_of(const Ctx* c) { return c->undistort_guard > 0.0 ? c->undistort_guard : kUndistortGuard; }
 
@@ -179,13 +180,16 @@ int undistort_device(const char* fn, Ctx* c, const Distortion& D, int nframes, c
     return ORB_OK;
 }
 
-// orb_frame_create_from_extract (d_counts NULL, one frame of n_single keypoints, d_uright optional) and
-// orb_frames_create_from_batch.  The stream is synchronised three times at the most: after the undistort launch (the
+}  // namespace
+
+// orb_frame_create_from_extract (d_counts NULL, one frame of n_single keypoints, d_uright optional),
+// orb_frames_create_from_batch and orb_frames_create_from_batch_rgbd (rgbd: the depth launch runs on the patched
+// undistorted records, before any grid).  The stream is synchronised three times at the most: after the undistort launch (the
 // counts and the number of points to recompute), after the keypoints and the redo list have come to the host, and
 // after the copies into the handles and the grid launches.
 int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int nframes, const uint8_t* d_desc,
                         const orb_keypoint* d_raw, const int* d_counts, int n_single, int kp_cap, const float* d_uright,
-                        float min_x, float min_y, float inv_w, float inv_h, orb_frame** out) {
+                        float min_x, float min_y, float inv_w, float inv_h, orb_frame** out, const RgbdStep* rgbd) {
     const bool batch = d_counts != nullptr;
     CTX_GUARD(c);
     const Distortion D = widen(*dist);
@@ -203,11 +207,21 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
     // the arena: the undistorted records, the redo counter and list, and every frame's k_frame_grid working space
     Arena a{c};
     if ((e = a.reserve(Arena::align(total * sizeof(orb_keypoint)) + Arena::align(total * sizeof(UndistortRedo)) +
-                       Arena::align(2 * total * 4 + 256 * (size_t)nframes) + 2048)) != hipSuccess)
+                       Arena::align(2 * total * 4 + 256 * (size_t)nframes) + (rgbd ? 2 * Arena::align(total * 4) : 0) +
+                       2048)) != hipSuccess)
         return fail("scratch", ORB_ERR_NOMEM);
     orb_keypoint* d_un = a.take<orb_keypoint>(total);
     int* d_cnt = a.take<int>(1);
     UndistortRedo* d_list = a.take<UndistortRedo>(total);
+    // mvuRight of the batch, frame f's at f * kp_cap: the caller's (one frame), or the depth launch's output
+    const float* d_ur_all = d_uright;
+    float* d_rgbd_ur = nullptr;
+    float* d_rgbd_depth = nullptr;
+    if (rgbd) {
+        d_rgbd_ur = rgbd->d_uright ? rgbd->d_uright : a.take<float>(total);
+        d_rgbd_depth = rgbd->d_depth ? rgbd->d_depth : a.take<float>(total);
+        d_ur_all = d_rgbd_ur;
+    }
     int cnt = 0;
     if ((e = launch_undistort(D, guard_of(c), d_raw, d_counts, n_single, nframes, kp_cap, d_un, d_cnt, d_list,
                               c->stream)) != hipSuccess ||
@@ -229,7 +243,7 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
             F[f] = H;
             H->device = c->device;
             H->n = n;
-            H->has_ur = d_uright != nullptr;
+            H->has_ur = d_ur_all != nullptr;
             H->min_x = min_x;
             H->min_y = min_y;
             H->inv_w = inv_w;
@@ -286,6 +300,10 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
             std::memcpy(&F[f]->kps[i].y, &p.y, 4);
         }
     }
+    // ComputeStereoFromRGBD on the final undistorted records (the patch is queued before it on the stream)
+    if (rgbd && (e = launch_rgbd_depth(rgbd->map, rgbd->mbf, nframes, d_raw, d_un, d_counts, kp_cap, d_rgbd_ur,
+                                       d_rgbd_depth, nullptr, c->stream)) != hipSuccess)
+        return fail("k_rgbd_depth", ORB_ERR_HIP);
     for (int f = 0; f < nframes; f++) {
         orb_frame* H = F[f];
         const size_t nn = (size_t)H->n;
@@ -295,8 +313,8 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
                                  c->stream)) != hipSuccess ||
              (e = hipMemcpyAsync(const_cast<orb_keypoint*>(H->d_kps), d_un + (size_t)f * kp_cap,
                                  nn * sizeof(orb_keypoint), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess ||
-             (d_uright && (e = hipMemcpyAsync(const_cast<float*>(H->d_ur), d_uright, nn * 4, hipMemcpyDeviceToDevice,
-                                              c->stream)) != hipSuccess)))
+             (d_ur_all && (e = hipMemcpyAsync(const_cast<float*>(H->d_ur), d_ur_all + (size_t)f * kp_cap, nn * 4,
+                                              hipMemcpyDeviceToDevice, c->stream)) != hipSuccess)))
             return fail("orb_frame copy", ORB_ERR_HIP);
         if ((e = launch_frame_grid(H->d_kps, H->n, ProjGrid{min_x, min_y, inv_w, inv_h}, const_cast<int*>(H->d_coff),
                                    const_cast<int*>(H->d_cidx), d_work, c->stream)) != hipSuccess)
@@ -315,7 +333,6 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
     return ORB_OK;
 }
 
-}  // namespace
 }  // namespace orbgpu
 
 using namespace orbgpu;

@@ -76,7 +76,7 @@ ORBextractor::~ORBextractor() {
     if (ctx_) orb_destroy(ctx_);
 }
 
-int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t step) {
+int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color) {
     const int cap = orb_batch_kp_cap(ctx_, cols, rows);   // exact upper bound for this image size
     if (cap < 0) throw OrbGpuError(cap, "orb_batch_kp_cap");
     if ((int)kbuf_.size() < cap) {
@@ -84,8 +84,12 @@ int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t st
         dbuf_.resize((size_t)cap * 32);
     }
     int n = 0;
-    check(orb_extract(ctx_, data, cols, rows, step, kbuf_.data(), (int)kbuf_.size(), &n, dbuf_.data()),
-          "orb_extract");
+    if (color < 0)
+        check(orb_extract(ctx_, data, cols, rows, step, kbuf_.data(), (int)kbuf_.size(), &n, dbuf_.data()),
+              "orb_extract");
+    else
+        check(orb_extract_color(ctx_, color, data, cols, rows, step, kbuf_.data(), (int)kbuf_.size(), &n, dbuf_.data()),
+              "orb_extract_color");
     mvImagePyramid.invalidate((size_t)nlevels);
     return n;
 }
@@ -95,6 +99,18 @@ void ORBextractor::operator()(const ImageView& image, const ImageView& /*mask*/,
     if (image.empty()) return;   // ORBextractor.cc:1046-1047
     const int n = extract_raw(image.data, image.cols, image.rows, image.step);
     // :1061-1070: descriptors n x 32, released when there is no keypoint
+    if (n == 0)
+        descriptors.release();
+    else
+        descriptors.create(n);
+    keypoints.assign(kbuf_.begin(), kbuf_.begin() + n);
+    if (n) memcpy(descriptors.buf.data(), dbuf_.data(), (size_t)n * 32);
+}
+
+void ORBextractor::operator()(const ColorImageView& image, const ImageView& /*mask*/, std::vector<KeyPoint>& keypoints,
+                              DescriptorMat& descriptors) {
+    if (image.empty()) return;   // ORBextractor.cc:1046-1047
+    const int n = extract_raw(image.data, image.cols, image.rows, image.step, image.code);
     if (n == 0)
         descriptors.release();
     else

@@ -54,6 +54,21 @@ struct ImageView {
     uint8_t at(int y, int x) const { return data[(size_t)y * step + x]; }
 };
 
+// Colour 8-bit image view (cv::Mat CV_8UC3 / CV_8UC4 stand-in; with OpenCV: ColorImageView(im.data, im.cols, im.rows,
+// im.step, code)): interleaved pixels in the order `code` names (ORB_COLOR_RGB / BGR / RGBA / BGRA of
+// include/orbgpu.h: Tracking's mbRGB and im.channels()), rows `step` bytes apart.
+struct ColorImageView {
+    const uint8_t* data = nullptr;
+    int cols = 0, rows = 0;
+    size_t step = 0;
+    int code = ORB_COLOR_RGB;
+    ColorImageView() = default;
+    ColorImageView(const uint8_t* d, int c, int r, size_t s, int code_)
+        : data(d), cols(c), rows(r), step(s ? s : (size_t)c * (code_ == ORB_COLOR_RGB || code_ == ORB_COLOR_BGR ? 3 : 4)),
+          code(code_) {}
+    bool empty() const { return data == nullptr || cols <= 0 || rows <= 0; }
+};
+
 // n x 32 CV_8U descriptor matrix stand-in (row i = descriptor of keypoint i).
 struct DescriptorMat {
     int rows = 0;
@@ -122,6 +137,10 @@ public:
     void operator()(cv::InputArray image, cv::InputArray mask, std::vector<cv::KeyPoint>& keypoints,
                     cv::OutputArray descriptors);
 #endif
+    // The same for the camera's colour image: the cvtColor that opens Tracking::GrabImage* (Tracking.cc:172-307) runs
+    // on the GPU in front of the extraction (orb_extract_color), and mvImagePyramid[0] is then mImGray.
+    void operator()(const ColorImageView& image, const ImageView& mask, std::vector<KeyPoint>& keypoints,
+                    DescriptorMat& descriptors);
 
     int inline GetLevels() { return nlevels; }
     float inline GetScaleFactor() { return (float)scaleFactor; }
@@ -152,7 +171,8 @@ protected:
 private:
     friend class ImagePyramid;
     void init(int device, int variant);
-    int extract_raw(const uint8_t* data, int cols, int rows, size_t step);   // returns #keypoints in kbuf_/dbuf_
+    // returns #keypoints in kbuf_/dbuf_; color < 0: a gray image, else its ORB_COLOR_* code
+    int extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color = -1);
     orb_ctx* ctx_ = nullptr;
     std::vector<KeyPoint> kbuf_;
     std::vector<uint8_t> dbuf_;

@@ -103,6 +103,15 @@ public:
                                                 const uint8_t* d_descriptors, const KeyPoint* d_keysRaw,
                                                 const int* d_counts, int kp_cap, float minX, float maxX, float minY,
                                                 float maxY);
+    // the RGB-D Frame constructor after extraction (Frame.cc:145-200) for a batch: FromBatch, with
+    // Frame::ComputeStereoFromRGBD run on the undistorted keypoints between the undistort step and the grids.  depth:
+    // the batch's depth maps in device memory (include/orbgpu.h orb_depth_map).  d_uRight / d_depth (nframes * kp_cap
+    // floats each, device memory, either may be NULL) receive mvuRight / mvDepth; every frame carries its uRight.
+    static std::vector<ResidentFrame> FromBatchRGBD(orb_ctx* ctx, const orb_distortion& dist, const orb_depth_map& depth,
+                                                    float mbf, int nframes, const uint8_t* d_descriptors,
+                                                    const KeyPoint* d_keysRaw, const int* d_counts, int kp_cap,
+                                                    float minX, float maxX, float minY, float maxY, float* d_uRight,
+                                                    float* d_depth);
     ~ResidentFrame();
     ResidentFrame(ResidentFrame&& o) noexcept;
     ResidentFrame& operator=(ResidentFrame&& o) noexcept;

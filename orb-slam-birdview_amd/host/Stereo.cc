@@ -21,4 +21,18 @@ int ComputeStereoMatches(const ORBextractor& left, const ORBextractor& right, co
     return n;
 }
 
+int ComputeStereoFromRGBD(const orb_depth_map& imDepth, const std::vector<KeyPoint>& mvKeys,
+                          const std::vector<KeyPoint>& mvKeysUn, float mbf, std::vector<float>& mvuRight,
+                          std::vector<float>& mvDepth) {
+    const int N = (int)mvKeys.size();
+    if (mvKeysUn.size() != mvKeys.size()) throw std::invalid_argument("ComputeStereoFromRGBD: mvKeysUn.size() != N");
+    mvuRight.assign(N, -1.0f);   // Frame.cc:841-842
+    mvDepth.assign(N, -1.0f);
+    int n = 0;
+    const int st = orb_stereo_from_rgbd_host(&imDepth, mbf, N, mvKeys.data(), mvKeysUn.data(), mvuRight.data(),
+                                             mvDepth.data(), &n);
+    if (st != ORB_OK) throw OrbGpuError(st, "ComputeStereoFromRGBD");
+    return n;
+}
+
 }  // namespace ORB_SLAM2

@@ -21,6 +21,15 @@ int ComputeStereoMatches(const ORBextractor& left, const ORBextractor& right, co
                          const DescriptorMat& mDescriptorsRight, float mb, float mbf, std::vector<float>& mvuRight,
                          std::vector<float>& mvDepth);
 
+// Frame::ComputeStereoFromRGBD (src/Frame.cc:839-860) with Tracking::GrabImageRGBD's convertTo folded in
+// (Tracking.cc:229-230): imDepth is the RAW depth image (CV_16U or CV_32F as orb_depth_map names them, host memory)
+// with factor = mDepthMapFactor; mvKeys gives the pixel, mvKeysUn the x of mvuRight.  Runs on the CPU (one frame's
+// keypoints are on the host already: orb_stereo_from_rgbd_host is the definition and the right call).  Returns the
+// number of keypoints with a depth; a keypoint outside the image throws OrbGpuError (the reference reads outside it).
+int ComputeStereoFromRGBD(const orb_depth_map& imDepth, const std::vector<KeyPoint>& mvKeys,
+                          const std::vector<KeyPoint>& mvKeysUn, float mbf, std::vector<float>& mvuRight,
+                          std::vector<float>& mvDepth);
+
 }  // namespace ORB_SLAM2
 
 #endif

@@ -12,12 +12,13 @@ import numpy as np
 
 from ._lib import (VARIANT_BLUR_HALFUP, VARIANT_DEFAULT, VARIANT_NO_FMA, VARIANT_RESIZE_GENERIC,
                    VARIANT_TIE_REVERSE, OrbBirdParams, OrbError, OrbFeatVec, OrbFrameGrid, OrbParams, OrbProjFrameTarget,
-                   OrbProjTarget, OrbCamera, OrbDistortion, OrbFusePointsTarget, KfdbNeighboursFn, check, lib)
+                   OrbProjTarget, OrbCamera, OrbDepthMap, OrbDistortion, OrbFusePointsTarget, KfdbNeighboursFn, check, lib)
 
 __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError", "device_count",
            "features_in_area", "frame_grid", "Frame", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
            "PROJ_GATE_NONE", "PROJ_GATE_FUSE", "proj_queries", "project_best_host",
-           "distortion", "undistort_points_host", "image_bounds", "undistort_keypoints", "undistort_guard",
+           "COLOR_RGB", "COLOR_BGR", "COLOR_RGBA", "COLOR_BGRA", "DEPTH_U16", "DEPTH_F32", "to_gray_host", "depth_map",
+           "stereo_from_rgbd_host", "distortion", "undistort_points_host", "image_bounds", "undistort_keypoints", "undistort_guard",
            "MapPoints", "POINT_PROJ_DTYPE", "FRUSTUM_FRAME", "FRUSTUM_FUSE", "camera", "project_points_host",
            "compute_stereo_matches", "ORBVocabulary", "KeyFrameDatabase", "bow_score", "KFDB_RELOC", "KFDB_LOOP",
            "BirdORB", "cornerSubPix",
@@ -44,8 +45,64 @@ assert POINT_PROJ_DTYPE.itemsize == 36
 FRUSTUM_FRAME, FRUSTUM_FUSE = 0, 1        # ORB_FRUSTUM_*
 
 
+COLOR_RGB, COLOR_BGR, COLOR_RGBA, COLOR_BGRA = 0, 1, 2, 3   # ORB_COLOR_*
+DEPTH_U16, DEPTH_F32 = 0, 1                                  # ORB_DEPTH_*
+
+
 def _p(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def _color_image(image, color):
+    """An H x W x 3 / 4 uint8 array with unit-stride pixels, as the colour entry points take it (rows may be padded)."""
+    img = np.asarray(image)
+    ch = 3 if color in (COLOR_RGB, COLOR_BGR) else 4
+    assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == ch, "H x W x %d uint8 expected" % ch
+    if not (img.strides[2] == 1 and img.strides[1] == ch and img.strides[0] >= img.shape[1] * ch):
+        img = np.ascontiguousarray(img)
+    return img
+
+
+def to_gray_host(image, color):
+    """orb_to_gray_host: cvtColor(image, gray, CV_{RGB,BGR,RGBA,BGRA}2GRAY) as OpenCV 3.2 computes it, on the CPU (the
+    definition the GPU forms equal byte for byte).  image: H x W x 3 / 4 uint8; color: COLOR_*; no context, no GPU."""
+    img = _color_image(image, color)
+    h, w = img.shape[:2]
+    out = np.zeros((h, w), np.uint8)
+    check(lib().orb_to_gray_host(color, _p(img), w, h, img.strides[0], _p(out), w), "orb_to_gray_host")
+    return out
+
+
+def depth_map(data, type, w, h, row_stride=None, frame_pitch=None, factor=1.0):
+    """orb_depth_map: data is a device pointer (int) or a host numpy array (kept alive by the caller); type DEPTH_U16 /
+    DEPTH_F32; row_stride / frame_pitch in bytes (default: packed); factor = mDepthMapFactor (already inverted)."""
+    es = 2 if type == DEPTH_U16 else 4
+    rs = w * es if row_stride is None else row_stride
+    ptr = data.ctypes.data if isinstance(data, np.ndarray) else data
+    return OrbDepthMap(ctypes.c_void_p(ptr), type, w, h, rs, rs * h if frame_pitch is None else frame_pitch,
+                       float(np.float32(factor)))
+
+
+def stereo_from_rgbd_host(depth_image, factor, kps, kps_un, mbf):
+    """orb_stereo_from_rgbd_host: Frame::ComputeStereoFromRGBD (with GrabImageRGBD's convertTo folded in) on the CPU, the
+    definition, and the right call for one frame whose keypoints are on the host.  depth_image: H x W uint16 or float32
+    (the RAW depth image; rows may be padded); kps: mvKeys (the pixel read), kps_un: mvKeysUn (the x of mvuRight).
+    Returns (mvuRight, mvDepth, number of keypoints with a depth).  No context, no GPU."""
+    d = np.asarray(depth_image)
+    assert d.ndim == 2 and d.dtype in (np.uint16, np.float32), "H x W uint16 or float32 expected"
+    if d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize:
+        d = np.ascontiguousarray(d)
+    k = np.ascontiguousarray(kps, KP_DTYPE)
+    ku = np.ascontiguousarray(kps_un, KP_DTYPE)
+    assert len(k) == len(ku)
+    m = depth_map(d, DEPTH_U16 if d.dtype == np.uint16 else DEPTH_F32, d.shape[1], d.shape[0], d.strides[0],
+                  factor=factor)
+    ur = np.zeros(len(k), np.float32)
+    dep = np.zeros(len(k), np.float32)
+    nv = ctypes.c_int(0)
+    check(lib().orb_stereo_from_rgbd_host(ctypes.byref(m), float(np.float32(mbf)), len(k), _p(k), _p(ku), _p(ur), _p(dep),
+                                          ctypes.byref(nv)), "orb_stereo_from_rgbd_host")
+    return ur, dep, nv.value
 
 
 def device_count():
@@ -142,29 +199,38 @@ class ORBextractor(_Ctx):
     def umax(self):
         return self._umax.copy()
 
-    def __call__(self, image, mask=None, keypoints=None, descriptors=None):
+    def __call__(self, image, mask=None, keypoints=None, descriptors=None, color=None):
         """operator()(image, mask, keypoints, descriptors): returns (keypoints, descriptors).
 
         An empty image returns the given outputs untouched (ORBextractor.cc:1046-1047); mask is
-        ignored as in the reference (ORBextractor.h:58)."""
+        ignored as in the reference (ORBextractor.h:58).  color=COLOR_*: image is the camera's H x W x 3 / 4 colour
+        image; the cvtColor of Tracking::GrabImage* runs on the GPU in front of the extraction (orb_extract_color) and
+        mvImagePyramid[0] is then mImGray."""
         img = np.asarray(image)
         if img.size == 0:
             return keypoints, descriptors
-        assert img.dtype == np.uint8 and img.ndim == 2, "CV_8UC1 expected (ORBextractor.cc:1050)"
-        if not (img.strides[1] == 1 and img.strides[0] >= img.shape[1]):   # rows with padding go down as they are
-            img = np.ascontiguousarray(img)
-        h, w = img.shape
+        if color is None:
+            assert img.dtype == np.uint8 and img.ndim == 2, "CV_8UC1 expected (ORBextractor.cc:1050)"
+            if not (img.strides[1] == 1 and img.strides[0] >= img.shape[1]):   # rows with padding go down as they are
+                img = np.ascontiguousarray(img)
+        else:
+            img = _color_image(img, color)
+        h, w = img.shape[:2]
         cap = 4 * max(self.params.nfeatures, 1) + 256
         while True:
             kps = np.zeros(cap, KP_DTYPE)
             desc = np.zeros((cap, 32), np.uint8)
             n = ctypes.c_int(0)
-            st = lib().orb_extract(self.h, _p(img), w, h, img.strides[0], _p(kps), cap, ctypes.byref(n),
-                                   _p(desc))
+            if color is None:
+                st = lib().orb_extract(self.h, _p(img), w, h, img.strides[0], _p(kps), cap, ctypes.byref(n),
+                                       _p(desc))
+            else:
+                st = lib().orb_extract_color(self.h, color, _p(img), w, h, img.strides[0], _p(kps), cap,
+                                             ctypes.byref(n), _p(desc))
             if st == -3:
                 cap = n.value
                 continue
-            check(st, "orb_extract")
+            check(st, "orb_extract" if color is None else "orb_extract_color")
             break
         self._last_shape = (h, w)
         return kps[:n.value].copy(), desc[:n.value].copy()
@@ -207,6 +273,33 @@ class BatchExtractor(_Ctx):
         frames = np.ascontiguousarray(frames, np.uint8)
         assert frames.shape == (self.batch, self.hgt, self.w)
         check(lib().orb_memcpy_h2d(self.h, self.d_frames, _p(frames), frames.nbytes), "h2d")
+
+    def upload_color(self, frames, color):
+        """The batch as the camera's colour frames ((batch, H, W, 3 / 4) uint8, color=COLOR_*): uploaded, then
+        converted to gray on the device into the buffer launch() reads (orb_to_gray_device; asynchronous on the
+        context's stream, so launch() may follow at once)."""
+        ch = 3 if color in (COLOR_RGB, COLOR_BGR) else 4
+        frames = np.ascontiguousarray(frames, np.uint8)
+        assert frames.shape == (self.batch, self.hgt, self.w, ch)
+        if getattr(self, "d_color_bytes", 0) < frames.nbytes:
+            if getattr(self, "d_color", None):
+                lib().orb_device_free(self.h, self.d_color)
+                self.d_color = None
+            self.d_color = self._alloc(frames.nbytes)
+            self.d_color_bytes = frames.nbytes
+        check(lib().orb_memcpy_h2d(self.h, self.d_color, _p(frames), frames.nbytes), "h2d")
+        check(lib().orb_to_gray_device(self.h, color, self.d_color, self.batch, self.w, self.hgt,
+                                       self.w * self.hgt * ch, self.w * ch, self.d_frames, self.w * self.hgt, self.w),
+              "orb_to_gray_device")
+
+    def stereo_from_rgbd(self, dmap, mbf, d_kps_un, d_uright, d_depth, d_nvalid=None, nframes=None):
+        """Frame::ComputeStereoFromRGBD for the frames of the last launch, on the device (orb_stereo_from_rgbd_device;
+        asynchronous).  dmap: depth_map(...) over device memory; d_kps_un: the undistorted keypoints in the layout of
+        d_kps (d_kps itself without distortion); outputs at [f * kp_cap + i] (device pointers)."""
+        n = self.batch if nframes is None else nframes
+        check(lib().orb_stereo_from_rgbd_device(self.h, ctypes.byref(dmap), float(np.float32(mbf)), n, self.d_kps,
+                                                d_kps_un, self.d_counts, self.kp_cap, d_uright, d_depth, d_nvalid),
+              "orb_stereo_from_rgbd_device")
 
     def launch(self, nframes=None):
         n = self.batch if nframes is None else nframes
@@ -263,7 +356,7 @@ class BatchExtractor(_Ctx):
 
     def close(self):
         if getattr(self, "h", None):
-            for p in ("d_frames", "d_kps", "d_desc", "d_counts"):
+            for p in ("d_frames", "d_kps", "d_desc", "d_counts", "d_color"):
                 if getattr(self, p, None):
                     lib().orb_device_free(self.h, getattr(self, p))
                     setattr(self, p, None)
@@ -399,6 +492,33 @@ class Frame:
         for f in range(int(nframes)):
             self = cls.__new__(cls)
             self.min_xy, self.inv, self.has_uright = proto.min_xy, proto.inv, False
+            self.h = vp(handles[f])
+            self.n = lib().orb_frame_count(self.h)
+            frames.append(self)
+        return frames
+
+    @classmethod
+    def from_batch_rgbd(cls, ctx_or_matcher, dist, dmap, mbf, nframes, d_desc, d_kps_raw, d_counts, kp_cap, bounds=None,
+                        inv=None, min_xy=(0.0, 0.0), d_uright=None, d_depth=None):
+        """The RGB-D Frame constructor after extraction for a whole batch (orb_frames_create_from_batch_rgbd): from_batch
+        with Frame::ComputeStereoFromRGBD on the undistorted keypoints; dmap: depth_map(...) over device memory.  Every
+        Frame carries its uright; d_uright / d_depth (device pointers, nframes * kp_cap floats, optional) receive
+        mvuRight / mvDepth."""
+        proto = cls.__new__(cls)
+        proto.h = None
+        proto._set_grid(bounds, inv, min_xy)
+        vp = ctypes.c_void_p
+        handles = (vp * max(int(nframes), 1))()
+        fn = "orb_frames_create_from_batch_rgbd"
+        check(getattr(lib(), fn)(_ctx_handle(ctx_or_matcher), ctypes.byref(dist), ctypes.byref(dmap),
+                                 float(np.float32(mbf)), int(nframes), vp(d_desc), vp(d_kps_raw), vp(d_counts),
+                                 int(kp_cap), proto.min_xy[0], proto.min_xy[1], proto.inv[0], proto.inv[1],
+                                 None if d_uright is None else vp(d_uright), None if d_depth is None else vp(d_depth),
+                                 handles), fn)
+        frames = []
+        for f in range(int(nframes)):
+            self = cls.__new__(cls)
+            self.min_xy, self.inv, self.has_uright = proto.min_xy, proto.inv, True
             self.h = vp(handles[f])
             self.n = lib().orb_frame_count(self.h)
             frames.append(self)

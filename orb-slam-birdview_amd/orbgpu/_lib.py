@@ -71,6 +71,11 @@ class OrbDistortion(ctypes.Structure):   # orb_distortion
     _fields_ = [("fx", cf), ("fy", cf), ("cx", cf), ("cy", cf), ("k", cf * 4)]
 
 
+class OrbDepthMap(ctypes.Structure):   # orb_depth_map
+    _fields_ = [("data", vp), ("type", ci), ("w", ci), ("h", ci), ("row_stride", csz), ("frame_pitch", csz),
+                ("factor", cf)]
+
+
 class OrbFusePointsTarget(ctypes.Structure):   # orb_fuse_points_target
     _fields_ = [("camera", OrbCamera), ("frame", vp), ("inv_sigma2", vp), ("th", cf), ("n", ci), ("ids", vp),
                 ("best_idx", vp), ("best_dist", vp), ("proj_out", vp)]
@@ -150,6 +155,13 @@ SIGNATURES = {
                                            ctypes.POINTER(vp)]),
     "orb_frames_create_from_batch": (ci, [vp, ctypes.POINTER(OrbDistortion), ci, vp, vp, vp, ci, cf, cf, cf, cf, vp]),
     "orb_debug_undistort_guard": (ci, [vp, ctypes.c_double]),
+    "orb_to_gray_host": (ci, [ci, vp, ci, ci, csz, vp, csz]),
+    "orb_to_gray_device": (ci, [vp, ci, vp, ci, ci, ci, csz, csz, vp, csz, csz]),
+    "orb_extract_color": (ci, [vp, ci, vp, ci, ci, csz, vp, ci, ctypes.POINTER(ci), vp]),
+    "orb_stereo_from_rgbd_host": (ci, [ctypes.POINTER(OrbDepthMap), cf, ci, vp, vp, vp, vp, ctypes.POINTER(ci)]),
+    "orb_stereo_from_rgbd_device": (ci, [vp, ctypes.POINTER(OrbDepthMap), cf, ci, vp, vp, vp, ci, vp, vp, vp]),
+    "orb_frames_create_from_batch_rgbd": (ci, [vp, ctypes.POINTER(OrbDistortion), ctypes.POINTER(OrbDepthMap), cf, ci,
+                                               vp, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp]),
     "orb_points_create": (ci, [vp, ci, ctypes.POINTER(vp)]),
     "orb_points_write": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
     "orb_points_capacity": (ci, [vp]),
