@@ -857,6 +857,96 @@ int orb_frames_create_from_batch_rgbd(orb_ctx* ctx, const orb_distortion* dist, 
                                       const int* d_counts, int kp_cap, float min_x, float min_y, float inv_w,
                                       float inv_h, float* d_uright, float* d_depth, orb_frame** out);
 
+/* ======================= Stereo input: rectification (cv::remap) and the stereo Frame constructor ============= */
+
+/* cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) as every stereo frame of the reference goes through it, once per eye,
+ * before System::TrackStereo sees it (Examples/Stereo/stereo_euroc.cc:136-137, Examples/ROS/ORB_SLAM2/src/
+ * ros_stereo.cc:161-162): 8-bit one-channel images, CV_32FC1 map1 / map2, INTER_LINEAR, BORDER_CONSTANT with value 0.
+ * The definition is OpenCV 3.2 imgwarp.cpp on x86-64 without IPP, RemapInvoker + remapBilinear<FixedPtCast<int, uchar,
+ * 15>, RemapVec_8u, short>.  The destination has the maps' size (dw, dh); the source (sw, sh) may
+ * differ.  For a destination pixel with map values mx, my:
+ *   sx = cvtss2si(mx * 32.0f), sy likewise: to nearest, ties to even; NaN, +-inf or a product outside int give INT_MIN;
+ *   ix = sat_s16(sx >> 5) (arithmetic shift), fx = sx & 31; iy, fy likewise;
+ *   w00 = (32-fx)(32-fy)*32, w01 = fx(32-fy)*32, w10 = (32-fx)fy*32, w11 = fx*fy*32  (integers, sum 32768);
+ *   each of the taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) is decided on its own: inside [0, sw) x [0, sh) it
+ *   reads the source, outside it reads 0;
+ *   dst = (w00 S00 + w01 S01 + w10 S10 + w11 S11 + 16384) >> 15.
+ * Rows are stride bytes apart for the images and map_stride bytes apart for the maps; any base alignment and any
+ * stride are accepted for the images, maps are 4-byte aligned (base and stride).  Only [row, row + dw) of the
+ * destination is written: padding bytes stay untouched.  There is no variant bit for it.
+ *   orb_remap_host         the definition, on the CPU.  No context, no GPU.
+ *   orb_rectify_maps_host  cv::initUndistortRectifyMap(K, D, R, P(0:3,0:3), size, CV_32F, m1, m2) of OpenCV 3.2
+ *                          undistort.cpp, on the CPU, one-off per calibration.  K, R, P33: nine doubles each, row-major,
+ *                          as the YAML gives them; D: nD = 4, 5 or 8 doubles (k1, k2, p1, p2, then k3, then k4..k6;
+ *                          missing ones 0).  All arithmetic in double, uncontracted: iR = inverse(P33 * R) (sums in the
+ *                          order k = 0, 1, 2; the 3x3 adjugate times 1.0 / det); per row i: _x = i*ir[1] + ir[2], _y =
+ *                          i*ir[4] + ir[5], _w = i*ir[7] + ir[8]; per column the pixel first, then _x += ir[0], _y +=
+ *                          ir[3], _w += ir[6] (sequential sums); per pixel w = 1/_w, x = _x*w, y = _y*w, r2 = x2 + y2,
+ *                          kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2), xd = x kr + p1 2xy +
+ *                          p2 (r2 + 2 x2), yd = y kr + p1 (r2 + 2 y2) + p2 2xy, map = (float)(fx xd + u0), (float)(fy yd
+ *                          + v0).  ORB_ERR_ARG: 12 or 14 coefficients (thin-prism and tilt are out of scope), any other
+ *                          nD, a zero determinant, NULL arrays, a side above 4096, misaligned maps.  A caller that has
+ *                          OpenCV passes ITS OWN maps to the calls below instead: the remap contract does not depend on
+ *                          this builder.
+ *   orb_rectify_create     the resident map of one camera, built once: the float maps (host memory) are converted to the
+ *                          fixed-point form above (OpenCV converts per call and per tile) and kept on ctx's device.
+ *                          Synchronous.  Lifetime and device rules are orb_frame's: usable with any context of the same
+ *                          device, one thread at a time, destroyed before the context that created it.  dw == 0 or dh ==
+ *                          0 gives an empty map (every remap through it is ORB_OK with nothing touched).
+ *   orb_rectify_size       the maps' (dw, dh).
+ *   orb_remap_device       nframes frames in device memory in one launch (k_remap), asynchronous on the context's
+ *                          stream: frame f at d_src + f * src_frame_pitch goes through maps[f % nmaps] to d_dst + f *
+ *                          dst_frame_pitch.  nmaps = 1 is a mono camera; nmaps = 2 is the interleaved left / right
+ *                          layout: frames 2p, 2p+1 are then exactly what orb_extract_batch_device and
+ *                          orb_stereo_batch_device consume, on the same stream with no synchronisation between.  All
+ *                          maps of a call have one size; at most ORB_REMAP_MAX_MAPS of them.  The birdview object has a
+ *                          STREAM OF ITS OWN: call orb_sync before d_dst goes to orb_bird_extract_device.
+ *   orb_remap              one host image, remapped on the GPU into a host image.  Synchronous.
+ *   orb_extract_rectified  orb_extract for a raw host image: uploaded, remapped on the device, then orb_extract's
+ *                          single-frame chain unchanged on the rectified image (of the maps' size).  orb_get_level(ctx,
+ *                          0, ...) afterwards returns the rectified image, and two contexts that did this are valid
+ *                          left / right arguments of orb_compute_stereo_matches.  Empty image (sw == 0 || sh == 0 ||
+ *                          img == NULL, or an empty map): ORB_OK, the outputs untouched; capacity as orb_extract.
+ * ORB_ERR_ARG before any GPU work, outputs untouched: NULL arrays with a non-empty size; negative sizes or counts; any
+ * side above 4096; a stride below a row; with nframes > 1 a frame pitch below (h - 1) * stride + the row's bytes;
+ * nmaps < 1 or above ORB_REMAP_MAX_MAPS, or a NULL entry; maps of differing size, or of another device than the
+ * context's; float maps that are not 4-byte aligned.  nframes == 0 or an empty destination: ORB_OK, nothing touched. */
+#define ORB_REMAP_MAX_MAPS 16
+typedef struct orb_rectify orb_rectify;
+int  orb_remap_host(const uint8_t* src, int sw, int sh, size_t src_stride, const float* map_x, const float* map_y,
+                    size_t map_stride, int dw, int dh, uint8_t* dst, size_t dst_stride);
+int  orb_rectify_maps_host(const double* K, const double* D, int nD, const double* R, const double* P33, int w, int h,
+                           float* map_x, float* map_y, size_t map_stride);
+int  orb_rectify_create(orb_ctx* ctx, int dw, int dh, const float* map_x, const float* map_y, size_t map_stride,
+                        orb_rectify** out);
+void orb_rectify_destroy(orb_rectify* rect);
+int  orb_rectify_size(const orb_rectify* rect, int* w, int* h);
+int  orb_remap_device(orb_ctx* ctx, int nmaps, const orb_rectify* const* maps, const uint8_t* d_src, int nframes, int sw,
+                      int sh, size_t src_frame_pitch, size_t src_row_stride, uint8_t* d_dst, size_t dst_frame_pitch,
+                      size_t dst_row_stride);
+int  orb_remap(orb_ctx* ctx, const orb_rectify* rect, const uint8_t* img, int sw, int sh, size_t stride, uint8_t* dst,
+               size_t dst_stride);
+int  orb_extract_rectified(orb_ctx* ctx, const orb_rectify* rect, const uint8_t* img, int sw, int sh, size_t stride,
+                           orb_keypoint* kps, int cap, int* n, uint8_t* desc);
+
+/* The stereo Frame constructor after extraction (Frame.cc:129-141: UndistortKeyPoints, ComputeStereoMatches,
+ * AssignFeaturesToGrid) in one call, after an orb_extract_batch_device of 2 * npairs frames on ctx (slots 2p, 2p+1 =
+ * the left, right image of pair p; d_desc / d_kps_raw / d_counts / kp_cap are that batch's outputs):
+ *   orb_frames_create_from_batch's undistort launch with its guard-band redo over the LEFT frames only (k[0] == 0 stays
+ *   the identity path, which is what rectified images give); orb_stereo_batch_device's search, which reads the RAW
+ *   keypoints of both sides as the reference's mvKeys / mvKeysRight; the grids of the left frames from their
+ *   undistorted keypoints.
+ * out receives npairs handles, every one carrying its mvuRight (use_uright = 1 works).  d_uright / d_depth (npairs *
+ * kp_cap floats each, pair p's at p * kp_cap, as orb_stereo_batch_device lays them out) receive mvuRight / mvDepth;
+ * either may be NULL.  Failure, synchronisation-count and argument rules are orb_frames_create_from_batch's (a count
+ * above kp_cap, of a left or a right slot, is ORB_ERR_CAPACITY with nothing leaked); ORB_ERR_ARG also for mb or mbf not
+ * finite, when the context's last batch has fewer than 2 * npairs frames or another kp_cap, and for kp_cap above
+ * ORB_STEREO_MAX_RIGHT. */
+int orb_frames_create_from_batch_stereo(orb_ctx* ctx, const orb_distortion* dist, int npairs, float mb, float mbf,
+                                        const uint8_t* d_desc, const orb_keypoint* d_kps_raw, const int* d_counts,
+                                        int kp_cap, float min_x, float min_y, float inv_w, float inv_h, float* d_uright,
+                                        float* d_depth, orb_frame** out);
+
 /* ======================= DBoW2 vocabulary transform ======================= */
 
 typedef struct orb_vocab orb_vocab;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "orbgpu_ctx.h"
+#include "remap.h"
 #include "rgbd.h"
 
 namespace orbgpu {
@@ -727,7 +728,9 @@ int orb_extract(orb_ctx* h, const uint8_t* img, int w, int hgt, size_t stride, o
     if ((e = c->h_pinned.ensure(need)) != hipSuccess) return set_error("pinned staging", e), ORB_ERR_NOMEM;
     // orb_extract_color (rgbd.hip) comes through here with its code in the context: img is then a colour image
     const int color = c->host_color;
-    const bool streamed = c->upload_stream && color < 0;   // (a colour image always takes the plain upload)
+    // orb_extract_rectified (remap.hip) likewise, with its map: img is then the raw image, w x hgt the maps' size
+    const orb_rectify* const rect = c->host_rect;
+    const bool streamed = c->upload_stream && color < 0 && !rect;   // (those two always take the plain upload)
     constexpr int kBands = 16;   // (h_flags[kBands .. 63]: [63] = the upload kernel's timeout flag)
     const int band_rows = (hgt + kBands - 1) / kBands, nbands = (hgt + band_rows - 1) / band_rows;
     if (color >= 0) {
@@ -742,6 +745,10 @@ int orb_extract(orb_ctx* h, const uint8_t* img, int w, int hgt, size_t stride, o
         if ((e = launch_to_gray(color, d_color, 1, w, hgt, cpitch * hgt, cpitch, c->d_in.get(), pitch * hgt, pitch,
                                 c->stream)) != hipSuccess)
             return set_error("k_to_gray", e), ORB_ERR_HIP;
+    } else if (rect) {
+        if ((st = upload_and_remap(c, rect, img, c->host_raw_w, c->host_raw_h, c->host_raw_stride, c->d_in.get(),
+                                   pitch)) != ORB_OK)
+            return st;
     } else if (streamed) {
         if ((e = c->h_img.ensure(pitch * hgt)) != hipSuccess) return set_error("pinned image staging", e), ORB_ERR_NOMEM;
         if (!c->h_flags) {

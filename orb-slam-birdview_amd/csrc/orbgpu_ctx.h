@@ -103,6 +103,10 @@ struct Ctx {
     DevBuf<uint8_t> d_in;
     // >= 0 only while orb_extract_color runs orb_extract: the ORB_COLOR_* code of the colour image it passes
     int host_color = -1;
+    // non-NULL only while orb_extract_rectified runs orb_extract: the map, and the raw image's size and stride
+    const orb_rectify* host_rect = nullptr;
+    int host_raw_w = 0, host_raw_h = 0;
+    size_t host_raw_stride = 0;
     // streamed upload (k_upload_stream; off by default, ORBGPU_UPLOAD=1 turns it on; off = the pageable
     // hipMemcpy2DAsync): the image's pinned host-coherent staging copy and the per-band flags the host raises (call
     // sequence numbers)

@@ -14,10 +14,12 @@
 #include <algorithm>
 #include <cstdlib>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "orbgpu_ctx.h"
+#include "undistort.h"
 
 namespace orbgpu {
 namespace {
@@ -461,6 +463,34 @@ int orb_stereo_batch_device(orb_ctx* h, int npairs, float mb, float mbf, float* 
     if (c->prof_on) Ctx::marker(c, ORB_K_STEREO, 0, c->stream);
     if (e != hipSuccess) return set_error("stereo kernels", e), ORB_ERR_HIP;
     return ORB_OK;
+}
+
+int orb_frames_create_from_batch_stereo(orb_ctx* h, const orb_distortion* dist, int npairs, float mb, float mbf,
+                                        const uint8_t* d_desc, const orb_keypoint* d_kps_raw, const int* d_counts,
+                                        int kp_cap, float min_x, float min_y, float inv_w, float inv_h, float* d_uright,
+                                        float* d_depth, orb_frame** out) {
+    const char* const fn = "orb_frames_create_from_batch_stereo";
+    if (const char* why = distortion_fault(dist)) return arg_error(fn, why);
+    if (!std::isfinite(mb) || !std::isfinite(mbf)) return arg_error(fn, "mb or mbf not finite");
+    if (npairs > 32767) return arg_error(fn, "more than 32,767 pairs");
+    if (const char* why = batch_fault(2 * npairs, kp_cap)) return arg_error(fn, why);
+    if (npairs > 0 && (!d_desc || !d_kps_raw || !d_counts || !out)) return arg_error(fn, "NULL arrays with npairs > 0");
+    if (const char* why = grid_fault(min_x, min_y, inv_w, inv_h)) return arg_error(fn, why);
+    if (npairs == 0) return ORB_OK;
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
+    // the window search reads the images and pyramids the context's last batch left on the device
+    if (!c->last_kps || c->last_nframes < 2 * npairs)
+        return arg_error(fn, "the last batch holds fewer than 2 * npairs frames");
+    if (c->last_kp_cap != kp_cap) return arg_error(fn, "kp_cap is not the last batch's");
+    if (kp_cap > kStereoMaxRight) return arg_error(fn, "kp_cap above 16,777,215");
+    const StereoStep step{mb, mbf, d_uright, d_depth};
+    std::vector<orb_frame*> F((size_t)npairs, nullptr);
+    const int st = frames_from_extract(fn, c, dist, npairs, d_desc, d_kps_raw, d_counts, 0, kp_cap, nullptr, min_x, min_y,
+                                       inv_w, inv_h, F.data(), nullptr, &step);
+    if (st == ORB_OK)
+        for (int p = 0; p < npairs; p++) out[p] = F[p];
+    return st;
 }
 
 }  // extern "C"

@@ -97,12 +97,22 @@ struct RgbdStep {
     float* d_depth;
 };
 
+// Frame::ComputeStereoMatches in the same place (stereo.hip): the batch then holds (left, right) slot pairs, frame p of
+// the call is slot 2 p, and the search reads the images and pyramids of the context's last batch.  mvuRight / mvDepth
+// of the pairs go to d_uright / d_depth (nframes * kp_cap floats each; nullptr: working space).
+struct StereoStep {
+    float mb, mbf;
+    float* d_uright;
+    float* d_depth;
+};
+
 // The creators of resident frames from extraction slots: orb_frame_create_from_extract (d_counts nullptr, one frame of
-// n_single keypoints, d_uright optional), orb_frames_create_from_batch and, with rgbd, orb_frames_create_from_batch_rgbd
-// (every handle's uright is then the depth launch's).  Arguments are checked by the caller.
+// n_single keypoints, d_uright optional), orb_frames_create_from_batch and, with rgbd or stereo,
+// orb_frames_create_from_batch_rgbd / _stereo (every handle's uright is then that step's).  With stereo the frames are
+// the batch's even slots (a frame stride of two).  Arguments are checked by the caller.
 int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int nframes, const uint8_t* d_desc,
                         const orb_keypoint* d_raw, const int* d_counts, int n_single, int kp_cap, const float* d_uright,
                         float min_x, float min_y, float inv_w, float inv_h, orb_frame** out,
-                        const RgbdStep* rgbd = nullptr);
+                        const RgbdStep* rgbd = nullptr, const StereoStep* stereo = nullptr);
 
 }  // namespace orbgpu

@@ -36,20 +36,22 @@ void undistort_point_host(const Distortion& D, float x, float y, uint32_t& ox, u
 }
 
 // One lane per keypoint, frame blockIdx.y of a batch laid out as orb_extract_batch_device's outputs (frame f's records
-// at f * kp_cap, its count in counts[f]; counts == NULL: one frame of n_single).  The record is read as 7 dwords and
-// written with x, y replaced; out may be kps (a lane reads its record before it writes it and touches no other).
+// in slot f * in_step, at kp_cap records per slot, its count in counts[f * in_step]; counts == NULL: one frame of
+// n_single).  The record is read as 7 dwords and written to out's slot f with x, y replaced; with in_step 1 out may be
+// kps (a lane reads its record before it writes it and touches no other).
 // Slots past a frame's count are not touched.  f64 throughout: the kernel is launch-bound (a few thousand lanes).
 __global__ __launch_bounds__(kUndistortThreads) void k_undistort_fisheye(Distortion D, double g, const orb_keypoint* kps,
                                                                         const int* counts, int n_single, int kp_cap,
-                                                                        orb_keypoint* out, int* redo_count,
+                                                                        int in_step, orb_keypoint* out, int* redo_count,
                                                                         UndistortRedo* redo) {
     const int f = blockIdx.y;
-    int n = counts ? counts[f] : n_single;
+    const size_t slot = (size_t)f * (size_t)in_step;
+    int n = counts ? counts[slot] : n_single;
     if (n > kp_cap) n = kp_cap;   // (the host refuses such a count once it has read it)
     const int i = blockIdx.x * kUndistortThreads + threadIdx.x;
     if (i >= n) return;
     const size_t r = (size_t)f * (size_t)kp_cap + (size_t)i;
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(kps + r);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(kps + slot * (size_t)kp_cap + (size_t)i);
     uint32_t w[7];
 #pragma unroll
     for (int k = 0; k < 7; k++) w[k] = src[k];
@@ -64,8 +66,8 @@ __global__ __launch_bounds__(kUndistortThreads) void k_undistort_fisheye(Distort
             undistort_project(D, t, scale * (1.0 - g), lx, ly);
             undistort_project(D, t, scale * (1.0 + g), hx, hy);
             if (lx != w[0] || hx != w[0] || ly != w[1] || hy != w[1]) {
-                const int slot = atomicAdd(redo_count, 1);   // < nframes * kp_cap: a point appends once
-                redo[slot] = UndistortRedo{(int)r, rx, ry};
+                const int at = atomicAdd(redo_count, 1);   // < nframes * kp_cap: a point appends once
+                redo[at] = UndistortRedo{(int)r, rx, ry};
             }
         }
     }
@@ -117,14 +119,15 @@ double guard_of(const Ctx* c) { return c->undistort_guard > 0.0 ? c->undistort_g
 
 // The counter cleared and the kernel queued (nframes >= 1, kp_cap >= 1)
 hipError_t launch_undistort(const Distortion& D, double g, const orb_keypoint* d_in, const int* d_counts, int n_single,
-                            int nframes, int kp_cap, orb_keypoint* d_out, int* d_cnt, UndistortRedo* d_list,
-                            hipStream_t stream) {
+                            int nframes, int kp_cap, int in_step, orb_keypoint* d_out, int* d_cnt,
+                            UndistortRedo* d_list, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(d_cnt, 0, 4, stream);
     if (e != hipSuccess) return e;
     const int width = d_counts ? kp_cap : n_single;
     if (width <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_undistort_fisheye, dim3((width + kUndistortThreads - 1) / kUndistortThreads, nframes),
-                       dim3(kUndistortThreads), 0, stream, D, g, d_in, d_counts, n_single, kp_cap, d_out, d_cnt, d_list);
+                       dim3(kUndistortThreads), 0, stream, D, g, d_in, d_counts, n_single, kp_cap, in_step, d_out, d_cnt,
+                       d_list);
     return hipGetLastError();
 }
 
@@ -157,7 +160,7 @@ int undistort_device(const char* fn, Ctx* c, const Distortion& D, int nframes, c
                      UndistortRedo* d_list, int* n_redone) {
     hipError_t e;
     int cnt = 0;
-    if ((e = launch_undistort(D, guard_of(c), d_in, d_counts, n_single, nframes, kp_cap, d_out, d_cnt, d_list,
+    if ((e = launch_undistort(D, guard_of(c), d_in, d_counts, n_single, nframes, kp_cap, 1, d_out, d_cnt, d_list,
                               c->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess)
@@ -183,20 +186,25 @@ int undistort_device(const char* fn, Ctx* c, const Distortion& D, int nframes, c
 }  // namespace
 
 // orb_frame_create_from_extract (d_counts NULL, one frame of n_single keypoints, d_uright optional),
-// orb_frames_create_from_batch and orb_frames_create_from_batch_rgbd (rgbd: the depth launch runs on the patched
-// undistorted records, before any grid).  The stream is synchronised three times at the most: after the undistort launch (the
-// counts and the number of points to recompute), after the keypoints and the redo list have come to the host, and
-// after the copies into the handles and the grid launches.
+// orb_frames_create_from_batch, orb_frames_create_from_batch_rgbd (rgbd: the depth launch runs on the patched
+// undistorted records, before any grid) and orb_frames_create_from_batch_stereo (stereo: frame f is slot 2 f of the
+// batch, slot 2 f + 1 its right image; the search runs on the raw records in the same place).  The stream is
+// synchronised three times at the most: after the undistort launch (the counts and the number of points to recompute),
+// after the keypoints and the redo list have come to the host, and after the copies into the handles and the grid
+// launches.
 int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int nframes, const uint8_t* d_desc,
                         const orb_keypoint* d_raw, const int* d_counts, int n_single, int kp_cap, const float* d_uright,
-                        float min_x, float min_y, float inv_w, float inv_h, orb_frame** out, const RgbdStep* rgbd) {
+                        float min_x, float min_y, float inv_w, float inv_h, orb_frame** out, const RgbdStep* rgbd,
+                        const StereoStep* stereo) {
     const bool batch = d_counts != nullptr;
+    const int step = stereo ? 2 : 1;   // slots per frame
     CTX_GUARD(c);
     const Distortion D = widen(*dist);
     const size_t total = (size_t)nframes * (size_t)kp_cap;
     hipError_t e = hipSuccess;
     std::vector<orb_frame*> F((size_t)nframes, nullptr);
     std::vector<int> counts((size_t)nframes, n_single);
+    std::vector<int> slot_counts;   // stereo: the counts of all 2 * nframes slots
     std::vector<UndistortRedo> list;
     auto fail = [&](const char* what, int st) {
         set_error(what, e);
@@ -207,7 +215,11 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
     // the arena: the undistorted records, the redo counter and list, and every frame's k_frame_grid working space
     Arena a{c};
     if ((e = a.reserve(Arena::align(total * sizeof(orb_keypoint)) + Arena::align(total * sizeof(UndistortRedo)) +
-                       Arena::align(2 * total * 4 + 256 * (size_t)nframes) + (rgbd ? 2 * Arena::align(total * 4) : 0) +
+                       Arena::align(2 * total * 4 + 256 * (size_t)nframes) +
+                       (rgbd || stereo ? 2 * Arena::align(total * 4) : 0) +
+                       (stereo ? Arena::align(stereo_scratch_ints(c->geom, nframes, kp_cap) * 4) +
+                                     Arena::align((size_t)nframes * 4)
+                               : 0) +
                        2048)) != hipSuccess)
         return fail("scratch", ORB_ERR_NOMEM);
     orb_keypoint* d_un = a.take<orb_keypoint>(total);
@@ -222,11 +234,22 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
         d_rgbd_depth = rgbd->d_depth ? rgbd->d_depth : a.take<float>(total);
         d_ur_all = d_rgbd_ur;
     }
+    float* d_st_depth = nullptr;
+    int *d_st_work = nullptr, *d_st_matched = nullptr;
+    if (stereo) {
+        d_rgbd_ur = stereo->d_uright ? stereo->d_uright : a.take<float>(total);
+        d_st_depth = stereo->d_depth ? stereo->d_depth : a.take<float>(total);
+        d_st_work = a.take<int>(stereo_scratch_ints(c->geom, nframes, kp_cap));
+        d_st_matched = a.take<int>((size_t)nframes);
+        d_ur_all = d_rgbd_ur;
+        slot_counts.assign((size_t)nframes * 2, 0);
+    }
+    int* const counts_down = stereo ? slot_counts.data() : counts.data();
     int cnt = 0;
-    if ((e = launch_undistort(D, guard_of(c), d_raw, d_counts, n_single, nframes, kp_cap, d_un, d_cnt, d_list,
+    if ((e = launch_undistort(D, guard_of(c), d_raw, d_counts, n_single, nframes, kp_cap, step, d_un, d_cnt, d_list,
                               c->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-        (batch && (e = hipMemcpyAsync(counts.data(), d_counts, (size_t)nframes * 4, hipMemcpyDeviceToHost,
+        (batch && (e = hipMemcpyAsync(counts_down, d_counts, (size_t)nframes * step * 4, hipMemcpyDeviceToHost,
                                       c->stream)) != hipSuccess))
         return fail("k_undistort_fisheye", ORB_ERR_HIP);
     // the handles, as orb_frame_create_device lays them out; the single form knows its count before the first
@@ -278,6 +301,11 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
         e = hipSuccess;
         return fail((std::string(fn) + ": redo count out of range").c_str(), ORB_ERR_INTERNAL);
     }
+    for (int f = 0; stereo && f < nframes; f++) {
+        counts[f] = slot_counts[2 * f];
+        // (the search sorts the right keypoints into kp_cap slots: a right count above them is refused as a left one is)
+        if (slot_counts[2 * f + 1] < 0 || slot_counts[2 * f + 1] > kp_cap) counts[f] = -1;
+    }
     if (batch && (st = make_frames()) != ORB_OK) return st;
     if (cnt > 0) {
         list.resize((size_t)cnt);
@@ -304,12 +332,24 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
     if (rgbd && (e = launch_rgbd_depth(rgbd->map, rgbd->mbf, nframes, d_raw, d_un, d_counts, kp_cap, d_rgbd_ur,
                                        d_rgbd_depth, nullptr, c->stream)) != hipSuccess)
         return fail("k_rgbd_depth", ORB_ERR_HIP);
+    // ComputeStereoMatches on the raw records of the slot pairs, over the images and pyramids of the context's last batch
+    if (stereo) {
+        const StereoSide SL{c->last_frames, c->last_frame_pitch, c->last_row_stride, c->d_pyr.get(), 0, 2, d_raw, d_desc,
+                            d_counts, kp_cap};
+        StereoSide SR = SL;
+        SR.frame0 = 1;
+        if (c->prof_on) Ctx::marker(c, ORB_K_STEREO, 1, c->stream);
+        e = launch_stereo(c->d_geom.get(), c->geom, SL, SR, nframes, stereo->mb, stereo->mbf, d_rgbd_ur, d_st_depth,
+                          d_st_work, kp_cap, d_st_matched, c->stream);
+        if (c->prof_on) Ctx::marker(c, ORB_K_STEREO, 0, c->stream);
+        if (e != hipSuccess) return fail("stereo kernels", ORB_ERR_HIP);
+    }
     for (int f = 0; f < nframes; f++) {
         orb_frame* H = F[f];
         const size_t nn = (size_t)H->n;
         int* d_work = a.take<int>(2 * nn);
         if (nn > 0 &&
-            ((e = hipMemcpyAsync(H->d_base.get(), d_desc + (size_t)f * kp_cap * 32, nn * 32, hipMemcpyDeviceToDevice,
+            ((e = hipMemcpyAsync(H->d_base.get(), d_desc + (size_t)f * step * kp_cap * 32, nn * 32, hipMemcpyDeviceToDevice,
                                  c->stream)) != hipSuccess ||
              (e = hipMemcpyAsync(const_cast<orb_keypoint*>(H->d_kps), d_un + (size_t)f * kp_cap,
                                  nn * sizeof(orb_keypoint), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess ||

@@ -76,15 +76,20 @@ ORBextractor::~ORBextractor() {
     if (ctx_) orb_destroy(ctx_);
 }
 
-int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color) {
-    const int cap = orb_batch_kp_cap(ctx_, cols, rows);   // exact upper bound for this image size
+int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color, const orb_rectify* rect) {
+    int ow = cols, oh = rows;   // the extracted image's size: the maps' for a raw image
+    if (rect) check(orb_rectify_size(rect, &ow, &oh), "orb_rectify_size");
+    const int cap = orb_batch_kp_cap(ctx_, ow, oh);   // exact upper bound for this image size
     if (cap < 0) throw OrbGpuError(cap, "orb_batch_kp_cap");
     if ((int)kbuf_.size() < cap) {
         kbuf_.resize(cap);
         dbuf_.resize((size_t)cap * 32);
     }
     int n = 0;
-    if (color < 0)
+    if (rect)
+        check(orb_extract_rectified(ctx_, rect, data, cols, rows, step, kbuf_.data(), (int)kbuf_.size(), &n, dbuf_.data()),
+              "orb_extract_rectified");
+    else if (color < 0)
         check(orb_extract(ctx_, data, cols, rows, step, kbuf_.data(), (int)kbuf_.size(), &n, dbuf_.data()),
               "orb_extract");
     else
@@ -111,6 +116,22 @@ void ORBextractor::operator()(const ColorImageView& image, const ImageView& /*ma
                               DescriptorMat& descriptors) {
     if (image.empty()) return;   // ORBextractor.cc:1046-1047
     const int n = extract_raw(image.data, image.cols, image.rows, image.step, image.code);
+    if (n == 0)
+        descriptors.release();
+    else
+        descriptors.create(n);
+    keypoints.assign(kbuf_.begin(), kbuf_.begin() + n);
+    if (n) memcpy(descriptors.buf.data(), dbuf_.data(), (size_t)n * 32);
+}
+
+void ORBextractor::operator()(const ImageView& rawImage, const orb_rectify* rectify, const ImageView& /*mask*/,
+                              std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors) {
+    if (rawImage.empty()) return;   // ORBextractor.cc:1046-1047
+    if (!rectify) throw std::invalid_argument("ORBextractor: rectify NULL");
+    int ow = 0, oh = 0;
+    check(orb_rectify_size(rectify, &ow, &oh), "orb_rectify_size");
+    if (ow == 0 || oh == 0) return;   // (an empty map gives an empty rectified image)
+    const int n = extract_raw(rawImage.data, rawImage.cols, rawImage.rows, rawImage.step, -1, rectify);
     if (n == 0)
         descriptors.release();
     else

@@ -142,6 +142,12 @@ public:
     void operator()(const ColorImageView& image, const ImageView& mask, std::vector<KeyPoint>& keypoints,
                     DescriptorMat& descriptors);
 
+    // The same for a stereo camera's RAW gray image: the cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) of the stereo
+    // examples (stereo_euroc.cc:136-137) runs on the GPU in front of the extraction (orb_extract_rectified; rectify is
+    // one eye's handle of a Rectifier, host/Rectifier.h), and mvImagePyramid[0] is then imRect, of the maps' size.
+    void operator()(const ImageView& rawImage, const orb_rectify* rectify, const ImageView& mask,
+                    std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors);
+
     int inline GetLevels() { return nlevels; }
     float inline GetScaleFactor() { return (float)scaleFactor; }
     std::vector<float> inline GetScaleFactors() { return mvScaleFactor; }
@@ -171,8 +177,10 @@ protected:
 private:
     friend class ImagePyramid;
     void init(int device, int variant);
-    // returns #keypoints in kbuf_/dbuf_; color < 0: a gray image, else its ORB_COLOR_* code
-    int extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color = -1);
+    // returns #keypoints in kbuf_/dbuf_; color < 0: a gray image, else its ORB_COLOR_* code; rect: a raw gray image
+    // to rectify first
+    int extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color = -1,
+                    const orb_rectify* rect = nullptr);
     orb_ctx* ctx_ = nullptr;
     std::vector<KeyPoint> kbuf_;
     std::vector<uint8_t> dbuf_;

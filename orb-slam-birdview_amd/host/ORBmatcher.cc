@@ -262,6 +262,26 @@ std::vector<ResidentFrame> ResidentFrame::FromBatchRGBD(orb_ctx* ctx, const orb_
     return out;
 }
 
+std::vector<ResidentFrame> ResidentFrame::FromBatchStereo(orb_ctx* ctx, const orb_distortion& dist, int npairs, float mb,
+                                                          float mbf, const uint8_t* d_descriptors,
+                                                          const KeyPoint* d_keysRaw, const int* d_counts, int kp_cap,
+                                                          float minX, float maxX, float minY, float maxY,
+                                                          float* d_uRight, float* d_depth) {
+    const float invW = static_cast<float>(ORBGPU_FRAME_GRID_COLS) / static_cast<float>(maxX - minX);
+    const float invH = static_cast<float>(ORBGPU_FRAME_GRID_ROWS) / static_cast<float>(maxY - minY);
+    std::vector<orb_frame*> h((size_t)std::max(npairs, 0), nullptr);
+    std::vector<ResidentFrame> out(h.size());   // (allocated before the handles exist: nothing can throw after)
+    check(orb_frames_create_from_batch_stereo(ctx, &dist, npairs, mb, mbf, d_descriptors, d_keysRaw, d_counts, kp_cap,
+                                              minX, minY, invW, invH, d_uRight, d_depth, h.data()),
+          "ResidentFrame::FromBatchStereo");
+    for (size_t f = 0; f < h.size(); f++) {
+        out[f].h_ = h[f];
+        out[f].n_ = orb_frame_count(h[f]);
+        out[f].hasURight_ = true;
+    }
+    return out;
+}
+
 namespace {
 orb_distortion distortion_of(float fx, float fy, float cx, float cy, const float distCoef[4]) {
     orb_distortion d;

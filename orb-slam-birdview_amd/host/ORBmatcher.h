@@ -112,6 +112,14 @@ public:
                                                     const KeyPoint* d_keysRaw, const int* d_counts, int kp_cap,
                                                     float minX, float maxX, float minY, float maxY, float* d_uRight,
                                                     float* d_depth);
+    // the stereo Frame constructor after extraction (Frame.cc:129-141) for a batch of 2 * npairs frames extracted on
+    // ctx (slots 2p, 2p + 1 = left, right): UndistortKeyPoints of the left keypoints, Frame::ComputeStereoMatches on
+    // the raw ones, the left frames' grids (orb_frames_create_from_batch_stereo).  d_uRight / d_depth (npairs * kp_cap
+    // floats each, device memory, either may be NULL) receive mvuRight / mvDepth; every frame carries its uRight.
+    static std::vector<ResidentFrame> FromBatchStereo(orb_ctx* ctx, const orb_distortion& dist, int npairs, float mb,
+                                                      float mbf, const uint8_t* d_descriptors, const KeyPoint* d_keysRaw,
+                                                      const int* d_counts, int kp_cap, float minX, float maxX,
+                                                      float minY, float maxY, float* d_uRight, float* d_depth);
     ~ResidentFrame();
     ResidentFrame(ResidentFrame&& o) noexcept;
     ResidentFrame& operator=(ResidentFrame&& o) noexcept;

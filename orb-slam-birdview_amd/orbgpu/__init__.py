@@ -18,7 +18,7 @@ __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError
            "features_in_area", "frame_grid", "Frame", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
            "PROJ_GATE_NONE", "PROJ_GATE_FUSE", "proj_queries", "project_best_host",
            "COLOR_RGB", "COLOR_BGR", "COLOR_RGBA", "COLOR_BGRA", "DEPTH_U16", "DEPTH_F32", "to_gray_host", "depth_map",
-           "stereo_from_rgbd_host", "distortion", "undistort_points_host", "image_bounds", "undistort_keypoints", "undistort_guard",
+           "stereo_from_rgbd_host", "remap_host", "rectify_maps_host", "remap_device", "Rectifier", "distortion", "undistort_points_host", "image_bounds", "undistort_keypoints", "undistort_guard",
            "MapPoints", "POINT_PROJ_DTYPE", "FRUSTUM_FRAME", "FRUSTUM_FUSE", "camera", "project_points_host",
            "compute_stereo_matches", "ORBVocabulary", "KeyFrameDatabase", "bow_score", "KFDB_RELOC", "KFDB_LOOP",
            "BirdORB", "cornerSubPix",
@@ -103,6 +103,98 @@ def stereo_from_rgbd_host(depth_image, factor, kps, kps_un, mbf):
     check(lib().orb_stereo_from_rgbd_host(ctypes.byref(m), float(np.float32(mbf)), len(k), _p(k), _p(ku), _p(ur), _p(dep),
                                           ctypes.byref(nv)), "orb_stereo_from_rgbd_host")
     return ur, dep, nv.value
+
+
+def _gray_image(image):
+    """An H x W uint8 array with unit-stride pixels (rows may be padded), as the gray entry points take it."""
+    img = np.asarray(image)
+    assert img.dtype == np.uint8 and img.ndim == 2, "CV_8UC1 expected"
+    if not (img.strides[1] == 1 and img.strides[0] >= img.shape[1]):
+        img = np.ascontiguousarray(img)
+    return img
+
+
+def _float_maps(map_x, map_y):
+    mx, my = np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32)
+    assert mx.ndim == 2 and mx.shape == my.shape, "two H x W float32 maps expected"
+    return mx, my
+
+
+def remap_host(image, map_x, map_y):
+    """orb_remap_host: cv::remap(image, out, map_x, map_y, INTER_LINEAR) with BORDER_CONSTANT 0 as OpenCV 3.2 computes
+    it for 8-bit one-channel images and CV_32FC1 maps, on the CPU (the definition the GPU forms equal byte for byte).
+    The result has the maps' size.  No context, no GPU."""
+    img = _gray_image(image)
+    mx, my = _float_maps(map_x, map_y)
+    dh, dw = mx.shape
+    out = np.zeros((dh, dw), np.uint8)
+    check(lib().orb_remap_host(_p(img), img.shape[1], img.shape[0], img.strides[0], _p(mx), _p(my), dw * 4, dw, dh,
+                               _p(out), dw), "orb_remap_host")
+    return out
+
+
+def rectify_maps_host(K, D, R, P, size):
+    """orb_rectify_maps_host: cv::initUndistortRectifyMap(K, D, R, P, size, CV_32F) of OpenCV 3.2, on the CPU.  K, R: 3 x 3;
+    P: 3 x 3 or 3 x 4 (its left 3 x 3 is read); D: 4, 5 or 8 coefficients; size = (width, height).  Returns (map_x,
+    map_y), float32 of shape (height, width).  A caller that has OpenCV may pass its own maps to Rectifier instead."""
+    K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
+    R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(3, 3))
+    P33 = np.ascontiguousarray(np.asarray(P, np.float64).reshape(3, -1)[:, :3])
+    D = np.ascontiguousarray(np.asarray(D, np.float64).ravel())
+    w, h = int(size[0]), int(size[1])
+    mx, my = np.zeros((max(h, 0), max(w, 0)), np.float32), np.zeros((max(h, 0), max(w, 0)), np.float32)
+    check(lib().orb_rectify_maps_host(_p(K), _p(D), len(D), _p(R), _p(P33), w, h, _p(mx), _p(my), w * 4),
+          "orb_rectify_maps_host")
+    return mx, my
+
+
+def remap_device(ctx_or_matcher, rectifiers, d_src, nframes, sw, sh, src_frame_pitch, src_row_stride, d_dst,
+                 dst_frame_pitch, dst_row_stride):
+    """orb_remap_device: nframes frames in device memory through rectifiers[f % len(rectifiers)] in one launch,
+    asynchronous on the context's stream (one Rectifier: a mono camera; two: interleaved left / right frames)."""
+    hs = (ctypes.c_void_p * len(rectifiers))(*[r.h for r in rectifiers])
+    check(lib().orb_remap_device(_ctx_handle(ctx_or_matcher), len(rectifiers), hs, d_src, nframes, sw, sh,
+                                 src_frame_pitch, src_row_stride, d_dst, dst_frame_pitch, dst_row_stride),
+          "orb_remap_device")
+
+
+class Rectifier:
+    """orb_rectify: one camera's rectification maps resident on the device, built once per camera from the CV_32FC1
+    maps of cv::initUndistortRectifyMap (or rectify_maps_host).  remap(image) / rectifier(image) is cv::remap(image, out,
+    M1, M2, cv::INTER_LINEAR) on the GPU (orb_remap).  Close it before the context that created it."""
+
+    def __init__(self, ctx_or_matcher, map_x, map_y):
+        mx, my = _float_maps(map_x, map_y)
+        self._ctx = ctx_or_matcher
+        self.h = ctypes.c_void_p()
+        dh, dw = mx.shape
+        check(lib().orb_rectify_create(_ctx_handle(ctx_or_matcher), dw, dh, _p(mx), _p(my), dw * 4,
+                                       ctypes.byref(self.h)), "orb_rectify_create")
+
+    @property
+    def size(self):
+        """(width, height) of the maps, which is the rectified image's."""
+        w, h = ctypes.c_int(), ctypes.c_int()
+        check(lib().orb_rectify_size(self.h, ctypes.byref(w), ctypes.byref(h)), "orb_rectify_size")
+        return w.value, h.value
+
+    def remap(self, image, ctx_or_matcher=None):
+        img = _gray_image(image)
+        dw, dh = self.size
+        out = np.zeros((dh, dw), np.uint8)
+        check(lib().orb_remap(_ctx_handle(ctx_or_matcher or self._ctx), self.h, _p(img), img.shape[1], img.shape[0],
+                              img.strides[0], _p(out), dw), "orb_remap")
+        return out
+
+    __call__ = remap
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().orb_rectify_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
 
 
 def device_count():
@@ -199,16 +291,19 @@ class ORBextractor(_Ctx):
     def umax(self):
         return self._umax.copy()
 
-    def __call__(self, image, mask=None, keypoints=None, descriptors=None, color=None):
+    def __call__(self, image, mask=None, keypoints=None, descriptors=None, color=None, rectify=None):
         """operator()(image, mask, keypoints, descriptors): returns (keypoints, descriptors).
 
         An empty image returns the given outputs untouched (ORBextractor.cc:1046-1047); mask is
         ignored as in the reference (ORBextractor.h:58).  color=COLOR_*: image is the camera's H x W x 3 / 4 colour
         image; the cvtColor of Tracking::GrabImage* runs on the GPU in front of the extraction (orb_extract_color) and
-        mvImagePyramid[0] is then mImGray."""
+        mvImagePyramid[0] is then mImGray.  rectify=Rectifier: image is the camera's raw gray image; the cv::remap of the
+        stereo examples runs on the GPU in front of the extraction (orb_extract_rectified) and mvImagePyramid[0] is then
+        the rectified image."""
         img = np.asarray(image)
         if img.size == 0:
             return keypoints, descriptors
+        assert color is None or rectify is None, "a colour image is converted before it is rectified"
         if color is None:
             assert img.dtype == np.uint8 and img.ndim == 2, "CV_8UC1 expected (ORBextractor.cc:1050)"
             if not (img.strides[1] == 1 and img.strides[0] >= img.shape[1]):   # rows with padding go down as they are
@@ -221,7 +316,10 @@ class ORBextractor(_Ctx):
             kps = np.zeros(cap, KP_DTYPE)
             desc = np.zeros((cap, 32), np.uint8)
             n = ctypes.c_int(0)
-            if color is None:
+            if rectify is not None:
+                st = lib().orb_extract_rectified(self.h, rectify.h, _p(img), w, h, img.strides[0], _p(kps), cap,
+                                                 ctypes.byref(n), _p(desc))
+            elif color is None:
                 st = lib().orb_extract(self.h, _p(img), w, h, img.strides[0], _p(kps), cap, ctypes.byref(n),
                                        _p(desc))
             else:
@@ -230,9 +328,10 @@ class ORBextractor(_Ctx):
             if st == -3:
                 cap = n.value
                 continue
-            check(st, "orb_extract" if color is None else "orb_extract_color")
+            check(st, "orb_extract_rectified" if rectify is not None else
+                  "orb_extract" if color is None else "orb_extract_color")
             break
-        self._last_shape = (h, w)
+        self._last_shape = (h, w) if rectify is None else rectify.size[::-1]
         return kps[:n.value].copy(), desc[:n.value].copy()
 
     @property
@@ -291,6 +390,24 @@ class BatchExtractor(_Ctx):
         check(lib().orb_to_gray_device(self.h, color, self.d_color, self.batch, self.w, self.hgt,
                                        self.w * self.hgt * ch, self.w * ch, self.d_frames, self.w * self.hgt, self.w),
               "orb_to_gray_device")
+
+    def upload_raw(self, frames, rectifiers):
+        """The batch as the cameras' raw gray frames ((batch, h, w) uint8, any raw size): uploaded, then rectified on
+        the device into the buffer launch() reads (orb_remap_device, frame f through rectifiers[f % len(rectifiers)];
+        asynchronous on the context's stream, so launch() may follow at once).  The maps have the extractor's size."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        assert frames.ndim == 3 and frames.shape[0] == self.batch
+        assert all(r.size == (self.w, self.hgt) for r in rectifiers), "the maps' size is the extractor's"
+        sh, sw = frames.shape[1:]
+        if getattr(self, "d_raw_bytes", 0) < frames.nbytes:
+            if getattr(self, "d_raw", None):
+                lib().orb_device_free(self.h, self.d_raw)
+                self.d_raw = None
+            self.d_raw = self._alloc(frames.nbytes)
+            self.d_raw_bytes = frames.nbytes
+        check(lib().orb_memcpy_h2d(self.h, self.d_raw, _p(frames), frames.nbytes), "h2d")
+        remap_device(self, rectifiers, self.d_raw, self.batch, sw, sh, sw * sh, sw, self.d_frames, self.w * self.hgt,
+                     self.w)
 
     def stereo_from_rgbd(self, dmap, mbf, d_kps_un, d_uright, d_depth, d_nvalid=None, nframes=None):
         """Frame::ComputeStereoFromRGBD for the frames of the last launch, on the device (orb_stereo_from_rgbd_device;
@@ -356,7 +473,7 @@ class BatchExtractor(_Ctx):
 
     def close(self):
         if getattr(self, "h", None):
-            for p in ("d_frames", "d_kps", "d_desc", "d_counts", "d_color"):
+            for p in ("d_frames", "d_kps", "d_desc", "d_counts", "d_color", "d_raw"):
                 if getattr(self, p, None):
                     lib().orb_device_free(self.h, getattr(self, p))
                     setattr(self, p, None)
@@ -517,6 +634,33 @@ class Frame:
                                  handles), fn)
         frames = []
         for f in range(int(nframes)):
+            self = cls.__new__(cls)
+            self.min_xy, self.inv, self.has_uright = proto.min_xy, proto.inv, True
+            self.h = vp(handles[f])
+            self.n = lib().orb_frame_count(self.h)
+            frames.append(self)
+        return frames
+
+    @classmethod
+    def from_batch_stereo(cls, ctx_or_matcher, dist, npairs, mb, mbf, d_desc, d_kps_raw, d_counts, kp_cap, bounds=None,
+                          inv=None, min_xy=(0.0, 0.0), d_uright=None, d_depth=None):
+        """The stereo Frame constructor after extraction for a whole batch (orb_frames_create_from_batch_stereo), after
+        a launch of 2 * npairs frames on the same context (slots 2p, 2p + 1 = left, right): undistortion of the left
+        keypoints, Frame::ComputeStereoMatches on the raw ones, the left frames' grids.  Every Frame carries its uright;
+        d_uright / d_depth (device pointers, npairs * kp_cap floats, optional) receive mvuRight / mvDepth."""
+        proto = cls.__new__(cls)
+        proto.h = None
+        proto._set_grid(bounds, inv, min_xy)
+        vp = ctypes.c_void_p
+        handles = (vp * max(int(npairs), 1))()
+        fn = "orb_frames_create_from_batch_stereo"
+        check(getattr(lib(), fn)(_ctx_handle(ctx_or_matcher), ctypes.byref(dist), int(npairs), float(np.float32(mb)),
+                                 float(np.float32(mbf)), vp(d_desc), vp(d_kps_raw), vp(d_counts), int(kp_cap),
+                                 proto.min_xy[0], proto.min_xy[1], proto.inv[0], proto.inv[1],
+                                 None if d_uright is None else vp(d_uright), None if d_depth is None else vp(d_depth),
+                                 handles), fn)
+        frames = []
+        for f in range(int(npairs)):
             self = cls.__new__(cls)
             self.min_xy, self.inv, self.has_uright = proto.min_xy, proto.inv, True
             self.h = vp(handles[f])

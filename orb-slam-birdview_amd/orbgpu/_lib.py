@@ -162,6 +162,16 @@ SIGNATURES = {
     "orb_stereo_from_rgbd_device": (ci, [vp, ctypes.POINTER(OrbDepthMap), cf, ci, vp, vp, vp, ci, vp, vp, vp]),
     "orb_frames_create_from_batch_rgbd": (ci, [vp, ctypes.POINTER(OrbDistortion), ctypes.POINTER(OrbDepthMap), cf, ci,
                                                vp, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp]),
+    "orb_remap_host": (ci, [vp, ci, ci, csz, vp, vp, csz, ci, ci, vp, csz]),
+    "orb_rectify_maps_host": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, csz]),
+    "orb_rectify_create": (ci, [vp, ci, ci, vp, vp, csz, ctypes.POINTER(vp)]),
+    "orb_rectify_destroy": (None, [vp]),
+    "orb_rectify_size": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "orb_remap_device": (ci, [vp, ci, ctypes.POINTER(vp), vp, ci, ci, ci, csz, csz, vp, csz, csz]),
+    "orb_remap": (ci, [vp, vp, vp, ci, ci, csz, vp, csz]),
+    "orb_extract_rectified": (ci, [vp, vp, vp, ci, ci, csz, vp, ci, ctypes.POINTER(ci), vp]),
+    "orb_frames_create_from_batch_stereo": (ci, [vp, ctypes.POINTER(OrbDistortion), ci, cf, cf, vp, vp, vp, ci, cf, cf,
+                                                 cf, cf, vp, vp, vp]),
     "orb_points_create": (ci, [vp, ci, ctypes.POINTER(vp)]),
     "orb_points_write": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
     "orb_points_capacity": (ci, [vp]),
