@@ -5,7 +5,7 @@
 #include <new>
 
 #include "frame_cell.h"
-#include "orbgpu_ctx.h"
+#include "undistort.h"
 
 namespace orbgpu {
 
@@ -120,6 +120,49 @@ hipError_t launch_frame_grid(const orb_keypoint* d_kps, int n, const ProjGrid& g
     return hipGetLastError();
 }
 
+const char* frame_alloc(Ctx* c, int n, bool has_ur, const ProjGrid& g, orb_frame*& out, hipError_t& e) {
+    out = nullptr;
+    orb_frame* F = new (std::nothrow) orb_frame();
+    if (!F) return "orb_frame";
+    F->device = c->device;
+    F->n = n;
+    F->has_ur = has_ur;
+    F->min_x = g.min_x;
+    F->min_y = g.min_y;
+    F->inv_w = g.inv_w;
+    F->inv_h = g.inv_h;
+    // [desc | kps | uright | cell_off | cell_idx], each region 256-byte aligned
+    const size_t nn = (size_t)n;
+    const size_t o_kps = Arena::align(nn * 32), o_ur = Arena::align(o_kps + nn * sizeof(orb_keypoint)),
+                 o_coff = Arena::align(o_ur + nn * 4), o_cidx = Arena::align(o_coff + (size_t)(kFrameGridCells + 1) * 4);
+    if ((e = F->d_base.ensure(Arena::align(o_cidx + nn * 4))) != hipSuccess) {
+        delete F;
+        return "orb_frame allocation";
+    }
+    const uint8_t* const base = F->d_base.get();
+    F->d_desc = base;
+    F->d_kps = reinterpret_cast<const orb_keypoint*>(base + o_kps);
+    F->d_ur = has_ur ? reinterpret_cast<const float*>(base + o_ur) : nullptr;
+    F->d_coff = reinterpret_cast<const int*>(base + o_coff);
+    F->d_cidx = reinterpret_cast<const int*>(base + o_cidx);
+    try {
+        F->kps.resize(nn);
+    } catch (const std::bad_alloc&) {
+        delete F;
+        return "orb_frame host keypoints";
+    }
+    out = F;
+    return nullptr;
+}
+
+void frame_octaves(orb_frame* F) {   // (orb_fuse_search_points checks them against its camera's nlevels per call)
+    for (int i = 0; i < F->n; i++) {
+        const int o = F->kps[i].octave;
+        F->oct_min = i ? std::min(F->oct_min, o) : o;
+        F->oct_max = i ? std::max(F->oct_max, o) : o;
+    }
+}
+
 namespace {
 
 // Both creators: src_kind says where desc / kps / uright live.  The keypoints come to the host copy (from the host
@@ -129,9 +172,7 @@ int frame_create(const char* fn, Ctx* c, int n, const uint8_t* desc, const orb_k
     if (!out) return arg_error(fn, "out NULL");
     if (n < 0) return arg_error(fn, "n < 0");
     if (n > 0 && (!desc || !kps)) return arg_error(fn, "NULL arrays with n > 0");
-    if (!std::isfinite(inv_w) || !std::isfinite(inv_h) || inv_w <= 0 || inv_h <= 0)
-        return arg_error(fn, "inverse cell size not finite or not positive");
-    if (!std::isfinite(min_x) || !std::isfinite(min_y)) return arg_error(fn, "grid origin not finite");
+    if (const char* why = grid_fault(min_x, min_y, inv_w, inv_h)) return arg_error(fn, why);
     if (src_kind == hipMemcpyHostToDevice)
         for (int i = 0; i < n; i++)
             if (!std::isfinite(kps[i].x) || !std::isfinite(kps[i].y))
@@ -139,19 +180,8 @@ int frame_create(const char* fn, Ctx* c, int n, const uint8_t* desc, const orb_k
     if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return set_error("hipSetDevice", e), ORB_ERR_HIP;
-    orb_frame* F = new (std::nothrow) orb_frame();
-    if (!F) return set_error("orb_frame", hipSuccess), ORB_ERR_NOMEM;
-    F->device = c->device;
-    F->n = n;
-    F->has_ur = uright != nullptr;
-    F->min_x = min_x;
-    F->min_y = min_y;
-    F->inv_w = inv_w;
-    F->inv_h = inv_h;
-    const size_t nn = (size_t)n;
-    const size_t o_desc = 0, o_kps = Arena::align(o_desc + nn * 32), o_ur = Arena::align(o_kps + nn * sizeof(orb_keypoint)),
-                 o_coff = Arena::align(o_ur + nn * 4), o_cidx = Arena::align(o_coff + (size_t)(kFrameGridCells + 1) * 4),
-                 total = Arena::align(o_cidx + nn * 4);
+    const ProjGrid g{min_x, min_y, inv_w, inv_h};
+    orb_frame* F = nullptr;
     auto fail = [&](const char* what, int st) {
         set_error(what, e);
         // copies already queued write into F's allocation and F's host keypoints: they end before either is released
@@ -159,46 +189,33 @@ int frame_create(const char* fn, Ctx* c, int n, const uint8_t* desc, const orb_k
         delete F;
         return st;
     };
-    if ((e = F->d_base.ensure(total)) != hipSuccess) return fail("orb_frame allocation", ORB_ERR_NOMEM);
-    uint8_t* const base = F->d_base.get();
-    F->d_desc = base + o_desc;
-    F->d_kps = reinterpret_cast<const orb_keypoint*>(base + o_kps);
-    F->d_ur = F->has_ur ? reinterpret_cast<const float*>(base + o_ur) : nullptr;
-    F->d_coff = reinterpret_cast<const int*>(base + o_coff);
-    F->d_cidx = reinterpret_cast<const int*>(base + o_cidx);
+    if (const char* what = frame_alloc(c, n, uright != nullptr, g, F, e)) return fail(what, ORB_ERR_NOMEM);
     // k_frame_grid's working space is the context's scratch arena, free again once this call has synchronised.
     // reserve() frees and reallocates the arena when it has to grow (hipFree waits for the device, so queued work that
     // reads the old arena ends first): like every user of the arena this relies on no caller keeping a pointer into it
     // across calls.  That holds for an extraction context too (the device form): the extraction's buffers and the
     // batch outputs are allocations of their own, and only the matcher calls and this one take from the arena.
+    const size_t nn = (size_t)n;
     Arena a{c};
     if ((e = a.reserve(Arena::align(2 * nn * 4) + 512)) != hipSuccess) return fail("scratch", ORB_ERR_NOMEM);
     int* d_work = a.take<int>(2 * nn);
-    try {
-        F->kps.resize(nn);
-    } catch (const std::bad_alloc&) {
-        return fail("orb_frame host keypoints", ORB_ERR_NOMEM);
-    }
     if (n > 0) {
         if (src_kind == hipMemcpyHostToDevice) std::memcpy(F->kps.data(), kps, nn * sizeof(orb_keypoint));
-        if ((e = hipMemcpyAsync(base + o_desc, desc, nn * 32, src_kind, c->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(base + o_kps, kps, nn * sizeof(orb_keypoint), src_kind, c->stream)) != hipSuccess ||
-            (uright && (e = hipMemcpyAsync(base + o_ur, uright, nn * 4, src_kind, c->stream)) != hipSuccess))
+        if ((e = hipMemcpyAsync(const_cast<uint8_t*>(F->d_desc), desc, nn * 32, src_kind, c->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(const_cast<orb_keypoint*>(F->d_kps), kps, nn * sizeof(orb_keypoint), src_kind, c->stream)) !=
+                hipSuccess ||
+            (uright && (e = hipMemcpyAsync(const_cast<float*>(F->d_ur), uright, nn * 4, src_kind, c->stream)) != hipSuccess))
             return fail("orb_frame copy", ORB_ERR_HIP);
         if (src_kind == hipMemcpyDeviceToDevice &&
             (e = hipMemcpyAsync(F->kps.data(), kps, nn * sizeof(orb_keypoint), hipMemcpyDeviceToHost, c->stream)) !=
                 hipSuccess)
             return fail("orb_frame keypoints to the host", ORB_ERR_HIP);
     }
-    if ((e = launch_frame_grid(F->d_kps, n, ProjGrid{min_x, min_y, inv_w, inv_h}, reinterpret_cast<int*>(base + o_coff),
-                               reinterpret_cast<int*>(base + o_cidx), d_work, c->stream)) != hipSuccess)
+    if ((e = launch_frame_grid(F->d_kps, n, g, const_cast<int*>(F->d_coff), const_cast<int*>(F->d_cidx), d_work,
+                               c->stream)) != hipSuccess)
         return fail("k_frame_grid", ORB_ERR_HIP);
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail("orb_frame synchronise", ORB_ERR_HIP);
-    for (int i = 0; i < n; i++) {   // (orb_fuse_search_points checks them against its camera's nlevels per call)
-        const int o = F->kps[i].octave;
-        F->oct_min = i ? std::min(F->oct_min, o) : o;
-        F->oct_max = i ? std::max(F->oct_max, o) : o;
-    }
+    frame_octaves(F);
     *out = F;
     return ORB_OK;
 }

@@ -549,6 +549,127 @@ int Ctx::run_extract(const uint8_t* d_frames, int nframes, long long frame_pitch
     return ORB_OK;
 }
 
+/* ---------------- the host-image path ---------------- */
+int upload_to_arena(Arena& a, const uint8_t* img, size_t row_bytes, int rows, size_t stride, size_t extra,
+                    const char* what_alloc, const char* what_copy, uint8_t** d_img) {
+    hipError_t e;
+    const size_t pitch = pitch64(row_bytes), bytes = pitch * std::max(rows, 1);
+    if ((e = a.reserve(Arena::align(bytes) + extra + 256)) != hipSuccess) return set_error(what_alloc, e), ORB_ERR_NOMEM;
+    *d_img = a.take<uint8_t>(bytes);
+    if (row_bytes > 0 && rows > 0 && (e = hipMemcpy2DAsync(*d_img, pitch, img, stride, row_bytes, rows,
+                                                           hipMemcpyHostToDevice, a.c->stream)) != hipSuccess)
+        return set_error(what_copy, e), ORB_ERR_HIP;
+    return ORB_OK;
+}
+
+constexpr int kUploadBands = 16;   // (h_flags[kUploadBands .. 63]: [63] = the upload kernel's timeout flag)
+
+// im as a gray frame of w x hgt into d_in (rows `pitch` apart), on the context's stream: what the chain then sees is
+// the same whatever the form.  Every allocation of a form comes before its first launch: with the streamed upload the
+// upload kernel polls for the host copy that follows it, so nothing in between may block on the stream (hipHostFree /
+// hipFree do).  streamed: the gray form's streamed upload (colour and raw images always take the plain one).
+static int stage_host_image(Ctx* c, const HostImage& im, int w, int hgt, uint8_t* d_in, size_t pitch, bool streamed) {
+    hipError_t e;
+    int st;
+    uint8_t* d_src;
+    if (im.color >= 0) {
+        // the colour image into the scratch arena, converted into d_in
+        const size_t cbytes = (size_t)w * color_channels(im.color);
+        Arena a{c};
+        if ((st = upload_to_arena(a, im.data, cbytes, hgt, im.stride, 0, "colour staging", "upload colour image", &d_src)) !=
+            ORB_OK)
+            return st;
+        const size_t cpitch = pitch64(cbytes);
+        if ((e = launch_to_gray(im.color, d_src, 1, w, hgt, cpitch * hgt, cpitch, d_in, pitch * hgt, pitch, c->stream)) !=
+            hipSuccess)
+            return set_error("k_to_gray", e), ORB_ERR_HIP;
+    } else if (im.rect) {
+        // the raw image (of its own size) into the scratch arena, remapped into d_in; an empty one reads 0 everywhere
+        Arena a{c};
+        if ((st = upload_to_arena(a, im.data, (size_t)im.w, im.h, im.stride, 0, "raw image staging", "upload raw image",
+                                  &d_src)) != ORB_OK)
+            return st;
+        if ((e = launch_remap(1, &im.rect, d_src, 1, im.w, im.h, 0, pitch64((size_t)im.w), d_in, 0, pitch, c->stream)) !=
+            hipSuccess)
+            return set_error("k_remap", e), ORB_ERR_HIP;
+    } else if (streamed) {
+        const int band_rows = (hgt + kUploadBands - 1) / kUploadBands, nbands = (hgt + band_rows - 1) / band_rows;
+        if ((e = c->h_img.ensure(pitch * hgt)) != hipSuccess) return set_error("pinned image staging", e), ORB_ERR_NOMEM;
+        if (!c->h_flags) {
+            if ((e = c->h_flags.ensure(64)) != hipSuccess) return set_error("pinned upload flags", e), ORB_ERR_NOMEM;
+            std::memset(c->h_flags.get(), 0, 64 * sizeof(uint32_t));
+        }
+        if (++c->upload_seq == 0) c->upload_seq = 1;   // (flags start at 0)
+        // the upload kernel first; the host copy raising the band flags follows, then (the caller's) extraction launches
+        if ((e = launch_upload_stream(c->h_img.get(), c->h_flags.get(), c->upload_seq, d_in, (int)pitch, hgt, nbands,
+                                      band_rows, c->h_flags.get() + 63, c->stream)) != hipSuccess)
+            return set_error("upload kernel", e), ORB_ERR_HIP;
+        // the host half, band by band, each band's flag raised after its bytes (x86 stores are ordered; the release
+        // store keeps the compiler from sinking the copy past it).  Before the extraction launches: the upload kernel
+        // pulls each band over PCIe while the host copies the next
+        for (int b = 0; b < nbands; b++) {
+            const int r0 = b * band_rows, r1 = std::min(hgt, r0 + band_rows);
+            for (int r = r0; r < r1; r++)
+                std::memcpy(c->h_img.get() + (size_t)r * pitch, im.data + (size_t)r * im.stride, (size_t)w);
+            __atomic_store_n(c->h_flags.get() + b, c->upload_seq, __ATOMIC_RELEASE);
+        }
+    } else {
+        // pageable 2-D upload (measured faster than a host copy into pinned staging + one DMA: 0.149 vs 0.168
+        // ms per C3 frame end to end, tools/host_latency; profiles/r03/latency_probe_upload.json)
+        if ((e = hipMemcpy2DAsync(d_in, pitch, im.data, im.stride, w, hgt, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+            return set_error("upload image", e), ORB_ERR_HIP;
+    }
+    return ORB_OK;
+}
+
+int extract_host(Ctx* c, const HostImage& im, orb_keypoint* kps, int cap, int* n, uint8_t* desc) {
+    const int w = im.rect ? im.rect->dw : im.w, hgt = im.rect ? im.rect->dh : im.h;   // the extracted image's size
+    int st = c->ensure_geometry(w, hgt);
+    if (st != ORB_OK) return st;
+    if ((st = c->ensure_frames(1)) != ORB_OK) return st;
+    hipError_t e;
+    const size_t pitch = ((size_t)w + 63) & ~(size_t)63;
+    const int kcap = c->geom.nkpcap;
+    const size_t kbytes = ((size_t)kcap * sizeof(orb_keypoint) + 63) & ~(size_t)63;   // descriptors 64-B aligned
+    const size_t need = 16 + kbytes + (size_t)kcap * 32;
+    if ((e = c->d_in.ensure(pitch * hgt, kGrowFloor)) != hipSuccess) return set_error("device allocation", e), ORB_ERR_NOMEM;
+    // mapped + coherent (fine-grained): k_describe stores the outputs straight into this block and the host reads
+    // them after hipStreamSynchronize, with no D2H copy in between
+    if ((e = c->h_pinned.ensure(need)) != hipSuccess) return set_error("pinned staging", e), ORB_ERR_NOMEM;
+    const bool streamed = c->upload_stream && im.color < 0 && !im.rect;
+    if ((st = stage_host_image(c, im, w, hgt, c->d_in.get(), pitch, streamed)) != ORB_OK) return st;
+    // output block [count | overflow flag | 8 B pad | keypoints | descriptors] in pinned, host-coherent
+    // memory: k_describe writes the keypoints, descriptors and count straight into it (and copies the
+    // octree's overflow flag), so no download follows the kernels
+    uint8_t* hp = c->h_pinned.get();
+    int* hcnt = reinterpret_cast<int*>(hp);
+    orb_keypoint* hk = reinterpret_cast<orb_keypoint*>(hp + 16);
+    uint8_t* hd = hp + 16 + kbytes;
+    st = c->run_extract(c->d_in.get(), 1, (long long)pitch * hgt, (int)pitch, hk, hd, hcnt, kcap, nullptr, true, hcnt + 1);
+    if (st != ORB_OK) return st;
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("extract", e), ORB_ERR_HIP;
+    if (streamed && __atomic_load_n(c->h_flags.get() + 63, __ATOMIC_ACQUIRE)) {
+        c->h_flags.get()[63] = 0;
+        return set_error("streamed image upload timed out", hipSuccess), ORB_ERR_INTERNAL;
+    }
+    if (hcnt[1]) {
+        set_error("octree node table overflow (raise nfeatures capacity)", hipSuccess);
+        return ORB_ERR_INTERNAL;
+    }
+    const int nk = hcnt[0];
+    if (nk > cap || !kps || !desc) {
+        *n = nk;
+        set_error("orb_extract: output capacity too small", hipSuccess);
+        return ORB_ERR_CAPACITY;
+    }
+    if (nk > 0) {
+        std::memcpy(kps, hk, (size_t)nk * sizeof(orb_keypoint));
+        std::memcpy(desc, hd, (size_t)nk * 32);
+    }
+    *n = nk;
+    return ORB_OK;
+}
+
 }  // namespace orbgpu
 
 using namespace orbgpu;
@@ -712,100 +833,7 @@ int orb_extract(orb_ctx* h, const uint8_t* img, int w, int hgt, size_t stride, o
     CTX_GUARD(c);
     if (!img || w <= 0 || hgt <= 0) return ORB_OK;   // _image.empty(): outputs untouched (:1046-1047)
     if (!n || stride < (size_t)w) return set_error("orb_extract: bad arguments", hipSuccess), ORB_ERR_ARG;
-    int st = c->ensure_geometry(w, hgt);
-    if (st != ORB_OK) return st;
-    if ((st = c->ensure_frames(1)) != ORB_OK) return st;
-    hipError_t e;
-    const size_t pitch = ((size_t)w + 63) & ~(size_t)63;
-    const int kcap = c->geom.nkpcap;
-    const size_t kbytes = ((size_t)kcap * sizeof(orb_keypoint) + 63) & ~(size_t)63;   // descriptors 64-B aligned
-    const size_t need = 16 + kbytes + (size_t)kcap * 32;
-    if ((e = c->d_in.ensure(pitch * hgt, kGrowFloor)) != hipSuccess) return set_error("device allocation", e), ORB_ERR_NOMEM;
-    // every allocation before the first launch: with the streamed upload the upload kernel queued below polls for
-    // the host copy that follows it, so nothing in between may block on the stream (hipHostFree / hipFree do)
-    // mapped + coherent (fine-grained): k_describe stores the outputs straight into this block and the host reads
-    // them after hipStreamSynchronize, with no D2H copy in between
-    if ((e = c->h_pinned.ensure(need)) != hipSuccess) return set_error("pinned staging", e), ORB_ERR_NOMEM;
-    // orb_extract_color (rgbd.hip) comes through here with its code in the context: img is then a colour image
-    const int color = c->host_color;
-    // orb_extract_rectified (remap.hip) likewise, with its map: img is then the raw image, w x hgt the maps' size
-    const orb_rectify* const rect = c->host_rect;
-    const bool streamed = c->upload_stream && color < 0 && !rect;   // (those two always take the plain upload)
-    constexpr int kBands = 16;   // (h_flags[kBands .. 63]: [63] = the upload kernel's timeout flag)
-    const int band_rows = (hgt + kBands - 1) / kBands, nbands = (hgt + band_rows - 1) / band_rows;
-    if (color >= 0) {
-        // the colour image into the scratch arena (rows padded to 64 bytes, so k_to_gray's dword path holds for
-        // every row), converted into d_in on the same stream: the chain below sees a gray frame as from the upload
-        const size_t cbytes = (size_t)w * color_channels(color), cpitch = (cbytes + 63) & ~(size_t)63;
-        Arena a{c};
-        if ((e = a.reserve(cpitch * hgt + 256)) != hipSuccess) return set_error("colour staging", e), ORB_ERR_NOMEM;
-        uint8_t* d_color = a.take<uint8_t>(cpitch * hgt);
-        if ((e = hipMemcpy2DAsync(d_color, cpitch, img, stride, cbytes, hgt, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-            return set_error("upload colour image", e), ORB_ERR_HIP;
-        if ((e = launch_to_gray(color, d_color, 1, w, hgt, cpitch * hgt, cpitch, c->d_in.get(), pitch * hgt, pitch,
-                                c->stream)) != hipSuccess)
-            return set_error("k_to_gray", e), ORB_ERR_HIP;
-    } else if (rect) {
-        if ((st = upload_and_remap(c, rect, img, c->host_raw_w, c->host_raw_h, c->host_raw_stride, c->d_in.get(),
-                                   pitch)) != ORB_OK)
-            return st;
-    } else if (streamed) {
-        if ((e = c->h_img.ensure(pitch * hgt)) != hipSuccess) return set_error("pinned image staging", e), ORB_ERR_NOMEM;
-        if (!c->h_flags) {
-            if ((e = c->h_flags.ensure(64)) != hipSuccess) return set_error("pinned upload flags", e), ORB_ERR_NOMEM;
-            std::memset(c->h_flags.get(), 0, 64 * sizeof(uint32_t));
-        }
-        if (++c->upload_seq == 0) c->upload_seq = 1;   // (flags start at 0)
-        // the upload kernel first; the host copy raising the band flags follows (below), then the extraction launches
-        if ((e = launch_upload_stream(c->h_img.get(), c->h_flags.get(), c->upload_seq, c->d_in.get(), (int)pitch, hgt,
-                                      nbands, band_rows, c->h_flags.get() + 63, c->stream)) != hipSuccess)
-            return set_error("upload kernel", e), ORB_ERR_HIP;
-    } else {
-        // pageable 2-D upload (measured faster than a host copy into pinned staging + one DMA: 0.149 vs 0.168
-        // ms per C3 frame end to end, tools/host_latency; profiles/r03/latency_probe_upload.json)
-        if ((e = hipMemcpy2DAsync(c->d_in.get(), pitch, img, stride, w, hgt, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-            return set_error("upload image", e), ORB_ERR_HIP;
-    }
-    // output block [count | overflow flag | 8 B pad | keypoints | descriptors] in pinned, host-coherent
-    // memory: k_describe writes the keypoints, descriptors and count straight into it (and copies the
-    // octree's overflow flag), so no download follows the kernels
-    uint8_t* hp = c->h_pinned.get();
-    int* hcnt = reinterpret_cast<int*>(hp);
-    orb_keypoint* hk = reinterpret_cast<orb_keypoint*>(hp + 16);
-    uint8_t* hd = hp + 16 + kbytes;
-    if (streamed) {
-        // the host half of the streamed upload, band by band, each band's flag raised after its bytes (x86 stores
-        // are ordered; the release store keeps the compiler from sinking the copy past it).  Before the extraction
-        // launches: the upload kernel pulls each band over PCIe while the host copies the next
-        for (int b = 0; b < nbands; b++) {
-            const int r0 = b * band_rows, r1 = std::min(hgt, r0 + band_rows);
-            for (int r = r0; r < r1; r++) std::memcpy(c->h_img.get() + (size_t)r * pitch, img + (size_t)r * stride, (size_t)w);
-            __atomic_store_n(c->h_flags.get() + b, c->upload_seq, __ATOMIC_RELEASE);
-        }
-    }
-    st = c->run_extract(c->d_in.get(), 1, (long long)pitch * hgt, (int)pitch, hk, hd, hcnt, kcap, nullptr, true, hcnt + 1);
-    if (st != ORB_OK) return st;
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("extract", e), ORB_ERR_HIP;
-    if (streamed && __atomic_load_n(c->h_flags.get() + 63, __ATOMIC_ACQUIRE)) {
-        c->h_flags.get()[63] = 0;
-        return set_error("streamed image upload timed out", hipSuccess), ORB_ERR_INTERNAL;
-    }
-    if (hcnt[1]) {
-        set_error("octree node table overflow (raise nfeatures capacity)", hipSuccess);
-        return ORB_ERR_INTERNAL;
-    }
-    const int nk = hcnt[0];
-    if (nk > cap || !kps || !desc) {
-        *n = nk;
-        set_error("orb_extract: output capacity too small", hipSuccess);
-        return ORB_ERR_CAPACITY;
-    }
-    if (nk > 0) {
-        std::memcpy(kps, hk, (size_t)nk * sizeof(orb_keypoint));
-        std::memcpy(desc, hd, (size_t)nk * 32);
-    }
-    *n = nk;
-    return ORB_OK;
+    return extract_host(c, HostImage{img, w, hgt, stride}, kps, cap, n, desc);
 }
 
 static int level_view(Ctx* c, int frame, int level, uint8_t* dst, int* w, int* hgt) {

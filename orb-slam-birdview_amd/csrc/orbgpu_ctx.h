@@ -99,14 +99,8 @@ struct Ctx {
     DevBuf<int> d_lvlCount;
     DevBuf<int> d_err;
 
-    // host-image path (orb_extract)
+    // host-image path (extract_host)
     DevBuf<uint8_t> d_in;
-    // >= 0 only while orb_extract_color runs orb_extract: the ORB_COLOR_* code of the colour image it passes
-    int host_color = -1;
-    // non-NULL only while orb_extract_rectified runs orb_extract: the map, and the raw image's size and stride
-    const orb_rectify* host_rect = nullptr;
-    int host_raw_w = 0, host_raw_h = 0;
-    size_t host_raw_stride = 0;
     // streamed upload (k_upload_stream; off by default, ORBGPU_UPLOAD=1 turns it on; off = the pageable
     // hipMemcpy2DAsync): the image's pinned host-coherent staging copy and the per-band flags the host raises (call
     // sequence numbers)
@@ -114,7 +108,7 @@ struct Ctx {
     MapBuf<uint8_t> h_img;
     MapBuf<uint32_t> h_flags;
     uint32_t upload_seq = 0;
-    // orb_extract's outputs [count | flag | pad | keypoints | descriptors]: host-coherent pinned memory the
+    // extract_host's outputs [count | flag | pad | keypoints | descriptors]: host-coherent pinned memory the
     // kernels write directly (no download)
     MapBuf<uint8_t> h_pinned;
 
@@ -216,6 +210,31 @@ struct Arena {
     }
 };
 
+inline size_t pitch64(size_t row_bytes) { return (std::max<size_t>(row_bytes, 1) + 63) & ~(size_t)63; }
+
+// A host image of `rows` rows of row_bytes bytes into the arena, rows padded to 64 bytes (pitch64: the dword paths of
+// k_to_gray and k_remap then hold for every row), by hipMemcpy2DAsync on the context's stream.  The arena is reserved
+// here, for the image and `extra` bytes the caller takes after it; an empty image uploads nothing.  ORB_OK and d_img,
+// or the status to return, with what_alloc / what_copy as the error text.
+int upload_to_arena(Arena& a, const uint8_t* img, size_t row_bytes, int rows, size_t stride, size_t extra,
+                    const char* what_alloc, const char* what_copy, uint8_t** d_img);
+
+// The image a host-image entry point was given: w x h pixels, rows `stride` bytes apart.  color >= 0: a colour image
+// with that ORB_COLOR_* code, converted to gray on the device; rect: a raw gray image to rectify on the device, the
+// extracted image then has the maps' size.  Neither: the gray image itself.
+struct HostImage {
+    const uint8_t* data;
+    int w, h;
+    size_t stride;
+    int color = -1;
+    const orb_rectify* rect = nullptr;
+};
+
+// orb_extract, orb_extract_color and orb_extract_rectified behind their argument checks (orbgpu_abi.hip): the image
+// staged into Ctx::d_in as a gray frame, the single-frame chain, one synchronisation, the outputs copied out.  The
+// chain sees the same frame whatever the form, so orb_get_level(ctx, 0) is the gray / rectified image.
+int extract_host(Ctx* c, const HostImage& im, orb_keypoint* kps, int cap, int* n, uint8_t* desc);
+
 // A host call's device arena and its pinned host mirror (Ctx::h_mstage): regions are laid out once
 // with add(), inputs are written into the mirror at the device offsets, one DMA takes the input span up
 // (or the kernels read the mirror itself, zc = 1), and the kernels store their outputs straight into the mirror
@@ -292,3 +311,15 @@ struct orb_frame {
     std::vector<orb_keypoint> kps;
     int oct_min = 0, oct_max = -1;   // the octaves of kps, found once by the creator (n > 0)
 };
+
+namespace orbgpu {
+
+// The one place the handle is laid out (frame.hip): F for n keypoints over grid g, its allocation made, the five device
+// pointers set (d_ur only with has_ur), the host keypoint copy sized but not filled.  nullptr, or the step that failed
+// for the caller's fail(what, ORB_ERR_NOMEM), with its HIP error in e; F is then nullptr and nothing is left allocated.
+const char* frame_alloc(Ctx* c, int n, bool has_ur, const ProjGrid& g, orb_frame*& F, hipError_t& e);
+
+// oct_min / oct_max from the host keypoints, once they hold the frame's final records
+void frame_octaves(orb_frame* F);
+
+}  // namespace orbgpu

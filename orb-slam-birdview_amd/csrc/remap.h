@@ -15,11 +15,6 @@ hipError_t launch_remap(int nmaps, const orb_rectify* const* maps, const uint8_t
                         size_t src_frame_pitch, size_t src_row_stride, uint8_t* d_dst, size_t dst_frame_pitch,
                         size_t dst_row_stride, hipStream_t stream);
 
-// orb_extract's upload for orb_extract_rectified: the raw host image into the scratch arena, remapped into d_dst (rows
-// dst_pitch apart) on the context's stream.  ORB_OK or the status to return.
-int upload_and_remap(Ctx* c, const orb_rectify* rect, const uint8_t* img, int sw, int sh, size_t stride, uint8_t* d_dst,
-                     size_t dst_pitch);
-
 }  // namespace orbgpu
 
 // A rectification map resident on the device (the object behind the opaque orb_rectify*): the float maps converted

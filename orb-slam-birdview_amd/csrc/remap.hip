@@ -130,26 +130,7 @@ const char* handles_fault(int nmaps, const orb_rectify* const* maps, const Ctx* 
     return nullptr;
 }
 
-inline size_t pitch64(size_t w) { return (std::max<size_t>(w, 1) + 63) & ~(size_t)63; }
-
 }  // namespace
-
-// The raw image of orb_extract_rectified into the scratch arena (rows padded to 64 bytes), remapped into d_dst on the
-// context's stream: what orb_extract's chain then sees is a gray frame as from its own upload.
-int upload_and_remap(Ctx* c, const orb_rectify* rect, const uint8_t* img, int sw, int sh, size_t stride, uint8_t* d_dst,
-                     size_t dst_pitch) {
-    hipError_t e;
-    const size_t sp = pitch64((size_t)sw);
-    Arena a{c};
-    if ((e = a.reserve(sp * std::max(sh, 1) + 256)) != hipSuccess) return set_error("raw image staging", e), ORB_ERR_NOMEM;
-    uint8_t* d_raw = a.take<uint8_t>(sp * std::max(sh, 1));
-    if (sw > 0 && sh > 0 &&
-        (e = hipMemcpy2DAsync(d_raw, sp, img, stride, sw, sh, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-        return set_error("upload raw image", e), ORB_ERR_HIP;
-    if ((e = launch_remap(1, &rect, d_raw, 1, sw, sh, 0, sp, d_dst, 0, dst_pitch, c->stream)) != hipSuccess)
-        return set_error("k_remap", e), ORB_ERR_HIP;
-    return ORB_OK;
-}
 
 }  // namespace orbgpu
 
@@ -275,14 +256,12 @@ int orb_remap(orb_ctx* h, const orb_rectify* rect, const uint8_t* img, int sw, i
     CTX_GUARD(c);
     hipError_t e;
     const size_t sp = pitch64((size_t)sw), dp = pitch64((size_t)dw);
-    const size_t sbytes = Arena::align(sp * std::max(sh, 1));
     Arena a{c};
-    if ((e = a.reserve(sbytes + dp * dh + 512)) != hipSuccess) return set_error("remap staging", e), ORB_ERR_NOMEM;
-    uint8_t* d_raw = a.take<uint8_t>(sbytes);
+    uint8_t* d_raw;
+    const int st =
+        upload_to_arena(a, img, (size_t)sw, sh, stride, dp * dh + 256, "remap staging", "upload raw image", &d_raw);
+    if (st != ORB_OK) return st;
     uint8_t* d_out = a.take<uint8_t>(dp * dh);
-    if (sw > 0 && sh > 0 &&
-        (e = hipMemcpy2DAsync(d_raw, sp, img, stride, sw, sh, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-        return set_error("upload raw image", e), ORB_ERR_HIP;
     if ((e = launch_remap(1, &rect, d_raw, 1, sw, sh, 0, sp, d_out, 0, dp, c->stream)) != hipSuccess)
         return set_error("k_remap", e), ORB_ERR_HIP;
     if ((e = hipMemcpy2DAsync(dst, dst_stride, d_out, dp, dw, dh, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
@@ -303,15 +282,9 @@ int orb_extract_rectified(orb_ctx* h, const orb_rectify* rect, const uint8_t* im
     // _image.empty(), before or after the remap: outputs untouched (ORBextractor.cc:1046-1047)
     if (!img || sw == 0 || sh == 0 || rect->dw == 0 || rect->dh == 0) return ORB_OK;
     if (!n) return arg_error(fn, "n NULL");
-    // orb_extract's chain with the raw upload and k_remap in place of its gray upload; its image is the rectified one,
-    // of the maps' size (the raw image's own size and stride travel in the context)
-    c->host_rect = rect;
-    c->host_raw_w = sw;
-    c->host_raw_h = sh;
-    c->host_raw_stride = stride;
-    const int st = orb_extract(h, img, rect->dw, rect->dh, (size_t)rect->dw, kps, cap, n, desc);
-    c->host_rect = nullptr;
-    return st;
+    // the single-frame chain with the raw upload and k_remap in place of the gray upload; its image is the rectified
+    // one, of the maps' size
+    return extract_host(c, HostImage{img, sw, sh, stride, -1, rect}, kps, cap, n, desc);
 }
 
 }  // extern "C"

@@ -256,11 +256,8 @@ int orb_extract_color(orb_ctx* h, int code, const uint8_t* img, int w, int hgt, 
     CTX_GUARD(c);
     if (!img || w == 0 || hgt == 0) return ORB_OK;   // _image.empty(): outputs untouched (ORBextractor.cc:1046-1047)
     if (!n) return arg_error(fn, "n NULL");
-    // orb_extract's chain with the colour upload and k_to_gray in place of its gray upload
-    c->host_color = code;
-    const int st = orb_extract(h, img, w, hgt, stride, kps, cap, n, desc);
-    c->host_color = -1;
-    return st;
+    // the single-frame chain with the colour upload and k_to_gray in place of the gray upload
+    return extract_host(c, HostImage{img, w, hgt, stride, code}, kps, cap, n, desc);
 }
 
 int orb_stereo_from_rgbd_host(const orb_depth_map* map, float mbf, int n, const orb_keypoint* kps,
@@ -321,7 +318,7 @@ int orb_frames_create_from_batch_rgbd(orb_ctx* h, const orb_distortion* dist, co
         return arg_error(fn, "NULL arrays with nframes > 0");
     if (const char* why = grid_fault(min_x, min_y, inv_w, inv_h)) return arg_error(fn, why);
     if (nframes == 0) return ORB_OK;
-    const RgbdStep step{*map, mbf, d_uright, d_depth};
+    const DepthStep step{DepthStep::kRgbd, *map, 0.0f, mbf, d_uright, d_depth};
     std::vector<orb_frame*> F((size_t)nframes, nullptr);
     const int st = frames_from_extract(fn, reinterpret_cast<Ctx*>(h), dist, nframes, d_desc, d_kps_raw, d_counts, 0,
                                        kp_cap, nullptr, min_x, min_y, inv_w, inv_h, F.data(), &step);

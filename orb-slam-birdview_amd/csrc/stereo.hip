@@ -484,10 +484,10 @@ int orb_frames_create_from_batch_stereo(orb_ctx* h, const orb_distortion* dist, 
         return arg_error(fn, "the last batch holds fewer than 2 * npairs frames");
     if (c->last_kp_cap != kp_cap) return arg_error(fn, "kp_cap is not the last batch's");
     if (kp_cap > kStereoMaxRight) return arg_error(fn, "kp_cap above 16,777,215");
-    const StereoStep step{mb, mbf, d_uright, d_depth};
+    const DepthStep step{DepthStep::kStereo, orb_depth_map{}, mb, mbf, d_uright, d_depth};
     std::vector<orb_frame*> F((size_t)npairs, nullptr);
     const int st = frames_from_extract(fn, c, dist, npairs, d_desc, d_kps_raw, d_counts, 0, kp_cap, nullptr, min_x, min_y,
-                                       inv_w, inv_h, F.data(), nullptr, &step);
+                                       inv_w, inv_h, F.data(), &step);
     if (st == ORB_OK)
         for (int p = 0; p < npairs; p++) out[p] = F[p];
     return st;

@@ -88,31 +88,28 @@ const char* distortion_fault(const orb_distortion* d);
 const char* grid_fault(float min_x, float min_y, float inv_w, float inv_h);   // orb_frame_create's grid checks
 const char* batch_fault(int nframes, int kp_cap);
 
-// Frame::ComputeStereoFromRGBD between the undistort step and the grids (rgbd.hip): the depth maps (device memory),
-// mbf, and where mvuRight / mvDepth of the batch go (nframes * kp_cap floats each; nullptr: working space)
-struct RgbdStep {
-    orb_depth_map map;
+// The step that gives a batch its mvuRight / mvDepth, between the undistort step and the grids:
+//   kRgbd    Frame::ComputeStereoFromRGBD (rgbd.hip) over the depth maps `map` (device memory) and mbf;
+//   kStereo  Frame::ComputeStereoMatches (stereo.hip) with mb and mbf: the batch then holds (left, right) slot pairs,
+//            frame p of the call is slot 2 p, and the search reads the images and pyramids of the context's last batch.
+// mvuRight / mvDepth go to d_uright / d_depth (nframes * kp_cap floats each; nullptr: working space).
+struct DepthStep {
+    enum Kind { kRgbd, kStereo } kind;
+    orb_depth_map map;   // kRgbd
+    float mb;            // kStereo
     float mbf;
     float* d_uright;
     float* d_depth;
-};
-
-// Frame::ComputeStereoMatches in the same place (stereo.hip): the batch then holds (left, right) slot pairs, frame p of
-// the call is slot 2 p, and the search reads the images and pyramids of the context's last batch.  mvuRight / mvDepth
-// of the pairs go to d_uright / d_depth (nframes * kp_cap floats each; nullptr: working space).
-struct StereoStep {
-    float mb, mbf;
-    float* d_uright;
-    float* d_depth;
+    int slots() const { return kind == kStereo ? 2 : 1; }   // batch slots per frame
 };
 
 // The creators of resident frames from extraction slots: orb_frame_create_from_extract (d_counts nullptr, one frame of
-// n_single keypoints, d_uright optional), orb_frames_create_from_batch and, with rgbd or stereo,
-// orb_frames_create_from_batch_rgbd / _stereo (every handle's uright is then that step's).  With stereo the frames are
-// the batch's even slots (a frame stride of two).  Arguments are checked by the caller.
+// n_single keypoints, d_uright optional), orb_frames_create_from_batch and, with a step,
+// orb_frames_create_from_batch_rgbd / _stereo (every handle's uright is then the step's).  Arguments are checked by the
+// caller.
 int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int nframes, const uint8_t* d_desc,
                         const orb_keypoint* d_raw, const int* d_counts, int n_single, int kp_cap, const float* d_uright,
                         float min_x, float min_y, float inv_w, float inv_h, orb_frame** out,
-                        const RgbdStep* rgbd = nullptr, const StereoStep* stereo = nullptr);
+                        const DepthStep* step = nullptr);
 
 }  // namespace orbgpu

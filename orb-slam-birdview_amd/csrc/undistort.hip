@@ -186,18 +186,19 @@ int undistort_device(const char* fn, Ctx* c, const Distortion& D, int nframes, c
 }  // namespace
 
 // orb_frame_create_from_extract (d_counts NULL, one frame of n_single keypoints, d_uright optional),
-// orb_frames_create_from_batch, orb_frames_create_from_batch_rgbd (rgbd: the depth launch runs on the patched
-// undistorted records, before any grid) and orb_frames_create_from_batch_stereo (stereo: frame f is slot 2 f of the
-// batch, slot 2 f + 1 its right image; the search runs on the raw records in the same place).  The stream is
+// orb_frames_create_from_batch, orb_frames_create_from_batch_rgbd (step kRgbd: the depth launch runs on the patched
+// undistorted records, before any grid) and orb_frames_create_from_batch_stereo (step kStereo: frame f is slot 2 f of
+// the batch, slot 2 f + 1 its right image; the search runs on the raw records in the same place).  The stream is
 // synchronised three times at the most: after the undistort launch (the counts and the number of points to recompute),
 // after the keypoints and the redo list have come to the host, and after the copies into the handles and the grid
 // launches.
 int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int nframes, const uint8_t* d_desc,
                         const orb_keypoint* d_raw, const int* d_counts, int n_single, int kp_cap, const float* d_uright,
-                        float min_x, float min_y, float inv_w, float inv_h, orb_frame** out, const RgbdStep* rgbd,
-                        const StereoStep* stereo) {
+                        float min_x, float min_y, float inv_w, float inv_h, orb_frame** out, const DepthStep* step) {
     const bool batch = d_counts != nullptr;
-    const int step = stereo ? 2 : 1;   // slots per frame
+    const bool stereo = step && step->kind == DepthStep::kStereo;
+    const int slots = step ? step->slots() : 1;   // batch slots per frame
+    const ProjGrid grid{min_x, min_y, inv_w, inv_h};
     CTX_GUARD(c);
     const Distortion D = widen(*dist);
     const size_t total = (size_t)nframes * (size_t)kp_cap;
@@ -212,48 +213,39 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
         for (orb_frame* f : F) orb_frame_destroy(f);
         return st;
     };
-    // the arena: the undistorted records, the redo counter and list, and every frame's k_frame_grid working space
+    // the arena: the undistorted records, the redo counter and list, every frame's k_frame_grid working space, a step's
+    // mvuRight / mvDepth, and the stereo search's working space and match counts
+    const size_t stereo_ints = stereo ? stereo_scratch_ints(c->geom, nframes, kp_cap) : 0;
     Arena a{c};
     if ((e = a.reserve(Arena::align(total * sizeof(orb_keypoint)) + Arena::align(total * sizeof(UndistortRedo)) +
-                       Arena::align(2 * total * 4 + 256 * (size_t)nframes) +
-                       (rgbd || stereo ? 2 * Arena::align(total * 4) : 0) +
-                       (stereo ? Arena::align(stereo_scratch_ints(c->geom, nframes, kp_cap) * 4) +
-                                     Arena::align((size_t)nframes * 4)
-                               : 0) +
-                       2048)) != hipSuccess)
+                       Arena::align(2 * total * 4 + 256 * (size_t)nframes) + (step ? 2 * Arena::align(total * 4) : 0) +
+                       (stereo ? Arena::align(stereo_ints * 4) + Arena::align((size_t)nframes * 4) : 0) + 2048)) !=
+        hipSuccess)
         return fail("scratch", ORB_ERR_NOMEM);
     orb_keypoint* d_un = a.take<orb_keypoint>(total);
     int* d_cnt = a.take<int>(1);
     UndistortRedo* d_list = a.take<UndistortRedo>(total);
-    // mvuRight of the batch, frame f's at f * kp_cap: the caller's (one frame), or the depth launch's output
-    const float* d_ur_all = d_uright;
-    float* d_rgbd_ur = nullptr;
-    float* d_rgbd_depth = nullptr;
-    if (rgbd) {
-        d_rgbd_ur = rgbd->d_uright ? rgbd->d_uright : a.take<float>(total);
-        d_rgbd_depth = rgbd->d_depth ? rgbd->d_depth : a.take<float>(total);
-        d_ur_all = d_rgbd_ur;
-    }
-    float* d_st_depth = nullptr;
-    int *d_st_work = nullptr, *d_st_matched = nullptr;
+    // mvuRight / mvDepth of the batch, frame f's at f * kp_cap: the step's output (the caller's arrays or working
+    // space), or without a step the caller's mvuRight of one frame
+    float* const d_step_ur = !step ? nullptr : step->d_uright ? step->d_uright : a.take<float>(total);
+    float* const d_step_depth = !step ? nullptr : step->d_depth ? step->d_depth : a.take<float>(total);
+    const float* const d_ur_all = step ? d_step_ur : d_uright;
+    int *d_stereo_work = nullptr, *d_stereo_matched = nullptr;
     if (stereo) {
-        d_rgbd_ur = stereo->d_uright ? stereo->d_uright : a.take<float>(total);
-        d_st_depth = stereo->d_depth ? stereo->d_depth : a.take<float>(total);
-        d_st_work = a.take<int>(stereo_scratch_ints(c->geom, nframes, kp_cap));
-        d_st_matched = a.take<int>((size_t)nframes);
-        d_ur_all = d_rgbd_ur;
+        d_stereo_work = a.take<int>(stereo_ints);
+        d_stereo_matched = a.take<int>((size_t)nframes);
         slot_counts.assign((size_t)nframes * 2, 0);
     }
     int* const counts_down = stereo ? slot_counts.data() : counts.data();
     int cnt = 0;
-    if ((e = launch_undistort(D, guard_of(c), d_raw, d_counts, n_single, nframes, kp_cap, step, d_un, d_cnt, d_list,
+    if ((e = launch_undistort(D, guard_of(c), d_raw, d_counts, n_single, nframes, kp_cap, slots, d_un, d_cnt, d_list,
                               c->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-        (batch && (e = hipMemcpyAsync(counts_down, d_counts, (size_t)nframes * step * 4, hipMemcpyDeviceToHost,
+        (batch && (e = hipMemcpyAsync(counts_down, d_counts, (size_t)nframes * slots * 4, hipMemcpyDeviceToHost,
                                       c->stream)) != hipSuccess))
         return fail("k_undistort_fisheye", ORB_ERR_HIP);
-    // the handles, as orb_frame_create_device lays them out; the single form knows its count before the first
-    // synchronisation, so its keypoints come down with the counter
+    // the handles; the single form knows its count before the first synchronisation, so its keypoints come down with
+    // the counter
     auto make_frames = [&]() -> int {
         for (int f = 0; f < nframes; f++) {
             const int n = counts[f];
@@ -261,34 +253,8 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
                 e = hipSuccess;
                 return fail((std::string(fn) + ": a frame's count is negative or above kp_cap").c_str(), ORB_ERR_CAPACITY);
             }
-            orb_frame* H = new (std::nothrow) orb_frame();
-            if (!H) return fail("orb_frame", ORB_ERR_NOMEM);
-            F[f] = H;
-            H->device = c->device;
-            H->n = n;
-            H->has_ur = d_ur_all != nullptr;
-            H->min_x = min_x;
-            H->min_y = min_y;
-            H->inv_w = inv_w;
-            H->inv_h = inv_h;
-            const size_t nn = (size_t)n;
-            const size_t o_kps = Arena::align(nn * 32), o_ur = Arena::align(o_kps + nn * sizeof(orb_keypoint)),
-                         o_coff = Arena::align(o_ur + nn * 4),
-                         o_cidx = Arena::align(o_coff + (size_t)(kFrameGridCells + 1) * 4);
-            if ((e = H->d_base.ensure(Arena::align(o_cidx + nn * 4))) != hipSuccess)
-                return fail("orb_frame allocation", ORB_ERR_NOMEM);
-            uint8_t* const base = H->d_base.get();
-            H->d_desc = base;
-            H->d_kps = reinterpret_cast<const orb_keypoint*>(base + o_kps);
-            H->d_ur = H->has_ur ? reinterpret_cast<const float*>(base + o_ur) : nullptr;
-            H->d_coff = reinterpret_cast<const int*>(base + o_coff);
-            H->d_cidx = reinterpret_cast<const int*>(base + o_cidx);
-            try {
-                H->kps.resize(nn);
-            } catch (const std::bad_alloc&) {
-                return fail("orb_frame host keypoints", ORB_ERR_NOMEM);
-            }
-            if (n > 0 && (e = hipMemcpyAsync(H->kps.data(), d_un + (size_t)f * kp_cap, nn * sizeof(orb_keypoint),
+            if (const char* what = frame_alloc(c, n, d_ur_all != nullptr, grid, F[f], e)) return fail(what, ORB_ERR_NOMEM);
+            if (n > 0 && (e = hipMemcpyAsync(F[f]->kps.data(), d_un + (size_t)f * kp_cap, (size_t)n * sizeof(orb_keypoint),
                                              hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
                 return fail("orb_frame keypoints to the host", ORB_ERR_HIP);
         }
@@ -329,8 +295,8 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
         }
     }
     // ComputeStereoFromRGBD on the final undistorted records (the patch is queued before it on the stream)
-    if (rgbd && (e = launch_rgbd_depth(rgbd->map, rgbd->mbf, nframes, d_raw, d_un, d_counts, kp_cap, d_rgbd_ur,
-                                       d_rgbd_depth, nullptr, c->stream)) != hipSuccess)
+    if (step && !stereo && (e = launch_rgbd_depth(step->map, step->mbf, nframes, d_raw, d_un, d_counts, kp_cap, d_step_ur,
+                                                  d_step_depth, nullptr, c->stream)) != hipSuccess)
         return fail("k_rgbd_depth", ORB_ERR_HIP);
     // ComputeStereoMatches on the raw records of the slot pairs, over the images and pyramids of the context's last batch
     if (stereo) {
@@ -339,8 +305,8 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
         StereoSide SR = SL;
         SR.frame0 = 1;
         if (c->prof_on) Ctx::marker(c, ORB_K_STEREO, 1, c->stream);
-        e = launch_stereo(c->d_geom.get(), c->geom, SL, SR, nframes, stereo->mb, stereo->mbf, d_rgbd_ur, d_st_depth,
-                          d_st_work, kp_cap, d_st_matched, c->stream);
+        e = launch_stereo(c->d_geom.get(), c->geom, SL, SR, nframes, step->mb, step->mbf, d_step_ur, d_step_depth,
+                          d_stereo_work, kp_cap, d_stereo_matched, c->stream);
         if (c->prof_on) Ctx::marker(c, ORB_K_STEREO, 0, c->stream);
         if (e != hipSuccess) return fail("stereo kernels", ORB_ERR_HIP);
     }
@@ -349,26 +315,21 @@ int frames_from_extract(const char* fn, Ctx* c, const orb_distortion* dist, int 
         const size_t nn = (size_t)H->n;
         int* d_work = a.take<int>(2 * nn);
         if (nn > 0 &&
-            ((e = hipMemcpyAsync(H->d_base.get(), d_desc + (size_t)f * step * kp_cap * 32, nn * 32, hipMemcpyDeviceToDevice,
+            ((e = hipMemcpyAsync(H->d_base.get(), d_desc + (size_t)f * slots * kp_cap * 32, nn * 32, hipMemcpyDeviceToDevice,
                                  c->stream)) != hipSuccess ||
              (e = hipMemcpyAsync(const_cast<orb_keypoint*>(H->d_kps), d_un + (size_t)f * kp_cap,
                                  nn * sizeof(orb_keypoint), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess ||
              (d_ur_all && (e = hipMemcpyAsync(const_cast<float*>(H->d_ur), d_ur_all + (size_t)f * kp_cap, nn * 4,
                                               hipMemcpyDeviceToDevice, c->stream)) != hipSuccess)))
             return fail("orb_frame copy", ORB_ERR_HIP);
-        if ((e = launch_frame_grid(H->d_kps, H->n, ProjGrid{min_x, min_y, inv_w, inv_h}, const_cast<int*>(H->d_coff),
-                                   const_cast<int*>(H->d_cidx), d_work, c->stream)) != hipSuccess)
+        if ((e = launch_frame_grid(H->d_kps, H->n, grid, const_cast<int*>(H->d_coff), const_cast<int*>(H->d_cidx), d_work,
+                                   c->stream)) != hipSuccess)
             return fail("k_frame_grid", ORB_ERR_HIP);
     }
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail("orb_frame synchronise", ORB_ERR_HIP);
     for (int f = 0; f < nframes; f++) {
-        orb_frame* H = F[f];
-        for (int i = 0; i < H->n; i++) {
-            const int o = H->kps[i].octave;
-            H->oct_min = i ? std::min(H->oct_min, o) : o;
-            H->oct_max = i ? std::max(H->oct_max, o) : o;
-        }
-        out[f] = H;
+        frame_octaves(F[f]);
+        out[f] = F[f];
     }
     return ORB_OK;
 }

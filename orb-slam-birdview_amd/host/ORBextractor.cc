@@ -99,10 +99,7 @@ int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t st
     return n;
 }
 
-void ORBextractor::operator()(const ImageView& image, const ImageView& /*mask*/, std::vector<KeyPoint>& keypoints,
-                              DescriptorMat& descriptors) {
-    if (image.empty()) return;   // ORBextractor.cc:1046-1047
-    const int n = extract_raw(image.data, image.cols, image.rows, image.step);
+void ORBextractor::deliver(int n, std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors) const {
     // :1061-1070: descriptors n x 32, released when there is no keypoint
     if (n == 0)
         descriptors.release();
@@ -112,16 +109,16 @@ void ORBextractor::operator()(const ImageView& image, const ImageView& /*mask*/,
     if (n) memcpy(descriptors.buf.data(), dbuf_.data(), (size_t)n * 32);
 }
 
+void ORBextractor::operator()(const ImageView& image, const ImageView& /*mask*/, std::vector<KeyPoint>& keypoints,
+                              DescriptorMat& descriptors) {
+    if (image.empty()) return;   // ORBextractor.cc:1046-1047
+    deliver(extract_raw(image.data, image.cols, image.rows, image.step), keypoints, descriptors);
+}
+
 void ORBextractor::operator()(const ColorImageView& image, const ImageView& /*mask*/, std::vector<KeyPoint>& keypoints,
                               DescriptorMat& descriptors) {
     if (image.empty()) return;   // ORBextractor.cc:1046-1047
-    const int n = extract_raw(image.data, image.cols, image.rows, image.step, image.code);
-    if (n == 0)
-        descriptors.release();
-    else
-        descriptors.create(n);
-    keypoints.assign(kbuf_.begin(), kbuf_.begin() + n);
-    if (n) memcpy(descriptors.buf.data(), dbuf_.data(), (size_t)n * 32);
+    deliver(extract_raw(image.data, image.cols, image.rows, image.step, image.code), keypoints, descriptors);
 }
 
 void ORBextractor::operator()(const ImageView& rawImage, const orb_rectify* rectify, const ImageView& /*mask*/,
@@ -131,13 +128,8 @@ void ORBextractor::operator()(const ImageView& rawImage, const orb_rectify* rect
     int ow = 0, oh = 0;
     check(orb_rectify_size(rectify, &ow, &oh), "orb_rectify_size");
     if (ow == 0 || oh == 0) return;   // (an empty map gives an empty rectified image)
-    const int n = extract_raw(rawImage.data, rawImage.cols, rawImage.rows, rawImage.step, -1, rectify);
-    if (n == 0)
-        descriptors.release();
-    else
-        descriptors.create(n);
-    keypoints.assign(kbuf_.begin(), kbuf_.begin() + n);
-    if (n) memcpy(descriptors.buf.data(), dbuf_.data(), (size_t)n * 32);
+    deliver(extract_raw(rawImage.data, rawImage.cols, rawImage.rows, rawImage.step, -1, rectify), keypoints,
+            descriptors);
 }
 
 #ifdef ORBGPU_WITH_OPENCV

@@ -181,6 +181,8 @@ private:
     // to rectify first
     int extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color = -1,
                     const orb_rectify* rect = nullptr);
+    // the first n results of kbuf_ / dbuf_ into the caller's containers
+    void deliver(int n, std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors) const;
     orb_ctx* ctx_ = nullptr;
     std::vector<KeyPoint> kbuf_;
     std::vector<uint8_t> dbuf_;

@@ -311,25 +311,24 @@ class ORBextractor(_Ctx):
         else:
             img = _color_image(img, color)
         h, w = img.shape[:2]
+        # the entry point and what it takes between the context and the image
+        if rectify is not None:
+            name, lead = "orb_extract_rectified", (rectify.h,)
+        elif color is not None:
+            name, lead = "orb_extract_color", (color,)
+        else:
+            name, lead = "orb_extract", ()
+        fn = getattr(lib(), name)
         cap = 4 * max(self.params.nfeatures, 1) + 256
         while True:
             kps = np.zeros(cap, KP_DTYPE)
             desc = np.zeros((cap, 32), np.uint8)
             n = ctypes.c_int(0)
-            if rectify is not None:
-                st = lib().orb_extract_rectified(self.h, rectify.h, _p(img), w, h, img.strides[0], _p(kps), cap,
-                                                 ctypes.byref(n), _p(desc))
-            elif color is None:
-                st = lib().orb_extract(self.h, _p(img), w, h, img.strides[0], _p(kps), cap, ctypes.byref(n),
-                                       _p(desc))
-            else:
-                st = lib().orb_extract_color(self.h, color, _p(img), w, h, img.strides[0], _p(kps), cap,
-                                             ctypes.byref(n), _p(desc))
+            st = fn(self.h, *lead, _p(img), w, h, img.strides[0], _p(kps), cap, ctypes.byref(n), _p(desc))
             if st == -3:
                 cap = n.value
                 continue
-            check(st, "orb_extract_rectified" if rectify is not None else
-                  "orb_extract" if color is None else "orb_extract_color")
+            check(st, name)
             break
         self._last_shape = (h, w) if rectify is None else rectify.size[::-1]
         return kps[:n.value].copy(), desc[:n.value].copy()
@@ -368,6 +367,16 @@ class BatchExtractor(_Ctx):
             raise OrbError(-5, "orb_device_alloc")
         return p
 
+    def _stage(self, name, frames):
+        """frames into the device staging buffer self.<name> (d_color / d_raw), grown when it is too small."""
+        if getattr(self, name + "_bytes", 0) < frames.nbytes:
+            if getattr(self, name, None):
+                lib().orb_device_free(self.h, getattr(self, name))
+                setattr(self, name, None)
+            setattr(self, name, self._alloc(frames.nbytes))
+            setattr(self, name + "_bytes", frames.nbytes)
+        check(lib().orb_memcpy_h2d(self.h, getattr(self, name), _p(frames), frames.nbytes), "h2d")
+
     def upload(self, frames):
         frames = np.ascontiguousarray(frames, np.uint8)
         assert frames.shape == (self.batch, self.hgt, self.w)
@@ -380,13 +389,7 @@ class BatchExtractor(_Ctx):
         ch = 3 if color in (COLOR_RGB, COLOR_BGR) else 4
         frames = np.ascontiguousarray(frames, np.uint8)
         assert frames.shape == (self.batch, self.hgt, self.w, ch)
-        if getattr(self, "d_color_bytes", 0) < frames.nbytes:
-            if getattr(self, "d_color", None):
-                lib().orb_device_free(self.h, self.d_color)
-                self.d_color = None
-            self.d_color = self._alloc(frames.nbytes)
-            self.d_color_bytes = frames.nbytes
-        check(lib().orb_memcpy_h2d(self.h, self.d_color, _p(frames), frames.nbytes), "h2d")
+        self._stage("d_color", frames)
         check(lib().orb_to_gray_device(self.h, color, self.d_color, self.batch, self.w, self.hgt,
                                        self.w * self.hgt * ch, self.w * ch, self.d_frames, self.w * self.hgt, self.w),
               "orb_to_gray_device")
@@ -399,13 +402,7 @@ class BatchExtractor(_Ctx):
         assert frames.ndim == 3 and frames.shape[0] == self.batch
         assert all(r.size == (self.w, self.hgt) for r in rectifiers), "the maps' size is the extractor's"
         sh, sw = frames.shape[1:]
-        if getattr(self, "d_raw_bytes", 0) < frames.nbytes:
-            if getattr(self, "d_raw", None):
-                lib().orb_device_free(self.h, self.d_raw)
-                self.d_raw = None
-            self.d_raw = self._alloc(frames.nbytes)
-            self.d_raw_bytes = frames.nbytes
-        check(lib().orb_memcpy_h2d(self.h, self.d_raw, _p(frames), frames.nbytes), "h2d")
+        self._stage("d_raw", frames)
         remap_device(self, rectifiers, self.d_raw, self.batch, sw, sh, sw * sh, sw, self.d_frames, self.w * self.hgt,
                      self.w)
 

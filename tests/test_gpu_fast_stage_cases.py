@@ -68,14 +68,22 @@ def test_batch_launch_matches_oracle(orbgpu_mod, oracle_mod, monkeypatch, name, 
 
 
 def test_host_path_pitch_is_dword_aligned():
-    """CPU only: orb_extract uploads into rows of a multiple of 64 bytes and passes that pitch as the row stride."""
+    """CPU only: the host-image path (extract_host behind orb_extract) uploads into rows of a multiple of 64 bytes and
+    passes that pitch as the row stride; its staging function receives that buffer and pitch and uploads with them."""
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "orb-slam-birdview_amd",
                             "csrc", "orbgpu_abi.hip")).read()
-    body = src[src.index("int orb_extract("):]
-    body = body[:body.index("\n}\n")]
+
+    def body_of(head):
+        body = src[src.index(head):]
+        return body[:body.index("\n}\n")]
+
+    assert "return extract_host(c, HostImage{img, w, hgt, stride}," in body_of("int orb_extract(")
+    body = body_of("int extract_host(")
     assert re.search(r"const size_t pitch = \(\(size_t\)w \+ 63\) & ~\(size_t\)63;", body)
     assert re.search(r"run_extract\(c->d_in\.get\(\), 1, \(long long\)pitch \* hgt, \(int\)pitch,", body)
-    assert "hipMemcpy2DAsync(c->d_in.get(), pitch, img, stride, w, hgt" in body
+    assert "stage_host_image(c, im, w, hgt, c->d_in.get(), pitch," in body
+    stage = body_of("static int stage_host_image(Ctx* c, const HostImage& im, int w, int hgt, uint8_t* d_in, size_t pitch,")
+    assert "hipMemcpy2DAsync(d_in, pitch, im.data, im.stride, w, hgt" in stage
 
 
 @pytest.mark.gpu
