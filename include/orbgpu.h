@@ -947,6 +947,83 @@ int orb_frames_create_from_batch_stereo(orb_ctx* ctx, const orb_distortion* dist
                                         int kp_cap, float min_x, float min_y, float inv_w, float inv_h, float* d_uright,
                                         float* d_depth, orb_frame** out);
 
+/* ======================= Fisheye driver input: mask, crop, half-size and gray (mono_fisheye) ============= */
+
+/* What Examples/Monocular/mono_fisheye.cc:94-116 does to the camera frame before System::TrackMonocularWithBirdview,
+ * and the cvtColor Tracking::GrabImageMonocularWithBirdview opens with (Tracking.cc:278-307), as one definition over a
+ * source of sw x sh interleaved 8-bit pixels.  `code` is ORB_PREP_GRAY (one byte per pixel: a gray camera) or an
+ * ORB_COLOR_* code (3 or 4 bytes per pixel in the order the code names).  The output is the cw/2 x ch/2 GRAY image
+ * the reference's extractor receives.  The definition is pinned to OpenCV 3.2 on x86-64 without IPP:
+ *   mask    applyMask (:202-212): a source pixel whose mask byte is > 250 has all its channels set to 0.  The mask has
+ *           the source's size; the byte is channel 1 of a 3-channel mask (mask.at<Vec3b>(i, j)[1]) or the only channel
+ *           of a 1-channel one.  It is read in SOURCE coordinates, before the crop.  mask NULL: nothing is zeroed.
+ *   crop    Rect(cx, cy, cw, ch) (:111-113): 0 <= cx, 0 <= cy, cx + cw <= sw, cy + ch <= sh.
+ *   resize  cv::resize(im, im, Size(0, 0), 0.5, 0.5) (:116): for an exact factor of 2 INTER_LINEAR takes the INTER_AREA
+ *           fast path, per channel D = (S00 + S01 + S10 + S11 + 2) >> 2 over the 2x2 block; every channel on its own; a
+ *           masked pixel contributes 0 and is not left out of the mean.
+ *   gray    3 or 4 channels: orb_to_gray_host's formula over the three AVERAGED channels (resize, then convert, as
+ *           the reference orders them; convert-then-resize differs by one level for some inputs); alpha is ignored.
+ *           ORB_PREP_GRAY: the averaged value itself.
+ * cw and ch must be EVEN: with an odd side OpenCV leaves the area path for a fractional-scale bilinear resize of the
+ * colour image, which is not built (ORB_ERR_ARG).  Scale factors other than 0.5 are not built either.
+ * Rows are stride bytes apart; any base alignment and any stride are accepted.  Only the crop rows' [cx * channels,
+ * (cx + cw) * channels) bytes are read and only [row, row + cw / 2) of the destination written.
+ *   orb_front_prep_host    the definition, on the CPU.  No context, no GPU.
+ *   orb_prep_create        one camera's source size, mask (host memory, may be NULL) and crop, resident on ctx's device:
+ *                          the mask is reduced once to 4 keep bits per output pixel over the crop.  Synchronous.  Lifetime
+ *                          and device rules are orb_rectify's: usable with any context of the same device, one thread at
+ *                          a time, destroyed before the context that created it.  cw == 0 or ch == 0 gives an empty
+ *                          handle (every call through it is ORB_OK with nothing touched).
+ *   orb_prep_size          the output's (cw / 2, ch / 2).
+ *   orb_prep_source_size   the source's (sw, sh): the size every frame given with the handle must have.
+ *   orb_front_prep_device  nframes source frames in device memory in one launch (k_front_prep), asynchronous on the
+ *                          context's stream: frame f at d_src + f * src_frame_pitch -> d_dst + f * dst_frame_pitch.  d_dst
+ *                          is what orb_extract_batch_device consumes (same stream: no synchronisation in between).
+ *   orb_extract_fisheye    orb_extract for a raw host frame of the handle's source size: only the crop's rows and columns
+ *                          are uploaded, prepared on the device, then orb_extract's single-frame chain runs unchanged on
+ *                          the prepared image.  orb_get_level(ctx, 0, ...) afterwards returns the prepared gray image.
+ *                          Empty image (img == NULL or an empty handle): ORB_OK, the outputs untouched; capacity as
+ *                          orb_extract.
+ * ORB_ERR_ARG before any GPU work, outputs untouched: an unknown code; mask_channels outside {1, 3} with a mask; a
+ * negative size, crop or nframes; an odd cw or ch; a crop outside the source; a source side above 8192 (the output side
+ * stays within the extractor's 4096); a source stride below sw * channels, a mask stride below sw * mask_channels, a
+ * destination stride below cw / 2; with nframes > 1 a frame pitch below (rows - 1) * stride + the row's bytes; NULL
+ * arrays with a non-empty crop; a NULL handle or one of another device than the context's.  nframes == 0: ORB_OK,
+ * nothing touched.
+ *
+ * ConvertMaskBirdview (mono_fisheye.cc:99, :244-271), which the driver runs on the birdview mask of EVERY frame:
+ *   dst = (src[1] < 20) ? 0 : 250   over a 3-channel (or 4-channel) mask, then the vehicle footprint zeroed: exactly
+ *   orb_bird_footprint_mask's rectangle.  The value is 250, not 255.
+ *   orb_bird_mask_host     the definition, on the CPU: the conversion, then orb_bird_footprint_mask.
+ *   orb_bird_mask_device   nframes masks in device memory in one launch (k_bird_mask), asynchronous on the context's
+ *                          stream.  d_dst with dst_row_stride / dst_frame_pitch is what orb_bird_extract_batch_device
+ *                          takes as d_masks with mask_stride / mask_frame_pitch.  The birdview object has a STREAM OF ITS
+ *                          OWN: call orb_sync before d_dst goes to orb_bird_extract_device or
+ *                          orb_bird_extract_batch_device.
+ * ORB_ERR_ARG before any GPU work, outputs untouched: channels outside {3, 4}; a negative size or nframes; a side above
+ * 4096; strides below a row; with nframes > 1 a frame pitch below (h - 1) * stride + the row's bytes; NULL arrays with
+ * a non-empty mask.  nframes == 0, w == 0 or h == 0: ORB_OK, nothing touched. */
+enum { ORB_PREP_GRAY = -1 };   /* a one-channel source, beside the ORB_COLOR_* codes */
+typedef struct orb_prep orb_prep;
+int  orb_front_prep_host(int code, const uint8_t* src, int sw, int sh, size_t src_stride, const uint8_t* mask,
+                         int mask_channels, size_t mask_stride, int cx, int cy, int cw, int ch, uint8_t* dst,
+                         size_t dst_stride);
+int  orb_prep_create(orb_ctx* ctx, int sw, int sh, const uint8_t* mask, int mask_channels, size_t mask_stride, int cx,
+                     int cy, int cw, int ch, orb_prep** out);
+void orb_prep_destroy(orb_prep* prep);
+int  orb_prep_size(const orb_prep* prep, int* w, int* h);
+int  orb_prep_source_size(const orb_prep* prep, int* sw, int* sh);
+int  orb_front_prep_device(orb_ctx* ctx, const orb_prep* prep, int code, const uint8_t* d_src, int nframes,
+                           size_t src_frame_pitch, size_t src_row_stride, uint8_t* d_dst, size_t dst_frame_pitch,
+                           size_t dst_row_stride);
+int  orb_extract_fisheye(orb_ctx* ctx, const orb_prep* prep, int code, const uint8_t* img, size_t stride,
+                         orb_keypoint* kps, int cap, int* n, uint8_t* desc);
+int  orb_bird_mask_host(int channels, const uint8_t* src, int w, int h, size_t src_stride, uint8_t* dst,
+                        size_t dst_stride);
+int  orb_bird_mask_device(orb_ctx* ctx, int channels, const uint8_t* d_src, int nframes, int w, int h,
+                          size_t src_frame_pitch, size_t src_row_stride, uint8_t* d_dst, size_t dst_frame_pitch,
+                          size_t dst_row_stride);
+
 /* ======================= DBoW2 vocabulary transform ======================= */
 
 typedef struct orb_vocab orb_vocab;

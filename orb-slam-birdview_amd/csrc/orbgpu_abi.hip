@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "orbgpu_ctx.h"
+#include "prep.h"
 #include "remap.h"
 #include "rgbd.h"
 
@@ -572,7 +573,18 @@ static int stage_host_image(Ctx* c, const HostImage& im, int w, int hgt, uint8_t
     hipError_t e;
     int st;
     uint8_t* d_src;
-    if (im.color >= 0) {
+    if (im.prep) {
+        // the crop's rows and columns alone into the scratch arena, prepared into d_in
+        const orb_prep& p = *im.prep;
+        const int ch = prep_channels(im.color);
+        const size_t cbytes = (size_t)p.cw * ch;
+        Arena a{c};
+        if ((st = upload_to_arena(a, im.data + (size_t)p.cy * im.stride + (size_t)p.cx * ch, cbytes, p.ch, im.stride, 0,
+                                  "fisheye frame staging", "upload fisheye frame", &d_src)) != ORB_OK)
+            return st;
+        if ((e = launch_front_prep(p, im.color, d_src, 1, 0, pitch64(cbytes), d_in, 0, pitch, c->stream)) != hipSuccess)
+            return set_error("k_front_prep", e), ORB_ERR_HIP;
+    } else if (im.color >= 0) {
         // the colour image into the scratch arena, converted into d_in
         const size_t cbytes = (size_t)w * color_channels(im.color);
         Arena a{c};
@@ -623,7 +635,9 @@ static int stage_host_image(Ctx* c, const HostImage& im, int w, int hgt, uint8_t
 }
 
 int extract_host(Ctx* c, const HostImage& im, orb_keypoint* kps, int cap, int* n, uint8_t* desc) {
-    const int w = im.rect ? im.rect->dw : im.w, hgt = im.rect ? im.rect->dh : im.h;   // the extracted image's size
+    // the extracted image's size
+    const int w = im.prep ? im.prep->cw / 2 : im.rect ? im.rect->dw : im.w;
+    const int hgt = im.prep ? im.prep->ch / 2 : im.rect ? im.rect->dh : im.h;
     int st = c->ensure_geometry(w, hgt);
     if (st != ORB_OK) return st;
     if ((st = c->ensure_frames(1)) != ORB_OK) return st;
@@ -636,7 +650,7 @@ int extract_host(Ctx* c, const HostImage& im, orb_keypoint* kps, int cap, int* n
     // mapped + coherent (fine-grained): k_describe stores the outputs straight into this block and the host reads
     // them after hipStreamSynchronize, with no D2H copy in between
     if ((e = c->h_pinned.ensure(need)) != hipSuccess) return set_error("pinned staging", e), ORB_ERR_NOMEM;
-    const bool streamed = c->upload_stream && im.color < 0 && !im.rect;
+    const bool streamed = c->upload_stream && im.color < 0 && !im.rect && !im.prep;
     if ((st = stage_host_image(c, im, w, hgt, c->d_in.get(), pitch, streamed)) != ORB_OK) return st;
     // output block [count | overflow flag | 8 B pad | keypoints | descriptors] in pinned, host-coherent
     // memory: k_describe writes the keypoints, descriptors and count straight into it (and copies the

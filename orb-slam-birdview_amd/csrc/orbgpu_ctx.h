@@ -221,16 +221,19 @@ int upload_to_arena(Arena& a, const uint8_t* img, size_t row_bytes, int rows, si
 
 // The image a host-image entry point was given: w x h pixels, rows `stride` bytes apart.  color >= 0: a colour image
 // with that ORB_COLOR_* code, converted to gray on the device; rect: a raw gray image to rectify on the device, the
-// extracted image then has the maps' size.  Neither: the gray image itself.
+// extracted image then has the maps' size; prep: the fisheye camera's frame (color is then its front-image code,
+// ORB_PREP_GRAY included), masked, cropped, halved and converted on the device, the extracted image then has
+// orb_prep_size's size.  None of them: the gray image itself.
 struct HostImage {
     const uint8_t* data;
     int w, h;
     size_t stride;
     int color = -1;
     const orb_rectify* rect = nullptr;
+    const orb_prep* prep = nullptr;
 };
 
-// orb_extract, orb_extract_color and orb_extract_rectified behind their argument checks (orbgpu_abi.hip): the image
+// orb_extract, orb_extract_color, orb_extract_rectified and orb_extract_fisheye behind their argument checks (orbgpu_abi.hip): the image
 // staged into Ctx::d_in as a gray frame, the single-frame chain, one synchronisation, the outputs copied out.  The
 // chain sees the same frame whatever the form, so orb_get_level(ctx, 0) is the gray / rectified image.
 int extract_host(Ctx* c, const HostImage& im, orb_keypoint* kps, int cap, int* n, uint8_t* desc);

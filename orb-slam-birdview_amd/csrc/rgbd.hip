@@ -5,23 +5,13 @@
 #include <climits>
 #include <cmath>
 
+#include "gray_def.h"
 #include "rgbd.h"
 #include "undistort.h"
 
 namespace orbgpu {
 
-// OpenCV 3.2 RGB2Gray<uchar> (color.cpp: R2Y 4899, G2Y 9617, B2Y 1868, yuv_shift 14).  c0 / c2 are
-// the first and third byte of the pixel, w0 / w2 their weights (4899, 1868 for RGB*, 1868, 4899 for BGR*).  The
-// weights sum to 16384 and the largest sum is 255 * 16384 + 8192 < 2^23: 24-bit multiply-adds are exact.
-__host__ __device__ inline uint32_t gray_of(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t w0, uint32_t w2) {
-    return (w0 * c0 + 9617u * c1 + w2 * c2 + 8192u) >> 14;
-}
-
-inline void gray_weights(int code, uint32_t& w0, uint32_t& w2) {
-    const bool bgr = code == ORB_COLOR_BGR || code == ORB_COLOR_BGRA;
-    w0 = bgr ? 1868u : 4899u;
-    w2 = bgr ? 4899u : 1868u;
-}
+// (gray_of and gray_weights, the cvtColor definition: gray_def.h)
 
 constexpr int kGrayThreads = 256;
 

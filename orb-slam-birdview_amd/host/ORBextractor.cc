@@ -76,9 +76,11 @@ ORBextractor::~ORBextractor() {
     if (ctx_) orb_destroy(ctx_);
 }
 
-int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color, const orb_rectify* rect) {
-    int ow = cols, oh = rows;   // the extracted image's size: the maps' for a raw image
+int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color, const orb_rectify* rect,
+                              const orb_prep* prep) {
+    int ow = cols, oh = rows;   // the extracted image's size: the maps' for a raw image, the handle's for a fisheye frame
     if (rect) check(orb_rectify_size(rect, &ow, &oh), "orb_rectify_size");
+    if (prep) check(orb_prep_size(prep, &ow, &oh), "orb_prep_size");
     const int cap = orb_batch_kp_cap(ctx_, ow, oh);   // exact upper bound for this image size
     if (cap < 0) throw OrbGpuError(cap, "orb_batch_kp_cap");
     if ((int)kbuf_.size() < cap) {
@@ -86,7 +88,10 @@ int ORBextractor::extract_raw(const uint8_t* data, int cols, int rows, size_t st
         dbuf_.resize((size_t)cap * 32);
     }
     int n = 0;
-    if (rect)
+    if (prep)
+        check(orb_extract_fisheye(ctx_, prep, color, data, step, kbuf_.data(), (int)kbuf_.size(), &n, dbuf_.data()),
+              "orb_extract_fisheye");
+    else if (rect)
         check(orb_extract_rectified(ctx_, rect, data, cols, rows, step, kbuf_.data(), (int)kbuf_.size(), &n, dbuf_.data()),
               "orb_extract_rectified");
     else if (color < 0)
@@ -130,6 +135,30 @@ void ORBextractor::operator()(const ImageView& rawImage, const orb_rectify* rect
     if (ow == 0 || oh == 0) return;   // (an empty map gives an empty rectified image)
     deliver(extract_raw(rawImage.data, rawImage.cols, rawImage.rows, rawImage.step, -1, rectify), keypoints,
             descriptors);
+}
+
+void ORBextractor::fisheye(const uint8_t* data, int cols, int rows, size_t step, int code, const orb_prep* prep,
+                           std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors) {
+    if (!prep) throw std::invalid_argument("ORBextractor: prep NULL");
+    int ow = 0, oh = 0;
+    check(orb_prep_size(prep, &ow, &oh), "orb_prep_size");
+    if (ow == 0 || oh == 0) return;   // (an empty crop gives an empty image)
+    int sw = 0, sh = 0;
+    check(orb_prep_source_size(prep, &sw, &sh), "orb_prep_source_size");
+    if (cols != sw || rows != sh) throw std::invalid_argument("ORBextractor: the frame has not the FrontPrep's source size");
+    deliver(extract_raw(data, cols, rows, step, code, nullptr, prep), keypoints, descriptors);
+}
+
+void ORBextractor::operator()(const ImageView& frame, const orb_prep* prep, const ImageView& /*mask*/,
+                              std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors) {
+    if (frame.empty()) return;   // ORBextractor.cc:1046-1047
+    fisheye(frame.data, frame.cols, frame.rows, frame.step, ORB_PREP_GRAY, prep, keypoints, descriptors);
+}
+
+void ORBextractor::operator()(const ColorImageView& frame, const orb_prep* prep, const ImageView& /*mask*/,
+                              std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors) {
+    if (frame.empty()) return;   // ORBextractor.cc:1046-1047
+    fisheye(frame.data, frame.cols, frame.rows, frame.step, frame.code, prep, keypoints, descriptors);
 }
 
 #ifdef ORBGPU_WITH_OPENCV

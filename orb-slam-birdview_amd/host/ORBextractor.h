@@ -148,6 +148,15 @@ public:
     void operator()(const ImageView& rawImage, const orb_rectify* rectify, const ImageView& mask,
                     std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors);
 
+    // The same for the fisheye camera's RAW frame, gray or colour, of the handle's source size: the driver's applyMask,
+    // crop and half-size resize (mono_fisheye.cc:102-116) and Tracking's cvtColor run on the GPU in front of the
+    // extraction (orb_extract_fisheye; prep is a FrontPrep's handle, host/FrontPrep.h), and mvImagePyramid[0] is then
+    // the prepared gray image, of the handle's size.
+    void operator()(const ImageView& frame, const orb_prep* prep, const ImageView& mask, std::vector<KeyPoint>& keypoints,
+                    DescriptorMat& descriptors);
+    void operator()(const ColorImageView& frame, const orb_prep* prep, const ImageView& mask,
+                    std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors);
+
     int inline GetLevels() { return nlevels; }
     float inline GetScaleFactor() { return (float)scaleFactor; }
     std::vector<float> inline GetScaleFactors() { return mvScaleFactor; }
@@ -180,7 +189,10 @@ private:
     // returns #keypoints in kbuf_/dbuf_; color < 0: a gray image, else its ORB_COLOR_* code; rect: a raw gray image
     // to rectify first
     int extract_raw(const uint8_t* data, int cols, int rows, size_t step, int color = -1,
-                    const orb_rectify* rect = nullptr);
+                    const orb_rectify* rect = nullptr, const orb_prep* prep = nullptr);
+    // both fisheye overloads behind their empty-image test
+    void fisheye(const uint8_t* data, int cols, int rows, size_t step, int code, const orb_prep* prep,
+                 std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors);
     // the first n results of kbuf_ / dbuf_ into the caller's containers
     void deliver(int n, std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors) const;
     orb_ctx* ctx_ = nullptr;

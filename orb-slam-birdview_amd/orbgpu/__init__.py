@@ -18,7 +18,8 @@ __all__ = ["ORBextractor", "ORBmatcher", "BatchExtractor", "KP_DTYPE", "OrbError
            "features_in_area", "frame_grid", "Frame", "PROJ_QUERY_DTYPE", "PROJ_BEST", "PROJ_RATIO_SAME_LEVEL",
            "PROJ_GATE_NONE", "PROJ_GATE_FUSE", "proj_queries", "project_best_host",
            "COLOR_RGB", "COLOR_BGR", "COLOR_RGBA", "COLOR_BGRA", "DEPTH_U16", "DEPTH_F32", "to_gray_host", "depth_map",
-           "stereo_from_rgbd_host", "remap_host", "rectify_maps_host", "remap_device", "Rectifier", "distortion", "undistort_points_host", "image_bounds", "undistort_keypoints", "undistort_guard",
+           "stereo_from_rgbd_host", "remap_host", "rectify_maps_host", "remap_device", "Rectifier", "PREP_GRAY", "front_prep_host", "bird_mask_host", "front_prep_device",
+           "bird_mask_device", "FrontPrep", "distortion", "undistort_points_host", "image_bounds", "undistort_keypoints", "undistort_guard",
            "MapPoints", "POINT_PROJ_DTYPE", "FRUSTUM_FRAME", "FRUSTUM_FUSE", "camera", "project_points_host",
            "compute_stereo_matches", "ORBVocabulary", "KeyFrameDatabase", "bow_score", "KFDB_RELOC", "KFDB_LOOP",
            "BirdORB", "cornerSubPix",
@@ -47,6 +48,7 @@ FRUSTUM_FRAME, FRUSTUM_FUSE = 0, 1        # ORB_FRUSTUM_*
 
 COLOR_RGB, COLOR_BGR, COLOR_RGBA, COLOR_BGRA = 0, 1, 2, 3   # ORB_COLOR_*
 DEPTH_U16, DEPTH_F32 = 0, 1                                  # ORB_DEPTH_*
+PREP_GRAY = -1                                               # ORB_PREP_GRAY: a one-channel fisheye frame
 
 
 def _p(a):
@@ -197,6 +199,111 @@ class Rectifier:
         self.close()
 
 
+def _front_image(image, color):
+    """The fisheye camera's frame as the front-image entry points take it: H x W uint8 (color None or PREP_GRAY) or
+    H x W x 3 / 4 uint8 (color = COLOR_*).  Returns (array, code)."""
+    if color is None or color == PREP_GRAY:
+        return _gray_image(image), PREP_GRAY
+    return _color_image(image, color), color
+
+
+def _mask_image(mask, shape):
+    """The camera mask: None, H x W uint8 or H x W x 3 uint8 (channel 1 is read), of the frame's size.  Returns
+    (array or None, channels, row stride)."""
+    if mask is None:
+        return None, 1, 0
+    m = np.asarray(mask)
+    assert m.dtype == np.uint8 and (m.ndim == 2 or (m.ndim == 3 and m.shape[2] == 3)), "H x W (x 3) uint8 mask expected"
+    assert m.shape[:2] == tuple(shape), "the mask has the frame's size"
+    m = np.ascontiguousarray(m)
+    return m, 1 if m.ndim == 2 else 3, m.strides[0]
+
+
+def front_prep_host(image, mask, crop, color=None):
+    """orb_front_prep_host: the mono_fisheye driver's applyMask, crop (x, y, w, h; even sides) and half-size cv::resize,
+    then Tracking's cvtColor, as OpenCV 3.2 computes them, on the CPU (the definition the GPU forms equal byte for
+    byte).  image: H x W uint8, or H x W x 3 / 4 uint8 with color = COLOR_*; mask: None, H x W or H x W x 3 uint8 of the
+    image's size (a pixel is zeroed where its mask byte, channel 1 of three, is > 250).  Returns the (h / 2, w / 2) gray
+    image.  No context, no GPU."""
+    img, code = _front_image(image, color)
+    sh, sw = img.shape[:2]
+    m, mc, ms = _mask_image(mask, (sh, sw))
+    cx, cy, cw, ch = (int(v) for v in crop)
+    out = np.zeros((max(ch, 0) // 2, max(cw, 0) // 2), np.uint8)
+    check(lib().orb_front_prep_host(code, _p(img), sw, sh, img.strides[0], _p(m), mc, ms, cx, cy, cw, ch, _p(out),
+                                    out.shape[1]), "orb_front_prep_host")
+    return out
+
+
+def bird_mask_host(mask_image):
+    """orb_bird_mask_host: mono_fisheye.cc's ConvertMaskBirdview on the CPU.  mask_image: H x W x 3 / 4 uint8; returns
+    the H x W mask, 0 where G < 20, else 250, with the vehicle footprint (bird_footprint_mask's rectangle) zeroed."""
+    m = np.asarray(mask_image)
+    assert m.dtype == np.uint8 and m.ndim == 3 and m.shape[2] in (3, 4), "H x W x 3 / 4 uint8 expected"
+    m = np.ascontiguousarray(m)
+    h, w, c = m.shape
+    out = np.zeros((h, w), np.uint8)
+    check(lib().orb_bird_mask_host(c, _p(m), w, h, m.strides[0], _p(out), w), "orb_bird_mask_host")
+    return out
+
+
+def front_prep_device(ctx_or_matcher, prep, color, d_src, nframes, src_frame_pitch, src_row_stride, d_dst,
+                      dst_frame_pitch, dst_row_stride):
+    """orb_front_prep_device: nframes camera frames in device memory through prep (a FrontPrep) in one launch,
+    asynchronous on the context's stream; color is PREP_GRAY or COLOR_*.  d_dst is what
+    BatchExtractor / orb_extract_batch_device consumes on the same stream."""
+    check(lib().orb_front_prep_device(_ctx_handle(ctx_or_matcher), prep.h, PREP_GRAY if color is None else color, d_src,
+                                      nframes, src_frame_pitch, src_row_stride, d_dst, dst_frame_pitch, dst_row_stride),
+          "orb_front_prep_device")
+
+
+def bird_mask_device(ctx_or_matcher, channels, d_src, nframes, w, h, src_frame_pitch, src_row_stride, d_dst,
+                     dst_frame_pitch, dst_row_stride):
+    """orb_bird_mask_device: ConvertMaskBirdview of nframes 3- or 4-channel masks in device memory in one launch,
+    asynchronous on the context's stream.  d_dst is what BirdORB.extract_batch_device takes as d_masks; the birdview
+    object has a stream of its own, so synchronise the context first."""
+    check(lib().orb_bird_mask_device(_ctx_handle(ctx_or_matcher), channels, d_src, nframes, w, h, src_frame_pitch,
+                                     src_row_stride, d_dst, dst_frame_pitch, dst_row_stride), "orb_bird_mask_device")
+
+
+class FrontPrep:
+    """orb_prep: the fisheye camera's mask and crop resident on the device, built once per camera.  size = (width,
+    height) of the camera's frames; mask: None, H x W or H x W x 3 uint8 of that size; crop = (x, y, w, h) with even
+    sides.  ORBextractor(frame, prep=this) is then the driver's applyMask, crop and half-size resize plus Tracking's
+    cvtColor on the GPU in front of the extraction.  Close it before the context that created it."""
+
+    def __init__(self, ctx_or_matcher, size, mask, crop):
+        sw, sh = int(size[0]), int(size[1])
+        m, mc, ms = _mask_image(mask, (sh, sw))
+        cx, cy, cw, ch = (int(v) for v in crop)
+        self.h = ctypes.c_void_p()
+        check(lib().orb_prep_create(_ctx_handle(ctx_or_matcher), sw, sh, _p(m), mc, ms, cx, cy, cw, ch,
+                                    ctypes.byref(self.h)), "orb_prep_create")
+
+    def _pair(self, fn):
+        w, h = ctypes.c_int(), ctypes.c_int()
+        check(getattr(lib(), fn)(self.h, ctypes.byref(w), ctypes.byref(h)), fn)
+        return w.value, h.value
+
+    @property
+    def size(self):
+        """(width, height) of the prepared image: half the crop's."""
+        return self._pair("orb_prep_size")
+
+    @property
+    def source_size(self):
+        """(width, height) every frame given with this handle must have."""
+        return self._pair("orb_prep_source_size")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().orb_prep_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 def device_count():
     return lib().orb_device_count()
 
@@ -291,7 +398,7 @@ class ORBextractor(_Ctx):
     def umax(self):
         return self._umax.copy()
 
-    def __call__(self, image, mask=None, keypoints=None, descriptors=None, color=None, rectify=None):
+    def __call__(self, image, mask=None, keypoints=None, descriptors=None, color=None, rectify=None, prep=None):
         """operator()(image, mask, keypoints, descriptors): returns (keypoints, descriptors).
 
         An empty image returns the given outputs untouched (ORBextractor.cc:1046-1047); mask is
@@ -299,11 +406,16 @@ class ORBextractor(_Ctx):
         image; the cvtColor of Tracking::GrabImage* runs on the GPU in front of the extraction (orb_extract_color) and
         mvImagePyramid[0] is then mImGray.  rectify=Rectifier: image is the camera's raw gray image; the cv::remap of the
         stereo examples runs on the GPU in front of the extraction (orb_extract_rectified) and mvImagePyramid[0] is then
-        the rectified image."""
+        the rectified image.  prep=FrontPrep: image is the fisheye camera's raw frame (gray, or colour with color=);
+        the mono_fisheye driver's applyMask, crop and half-size resize and the cvtColor run on the GPU in front of the
+        extraction (orb_extract_fisheye) and mvImagePyramid[0] is then the prepared gray image."""
         img = np.asarray(image)
         if img.size == 0:
             return keypoints, descriptors
         assert color is None or rectify is None, "a colour image is converted before it is rectified"
+        assert prep is None or rectify is None, "a fisheye frame is not rectified"
+        if color == PREP_GRAY:
+            color = None
         if color is None:
             assert img.dtype == np.uint8 and img.ndim == 2, "CV_8UC1 expected (ORBextractor.cc:1050)"
             if not (img.strides[1] == 1 and img.strides[0] >= img.shape[1]):   # rows with padding go down as they are
@@ -311,26 +423,29 @@ class ORBextractor(_Ctx):
         else:
             img = _color_image(img, color)
         h, w = img.shape[:2]
-        # the entry point and what it takes between the context and the image
-        if rectify is not None:
-            name, lead = "orb_extract_rectified", (rectify.h,)
+        # the entry point, what it takes between the context and the image, and the image's size where it takes one
+        if prep is not None:
+            assert (w, h) == prep.source_size, "the frame has the FrontPrep's source size"
+            name, lead, dims = "orb_extract_fisheye", (prep.h, PREP_GRAY if color is None else color), ()
+        elif rectify is not None:
+            name, lead, dims = "orb_extract_rectified", (rectify.h,), (w, h)
         elif color is not None:
-            name, lead = "orb_extract_color", (color,)
+            name, lead, dims = "orb_extract_color", (color,), (w, h)
         else:
-            name, lead = "orb_extract", ()
+            name, lead, dims = "orb_extract", (), (w, h)
         fn = getattr(lib(), name)
         cap = 4 * max(self.params.nfeatures, 1) + 256
         while True:
             kps = np.zeros(cap, KP_DTYPE)
             desc = np.zeros((cap, 32), np.uint8)
             n = ctypes.c_int(0)
-            st = fn(self.h, *lead, _p(img), w, h, img.strides[0], _p(kps), cap, ctypes.byref(n), _p(desc))
+            st = fn(self.h, *lead, _p(img), *dims, img.strides[0], _p(kps), cap, ctypes.byref(n), _p(desc))
             if st == -3:
                 cap = n.value
                 continue
             check(st, name)
             break
-        self._last_shape = (h, w) if rectify is None else rectify.size[::-1]
+        self._last_shape = prep.size[::-1] if prep is not None else (h, w) if rectify is None else rectify.size[::-1]
         return kps[:n.value].copy(), desc[:n.value].copy()
 
     @property
@@ -406,6 +521,20 @@ class BatchExtractor(_Ctx):
         remap_device(self, rectifiers, self.d_raw, self.batch, sw, sh, sw * sh, sw, self.d_frames, self.w * self.hgt,
                      self.w)
 
+    def upload_fisheye(self, frames, prep, color=None):
+        """The batch as the fisheye camera's raw frames ((batch, H, W) uint8, or (batch, H, W, 3 / 4) with
+        color=COLOR_*; H x W is prep's source size): uploaded, then masked, cropped, halved and converted on the device
+        into the buffer launch() reads (orb_front_prep_device; asynchronous on the context's stream, so launch() may
+        follow at once).  prep's size is the extractor's."""
+        ch = 1 if color in (None, PREP_GRAY) else 3 if color in (COLOR_RGB, COLOR_BGR) else 4
+        frames = np.ascontiguousarray(frames, np.uint8)
+        sw, sh = prep.source_size
+        assert frames.shape == ((self.batch, sh, sw) if ch == 1 else (self.batch, sh, sw, ch))
+        assert prep.size == (self.w, self.hgt), "the prepared image's size is the extractor's"
+        self._stage("d_fisheye", frames)
+        front_prep_device(self, prep, color, self.d_fisheye, self.batch, sw * sh * ch, sw * ch, self.d_frames,
+                          self.w * self.hgt, self.w)
+
     def stereo_from_rgbd(self, dmap, mbf, d_kps_un, d_uright, d_depth, d_nvalid=None, nframes=None):
         """Frame::ComputeStereoFromRGBD for the frames of the last launch, on the device (orb_stereo_from_rgbd_device;
         asynchronous).  dmap: depth_map(...) over device memory; d_kps_un: the undistorted keypoints in the layout of
@@ -470,7 +599,7 @@ class BatchExtractor(_Ctx):
 
     def close(self):
         if getattr(self, "h", None):
-            for p in ("d_frames", "d_kps", "d_desc", "d_counts", "d_color", "d_raw"):
+            for p in ("d_frames", "d_kps", "d_desc", "d_counts", "d_color", "d_raw", "d_fisheye"):
                 if getattr(self, p, None):
                     lib().orb_device_free(self.h, getattr(self, p))
                     setattr(self, p, None)

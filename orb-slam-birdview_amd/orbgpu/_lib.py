@@ -172,6 +172,15 @@ SIGNATURES = {
     "orb_extract_rectified": (ci, [vp, vp, vp, ci, ci, csz, vp, ci, ctypes.POINTER(ci), vp]),
     "orb_frames_create_from_batch_stereo": (ci, [vp, ctypes.POINTER(OrbDistortion), ci, cf, cf, vp, vp, vp, ci, cf, cf,
                                                  cf, cf, vp, vp, vp]),
+    "orb_front_prep_host": (ci, [ci, vp, ci, ci, csz, vp, ci, csz, ci, ci, ci, ci, vp, csz]),
+    "orb_prep_create": (ci, [vp, ci, ci, vp, ci, csz, ci, ci, ci, ci, ctypes.POINTER(vp)]),
+    "orb_prep_destroy": (None, [vp]),
+    "orb_prep_size": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "orb_prep_source_size": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "orb_front_prep_device": (ci, [vp, vp, ci, vp, ci, csz, csz, vp, csz, csz]),
+    "orb_extract_fisheye": (ci, [vp, vp, ci, vp, csz, vp, ci, ctypes.POINTER(ci), vp]),
+    "orb_bird_mask_host": (ci, [ci, vp, ci, ci, csz, vp, csz]),
+    "orb_bird_mask_device": (ci, [vp, ci, vp, ci, ci, ci, csz, csz, vp, csz, csz]),
     "orb_points_create": (ci, [vp, ci, ctypes.POINTER(vp)]),
     "orb_points_write": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
     "orb_points_capacity": (ci, [vp]),
