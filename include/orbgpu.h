@@ -550,6 +550,7 @@ int orb_features_in_area(int n, const orb_keypoint* kps_un, float min_x, float m
  * orb_frame_grid_read copies the grid out (cell_off: 64 * 48 + 1 ints; cell_idx: *nslots <= n ints; ORB_ERR_CAPACITY
  * with *nslots set when cap is smaller). */
 typedef struct orb_frame orb_frame;
+typedef struct orb_vocab orb_vocab;   /* (the vocabulary section below) */
 int  orb_frame_create(orb_ctx* ctx, int n, const uint8_t* desc, const orb_keypoint* kps_un, const float* uright,
                       float min_x, float min_y, float inv_w, float inv_h, orb_frame** out);
 int  orb_frame_create_device(orb_ctx* ctx, int n, const uint8_t* d_desc, const orb_keypoint* d_kps,
@@ -558,6 +559,75 @@ int  orb_frame_create_device(orb_ctx* ctx, int n, const uint8_t* d_desc, const o
 void orb_frame_destroy(orb_frame* frame);
 int  orb_frame_count(const orb_frame* frame);
 int  orb_frame_grid_read(const orb_frame* frame, int* cell_off, int* cell_idx, int cap, int* nslots);
+
+/* BoW on the handle: Frame::ComputeBoW / KeyFrame::ComputeBoW (Frame.cc:562-569, KeyFrame.cc:74-83) without the
+ * descriptors leaving the device.  A handle may carry a BoW part, an allocation of its own that it owns: the
+ * per-feature triples (word id, weight, node levelsup above the leaf), a per-feature node id (0xFFFFFFFF for a feature
+ * outside the FeatureVector) and the FeatureVector as CSR (node ids strictly ascending, nnodes + 1 offsets, a node's
+ * feature indices ascending), with a host copy of the CSR for the searches' replays.  Attaching again replaces it.
+ *   orb_frame_compute_bow   transform(mDescriptors, mBowVec, mFeatVec, levelsup) (TemplatedVocabulary.h:1139-1210) for
+ *                           nframes handles: one k_vocab_transform launch over all their resident descriptors, one
+ *                           k_frame_featvec launch (a feature is in the FeatureVector iff (double)weight > 0, DBoW2's
+ *                           "not stopped"; equal to orb_vocab_bow's fv_* for the same triples, n == 0 and an
+ *                           all-stopped frame included), one synchronisation.  ORB_ERR_ARG before the context is
+ *                           touched: nframes < 0, a NULL vocabulary / handle, a handle listed twice; then a vocabulary
+ *                           or handle of another device.  On failure no handle is changed.
+ *   orb_frame_set_featvec   attaches a FeatureVector the caller holds (a KeyFrame's mFeatVec): checked as the matchers
+ *                           check an orb_featvec over the handle's n (ORB_ERR_ARG before any GPU work; node id
+ *                           0xFFFFFFFF is reserved), uploaded once; synchronises.  The triples are then absent.
+ *   orb_frame_has_bow       0: none, 1: a FeatureVector only, 2: with the triples.
+ *   orb_frame_bow_read      the BowVector (words ascending, values in double: orb_vocab_bow's own summation over the
+ *                           handle's triples, on the host; *nbow = 0 and vocab unused without triples) and the
+ *                           FeatureVector from the CSR the GPU built, in orb_vocab_bow's output format (arrays of n
+ *                           entries, fv_off n + 1; after orb_frame_set_featvec as many as the given CSR held).  Host
+ *                           only.  ORB_ERR_ARG for a NULL handle or one without BoW. */
+int orb_frame_compute_bow(orb_ctx* ctx, const orb_vocab* vocab, int levelsup, int nframes, orb_frame* const* frames);
+int orb_frame_set_featvec(orb_ctx* ctx, orb_frame* frame, orb_featvec fv);
+int orb_frame_has_bow(const orb_frame* frame);
+int orb_frame_bow_read(const orb_vocab* vocab, const orb_frame* frame, int* bow_words, double* bow_values, int* nbow,
+                       uint32_t* fv_nodes, int* fv_off, int* fv_idx, int* nfv);
+
+/* The vocabulary-gated searches between handles that carry BoW: every output and the return value are byte for byte
+ * those of the host-pointer entry point on the same data (the handles' descriptors, keypoints, uright and
+ * FeatureVectors), and nothing per feature is staged: the only per-call upload is the map-point flags (and a small
+ * table of per-keyframe constants).  ORB_ERR_ARG before the context is touched: a NULL handle, a handle without BoW,
+ * handles of different devices or of another device than the context's, a NULL output, NULL flags with n > 0, a
+ * negative count.  One launch sequence and one synchronisation per call (one more per re-rank of the BoW searches, as
+ * in the host-pointer forms).
+ *   orb_search_for_triangulation_frames  = orb_search_for_triangulation_batch (LocalMapping::CreateNewMapPoints,
+ *     LocalMapping.cc:247-278): frame1 against pairs[p].frame2, one wavefront per (pair, KF1 feature)
+ *     (k_triangulation_frames).  Both sides must have been created with uright (ORB_ERR_ARG otherwise); frame1's
+ *     FeatureVector must list no feature twice (one built by orb_frame_compute_bow never does); nlevels2 outside
+ *     [1, ORBGPU_MAX_LEVELS] or a frame2 keypoint octave outside [0, nlevels2) is ORB_ERR_ARG; at most 65535 pairs.
+ *     ORB_ERR_CAPACITY as the batch call: every *npairs holds its full count.
+ *   orb_search_by_bow_frames_kf_f   = orb_search_by_bow_kf_f_batch (Tracking::TrackReferenceKeyFrame,
+ *     Tracking.cc:766-772, and Relocalization, :1931-1938): keyframe kfs[p].frame with its map-point flags mp against
+ *     the Frame frame_f; match: frame_f's n ints.  The items are built on the device (k_bow_items).
+ *   orb_search_by_bow_frames_kf_kf  = orb_search_by_bow_kf_kf (one KF2; loop closing's callers loop over it). */
+typedef struct orb_tri_frame_pair {
+    const orb_frame* frame2;
+    const uint8_t* has_mp2;
+    const float* F12;            /* row-major 3x3 */
+    float ex, ey;
+    const float* scale2;         /* pKF2->mvScaleFactors, nlevels2 entries */
+    const float* sigma2_2;       /* pKF2->mvLevelSigma2 */
+    int nlevels2;
+    int* pairs_out;              /* 2 ints per pair */
+    int cap;
+    int* npairs;
+} orb_tri_frame_pair;
+int orb_search_for_triangulation_frames(orb_ctx* ctx, int check_ori, int only_stereo, const orb_frame* frame1,
+                                        const uint8_t* has_mp1, int npairs, const orb_tri_frame_pair* pairs);
+typedef struct orb_bow_frame_kf {
+    const orb_frame* frame;
+    const uint8_t* mp;
+    int* match;
+    int* nmatches;
+} orb_bow_frame_kf;
+int orb_search_by_bow_frames_kf_f(orb_ctx* ctx, float nnratio, int check_ori, const orb_frame* frame_f, int nkf,
+                                  const orb_bow_frame_kf* kfs);
+int orb_search_by_bow_frames_kf_kf(orb_ctx* ctx, float nnratio, int check_ori, const orb_frame* kf1, const uint8_t* mp1,
+                                   const orb_frame* kf2, const uint8_t* mp2, int* match12, int* nmatches);
 
 /* The grid searches with a handle as their train side: every output is byte for byte that of the host-pointer entry
  * point given the same train data and a grid equal to the handle's, and every argument check of that entry point

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "orbgpu_internal.h"
+#include "tri_geometry.h"
 
 namespace orbgpu {
 
@@ -411,6 +412,149 @@ __global__ __launch_bounds__(256) void k_triangulation(const TriItem* __restrict
     }
     bestKey = wave_min_u64(bestKey);
     if (lane == 0) best_out[it] = bestKey != ~0ull ? c0 + (0x7FFFFFFF - (int)(bestKey & 0xFFFFFFFFu)) : -1;
+}
+
+/* SearchForTriangulation (ORBmatcher.cc:684-761) between two resident frames, one wavefront per (pair, KF1 feature):
+ * the feature's node is looked up in KF2's FeatureVector (a wave-uniform binary search), the lanes stride the node's
+ * candidates in CSR order, and the pair's float work (tri_geometry.h) runs here instead of on staged records.  The
+ * tests and the key are k_triangulation's; a candidate's position is its place in the node's CSR order (the host
+ * form numbers the candidates that pass the map-point / stereo filter, in the same order: the same winner).
+ * Reads: node_of / has_mp / ur / kps / desc of KF1 at idx1 < n1; fv_nodes[0, nnodes), fv_off[0, nnodes], fv_idx below
+ * fv_off[nnodes]; KF2's arrays at fv_idx's entries (< n2, featvec_ok or k_frame_featvec); scale2 / sigma2 at a KF2
+ * octave (the host checked the frame's octaves against nlevels2).  Writes best_out[pair * n1 + idx1]. */
+__global__ __launch_bounds__(256) void k_triangulation_frames(TriFrameKf1 A, const TriFramePair* __restrict__ tab,
+                                                              int only_stereo, int* __restrict__ best_out) {
+    const int idx1 = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (idx1 >= A.n) return;
+    const int p = blockIdx.y;
+    int* const out = best_out + (long long)p * A.n + idx1;
+    const uint32_t nd = A.node_of[idx1];
+    const bool st1 = A.ur[idx1] >= 0;
+    // a map point already (:694-696), outside KF1's FeatureVector, or mono under bOnlyStereo (:698-702)
+    if (A.has_mp[idx1] || nd == 0xFFFFFFFFu || (only_stereo && !st1)) {
+        if (lane == 0) *out = -1;
+        return;
+    }
+    const TriFramePair& P = tab[p];
+    int lo = 0, hi = P.nnodes;   // the first node of KF2 not below nd
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (P.fv_nodes[mid] < nd) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= P.nnodes || P.fv_nodes[lo] != nd) {
+        if (lane == 0) *out = -1;
+        return;
+    }
+    const int c0 = P.fv_off[lo], c1 = P.fv_off[lo + 1];
+    const uint4* qp = reinterpret_cast<const uint4*>(A.desc + (long long)idx1 * 32);
+    const uint4 qa = qp[0], qb = qp[1];
+    const orb_keypoint k1 = A.kps[idx1];
+    float la, lb, lc;
+    tri_line(k1.x, k1.y, P.F, la, lb, lc);
+    const float den = __builtin_fmaf(la, la, lb * lb);
+    unsigned long long bestKey = ~0ull;
+    for (int pos = c0 + lane; pos < c1; pos += 64) {
+        const int i2 = P.fv_idx[pos];
+        if (P.has_mp[i2]) continue;                    // :725-727
+        const bool st2 = P.ur[i2] >= 0;
+        if (only_stereo && !st2) continue;             // :729-733
+        const uint4* tp = reinterpret_cast<const uint4*>(P.desc + (long long)i2 * 32);
+        const int dist = hamming256(qa, qb, tp[0], tp[1]);
+        if (dist > 50) continue;
+        const orb_keypoint& k2 = P.kps[i2];
+        const float x2 = k2.x, y2 = k2.y;
+        const int oct = k2.octave;
+        if (!st1 && !st2 && tri_near_epipole(P.ex, P.ey, x2, y2, P.scale2, oct)) continue;   // :743-748
+        if (den == 0) continue;
+        const float num = __builtin_fmaf(lb, y2, la * x2) + lc;
+        const float dsqr = num * num / den;
+        if (!((double)dsqr < 3.84 * (double)tri_sigma2(P.sigma2, oct))) continue;
+        const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(0x7FFFFFFF - (pos - c0));
+        bestKey = key < bestKey ? key : bestKey;
+    }
+    bestKey = wave_min_u64(bestKey);
+    if (lane == 0) *out = bestKey != ~0ull ? P.fv_idx[c0 + (0x7FFFFFFF - (int)(bestKey & 0xFFFFFFFFu))] : -1;
+}
+
+/* The items of SearchByBoW between resident frames, one workgroup per keyframe of the batch: every position k of the
+ * query side's FeatureVector CSR, in order (ascending node, then the node's order: the reference's iteration order),
+ * is an item iff its node is also a node of the train side and the feature's flag is set.  The kept positions are
+ * compacted in order (ballot + wave counts) to [seg0, seg0 + len); an item gets its feature index, its candidate range
+ * in the train CSR and its descriptor, item-major, for k_topk.  The rest of the segment gets an empty range, so one
+ * k_topk launch over every segment's capacity ranks nothing there.
+ * Reads: q_off[0, q_nnodes], q_nodes / t_nodes below their counts, t_off[b + 1] with b < t_nnodes, q_idx[k] with
+ * k < q_nnz, q_flag / q_desc at q_idx's entries.  Writes: the segment's q_nnz slots of the three arrays, seg_len[p]. */
+__global__ __launch_bounds__(256) void k_bow_items(const BowItemsRow* __restrict__ tab, int* __restrict__ item_q,
+                                                   int2* __restrict__ item_rng, uint8_t* __restrict__ qbuf,
+                                                   int* __restrict__ seg_len) {
+    __shared__ int s_wave[4];
+    const BowItemsRow R = tab[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int done = 0;
+    for (int k0 = 0; k0 < R.q_nnz; k0 += 256) {   // (uniform trip count)
+        const int k = k0 + tid;
+        bool keep = false;
+        int feat = 0;
+        int2 rng = make_int2(0, 0);
+        if (k < R.q_nnz) {
+            int lo = 0, hi = R.q_nnodes;   // the first node whose offset is above k (q_off[q_nnodes] = q_nnz > k)
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (R.q_off[mid] <= k) lo = mid + 1;
+                else hi = mid;
+            }
+            const uint32_t nd = R.q_nodes[lo - 1];   // (q_off[0] = 0 <= k: lo >= 1)
+            int b = 0, e = R.t_nnodes;
+            while (b < e) {
+                const int mid = (b + e) >> 1;
+                if (R.t_nodes[mid] < nd) b = mid + 1;
+                else e = mid;
+            }
+            feat = R.q_idx[k];
+            if (b < R.t_nnodes && R.t_nodes[b] == nd && R.q_flag[feat]) {
+                keep = true;
+                rng = make_int2(R.rng_base + R.t_off[b], R.rng_base + R.t_off[b + 1]);
+            }
+        }
+        const unsigned long long m = __ballot(keep);
+        __syncthreads();   // the previous step's s_wave has been read
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int pos = done + __popcll(m & ((1ull << lane) - 1ull)), total = 0;
+        for (int w = 0; w < 4; w++) {
+            if (w < wave) pos += s_wave[w];
+            total += s_wave[w];
+        }
+        if (keep) {   // pos < the number of kept positions <= q_nnz
+            const long long o = (long long)R.seg0 + pos;
+            item_q[o] = feat;
+            item_rng[o] = rng;
+            const uint4* src = reinterpret_cast<const uint4*>(R.q_desc + (long long)feat * 32);
+            uint4* dst = reinterpret_cast<uint4*>(qbuf + o * 32);
+            dst[0] = src[0];
+            dst[1] = src[1];
+        }
+        done += total;
+    }
+    for (int k = done + tid; k < R.q_nnz; k += 256) item_rng[(long long)R.seg0 + k] = make_int2(0, 0);
+    if (tid == 0) seg_len[blockIdx.x] = done;
+}
+
+hipError_t launch_triangulation_frames(const TriFrameKf1& a, const TriFramePair* d_tab, int npairs, int only_stereo,
+                                       int* best_out, hipStream_t stream) {
+    if (npairs <= 0 || a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_triangulation_frames, dim3((a.n + 3) / 4, npairs), dim3(256), 0, stream, a, d_tab, only_stereo,
+                       best_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_bow_items(const BowItemsRow* d_tab, int nkf, int* item_q, int2* d_item_rng, uint8_t* d_qbuf,
+                            int* seg_len, hipStream_t stream) {
+    if (nkf <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_bow_items, dim3(nkf), dim3(256), 0, stream, d_tab, item_q, d_item_rng, d_qbuf, seg_len);
+    return hipGetLastError();
 }
 
 hipError_t launch_hamming_topk(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, const int2* d_ranges,

@@ -16,8 +16,27 @@
 #include "orbgpu_ctx.h"
 #include "point_project.h"
 #include "topk_scan.h"
+#include "tri_geometry.h"
 
 namespace orbgpu {
+
+// A FeatureVector CSR the walks below can trust: offsets start at 0 and never decrease (so the features of the
+// nodes a walk visits number at most offsets[nnodes], the size the staging is allocated for), every feature index
+// lies in [0, n) (the walks index the descriptors, keypoints and map-point flags with it), and node ids ascend
+// strictly (for_common_nodes is the std::map merge, which assumes ordered unique keys).  O(nnodes + nnz).
+bool featvec_ok(const orb_featvec& v, int n) {
+    if (v.nnodes < 0 || (v.nnodes > 0 && (!v.offsets || !v.indices || !v.node_ids))) return false;
+    if (v.nnodes == 0) return true;
+    if (v.offsets[0] != 0) return false;
+    for (int i = 0; i < v.nnodes; i++) {
+        if (v.offsets[i + 1] < v.offsets[i]) return false;
+        if (i > 0 && v.node_ids[i] <= v.node_ids[i - 1]) return false;
+    }
+    for (int k = 0; k < v.offsets[v.nnodes]; k++)
+        if (v.indices[k] < 0 || v.indices[k] >= n) return false;
+    return true;
+}
+
 namespace {
 
 constexpr int TH_LOW = 50;          // ORBmatcher.cc:38
@@ -73,23 +92,6 @@ void cull_rotation_all(const std::vector<int>* rotHist, std::vector<int>& matche
         if (i == i1 || i == i2 || i == i3) continue;
         for (int q : rotHist[i]) { matches[q] = reset_value; nmatches--; }
     }
-}
-
-// A FeatureVector CSR the walks below can trust: offsets start at 0 and never decrease (so the features of the
-// nodes a walk visits number at most offsets[nnodes], the size the staging is allocated for), every feature index
-// lies in [0, n) (the walks index the descriptors, keypoints and map-point flags with it), and node ids ascend
-// strictly (for_common_nodes is the std::map merge, which assumes ordered unique keys).  O(nnodes + nnz).
-bool featvec_ok(const orb_featvec& v, int n) {
-    if (v.nnodes < 0 || (v.nnodes > 0 && (!v.offsets || !v.indices || !v.node_ids))) return false;
-    if (v.nnodes == 0) return true;
-    if (v.offsets[0] != 0) return false;
-    for (int i = 0; i < v.nnodes; i++) {
-        if (v.offsets[i + 1] < v.offsets[i]) return false;
-        if (i > 0 && v.node_ids[i] <= v.node_ids[i - 1]) return false;
-    }
-    for (int k = 0; k < v.offsets[v.nnodes]; k++)
-        if (v.indices[k] < 0 || v.indices[k] >= n) return false;
-    return true;
 }
 
 template <class F>
@@ -236,12 +238,21 @@ struct TopkSession {
     }
     // device_queries: the queries and their descriptors are written on the device (setup_points): their regions come
     // last, past the end of the pinned mirror
-    int finish_layout(bool device_queries = false) {
+    // resident_kfs > 0: the items are written on the device (setup_bow_frames): item_q and the segment lengths come
+    // down in the mirror beside the lists, the item-major queries and the ranges are device-only regions
+    int finish_layout(bool device_queries = false, int resident_kfs = 0) {
         o_thr = st.add((size_t)nt * 4);
         o_in_end = st.off;
         o_dist = st.add((size_t)nitems * K * 4);
         o_idx = st.add((size_t)nitems * K * 4);
         o_nv = st.add((size_t)nitems * 4);
+        if (resident_kfs > 0) {
+            o_itemq = st.add((size_t)nitems * 4);
+            o_seglen = st.add((size_t)resident_kfs * 4);
+            st.end_mirror();
+            o_q = st.add((size_t)nitems * 32);
+            o_rng = st.add((size_t)nitems * 8);
+        }
         if (device_queries) {
             st.end_mirror();
             o_pq = st.add((size_t)nitems * sizeof(orb_proj_query));
@@ -353,6 +364,62 @@ struct TopkSession {
         return ORB_OK;
     }
 
+    // List mode between resident frames (orb_search_by_bow_frames_*): keyframe p's queries are the features of
+    // kfs[p].q's FeatureVector that share a node with `train`'s and whose flag is set, its items the segment
+    // [seg0_p, seg0_p + nnz_p) of the session (seg0_p = the earlier keyframes' CSR lengths), of which k_bow_items,
+    // queued here, fills the first seg_len[p].  The trains and the candidate list are the train frame's descriptors
+    // and its FeatureVector's indices: only [table | flags] go up.  fetch_items() after the first run() brings
+    // item_q and each keyframe's [first, last) to the host.
+    struct BowFrameKf {
+        const orb_frame* q;
+        const uint8_t* flag;
+    };
+    const uint8_t* r_t = nullptr;
+    const int* r_cand = nullptr;
+    size_t o_itemq = 0, o_seglen = 0;
+    std::vector<int> seg0;
+    int setup_bow_frames(int nkf, const BowFrameKf* kfs, const orb_frame* train) {
+        long long cap = 0;
+        seg0.assign(nkf + 1, 0);
+        for (int p = 0; p < nkf; p++) seg0[p + 1] = (int)(cap += kfs[p].q->bow->nnz);
+        if (cap > INT_MAX / 64) return arg_error("orb_search_by_bow_frames", "too many features");
+        if (!begin(LIST, (int)cap, train->n)) return ORB_OK;
+        const size_t o_tab = st.add((size_t)nkf * sizeof(BowItemsRow));
+        std::vector<size_t> o_flag(nkf);
+        for (int p = 0; p < nkf; p++) o_flag[p] = st.add((size_t)kfs[p].q->n);
+        const size_t in_end = st.off;
+        const int r = finish_layout(false, nkf);
+        if (r != ORB_OK) return r;
+        const orb_frame_bow* T = train->bow;
+        BowItemsRow* tab = st.hi<BowItemsRow>(o_tab);
+        for (int p = 0; p < nkf; p++) {
+            const orb_frame* Q = kfs[p].q;
+            const orb_frame_bow* B = Q->bow;
+            st.put(o_flag[p], kfs[p].flag, (size_t)Q->n);
+            tab[p] = BowItemsRow{B->d<uint32_t>(B->L.o_nodes), B->d<int>(B->L.o_off), B->d<int>(B->L.o_idx), Q->d_desc,
+                                 st.d<uint8_t>(o_flag[p]), T->d<uint32_t>(T->L.o_nodes), T->d<int>(T->L.o_off),
+                                 B->nnodes, B->nnz, T->nnodes, seg0[p], 0, 0};
+        }
+        r_t = train->d_desc;
+        r_cand = T->d<int>(T->L.o_idx);
+        hipError_t e;
+        if ((e = st.up(0, in_end)) != hipSuccess) return set_error("upload", e), ORB_ERR_HIP;
+        if ((e = launch_bow_items(st.d<BowItemsRow>(o_tab), nkf, st.h<int>(o_itemq), st.d<int2>(o_rng),
+                                  st.d<uint8_t>(o_q), st.h<int>(o_seglen), c->stream)) != hipSuccess)
+            return set_error("k_bow_items", e), ORB_ERR_HIP;
+        uploaded = true;
+        return ORB_OK;
+    }
+    // keyframe p's live items [first[p], last[p]) and item_q, once run() has synchronised
+    void fetch_items(std::vector<int>& first, std::vector<int>& last) {
+        const int nkf = (int)seg0.size() - 1;
+        first.assign(seg0.begin(), seg0.begin() + nkf);
+        last = first;
+        if (nitems <= 0) return;
+        item_q.assign(st.h<int>(o_itemq), st.h<int>(o_itemq) + nitems);
+        for (int p = 0; p < nkf; p++) last[p] = first[p] + std::min(st.h<int>(o_seglen)[p], seg0[p + 1] - seg0[p]);
+    }
+
     // Rank items [from, to) (to < 0: nitems) with train thresholds thr (NULL = admit all).
     int run(int from, const int* thr, int to = -1) {
         const int n = (to < 0 ? nitems : to) - from;
@@ -384,9 +451,9 @@ struct TopkSession {
                                    out_nv, c->stream);
             break;
         case LIST:
-            e = launch_hamming_topk(st.di<uint8_t>(o_q) + (size_t)from * 32, n, st.di<uint8_t>(o_t), nt,
-                                    st.di<int2>(o_rng) + from, st.di<int>(o_cand), d_thr, K, out_dist, out_idx, out_nv,
-                                    c->stream);
+            e = launch_hamming_topk(st.di<uint8_t>(o_q) + (size_t)from * 32, n, r_t ? r_t : st.di<uint8_t>(o_t), nt,
+                                    st.di<int2>(o_rng) + from, r_cand ? r_cand : st.di<int>(o_cand), d_thr, K, out_dist,
+                                    out_idx, out_nv, c->stream);
             break;
         }
         if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 0, c->stream);
@@ -544,6 +611,52 @@ int bow_kf_kf_run(Ctx* c, float nnratio, int check_ori, int n1, const uint8_t* d
         st = bow_kf_kf_replay(s, first[p], first[p + 1], tb[p], thr, nnratio, check_ori, n1, angle1, kf2s[p].n,
                               kf2s[p].angle, kf2s[p].mp, kf2s[p].match, kf2s[p].nmatches);
     return st;
+}
+
+// The BoW searches between resident frames: the items come from k_bow_items, the lists from k_topk over the train
+// frame's own arrays, the acceptance from the replays above, with the angles of the handles' host keypoints.
+std::vector<float> frame_angles(const orb_frame* F) {
+    std::vector<float> a((size_t)F->n);
+    for (int i = 0; i < F->n; i++) a[i] = F->kps[i].angle;
+    return a;
+}
+
+int bow_frames_kf_f_run(Ctx* c, float nnratio, int check_ori, const orb_frame* Ff, int nkf, const orb_bow_frame_kf* kfs) {
+    TopkSession s{c};
+    std::vector<TopkSession::BowFrameKf> q(nkf);
+    for (int p = 0; p < nkf; p++) q[p] = TopkSession::BowFrameKf{kfs[p].frame, kfs[p].mp};
+    int st = s.setup_bow_frames(nkf, q.data(), Ff);
+    if (st == ORB_OK) st = s.run(0, nullptr);
+    if (st != ORB_OK) return st;
+    std::vector<int> first, last;
+    s.fetch_items(first, last);
+    const std::vector<float> angle_f = frame_angles(Ff);
+    for (int p = 0; p < nkf && st == ORB_OK; p++)
+        st = bow_kf_f_replay(s, first[p], last[p], nnratio, check_ori, Ff->n, frame_angles(kfs[p].frame).data(),
+                             angle_f.data(), kfs[p].match, kfs[p].nmatches);
+    return st;
+}
+
+int bow_frames_kf_kf_run(Ctx* c, float nnratio, int check_ori, const orb_frame* F1, const uint8_t* mp1,
+                         const orb_frame* F2, const uint8_t* mp2, int* match12, int* nmatches) {
+    TopkSession s{c};
+    const TopkSession::BowFrameKf q{F1, mp1};
+    std::vector<int> thr((size_t)F2->n);
+    for (int t = 0; t < F2->n; t++) thr[t] = mp2[t] ? INT_MAX : -1;   // !pMP2 || isBad (:584-588)
+    int st = s.setup_bow_frames(1, &q, F2);
+    if (st == ORB_OK) st = s.run(0, thr.data());
+    if (st != ORB_OK) return st;
+    std::vector<int> first, last;
+    s.fetch_items(first, last);
+    return bow_kf_kf_replay(s, first[0], last[0], 0, thr, nnratio, check_ori, F1->n, frame_angles(F1).data(), F2->n,
+                            frame_angles(F2).data(), mp2, match12, nmatches);
+}
+
+// What is wrong with a handle the vocabulary-gated searches take, or NULL
+const char* bow_frame_fault(const orb_frame* F) {
+    if (!F) return "NULL frame";
+    if (!F->bow) return "a frame carries no BoW";
+    return nullptr;
 }
 
 }  // namespace
@@ -761,6 +874,37 @@ int orb_search_by_bow_kf_kf_batch(orb_ctx* h, float nnratio, int check_ori, int 
     return nkf ? bow_kf_kf_run(c, nnratio, check_ori, n1, desc1, angle1, mp1, fv1, nkf, kf2s) : ORB_OK;
 }
 
+int orb_search_by_bow_frames_kf_f(orb_ctx* h, float nnratio, int check_ori, const orb_frame* frame_f, int nkf,
+                                  const orb_bow_frame_kf* kfs) {
+    const char* const fn = "orb_search_by_bow_frames_kf_f";
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (nkf < 0 || (nkf > 0 && !kfs)) return arg_error(fn, "bad arguments");
+    if (const char* why = bow_frame_fault(frame_f)) return arg_error(fn, why);
+    for (int p = 0; p < nkf; p++) {
+        if (const char* why = bow_frame_fault(kfs[p].frame)) return arg_error(fn, why);
+        if (kfs[p].frame->device != frame_f->device) return arg_error(fn, "frames of different devices");
+        if (!kfs[p].match || (kfs[p].frame->n > 0 && !kfs[p].mp)) return arg_error(fn, "bad keyframe arguments");
+    }
+    if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
+    if (frame_f->device != c->device) return arg_error(fn, "frame of another device");
+    CTX_GUARD(c);
+    return nkf ? bow_frames_kf_f_run(c, nnratio, check_ori, frame_f, nkf, kfs) : ORB_OK;
+}
+
+int orb_search_by_bow_frames_kf_kf(orb_ctx* h, float nnratio, int check_ori, const orb_frame* kf1, const uint8_t* mp1,
+                                   const orb_frame* kf2, const uint8_t* mp2, int* match12, int* nmatches) {
+    const char* const fn = "orb_search_by_bow_frames_kf_kf";
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (const char* why = bow_frame_fault(kf1)) return arg_error(fn, why);
+    if (const char* why = bow_frame_fault(kf2)) return arg_error(fn, why);
+    if (!match12 || (kf1->n > 0 && !mp1) || (kf2->n > 0 && !mp2)) return arg_error(fn, "bad arguments");
+    if (kf1->device != kf2->device) return arg_error(fn, "frames of different devices");
+    if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
+    if (kf1->device != c->device) return arg_error(fn, "frame of another device");
+    CTX_GUARD(c);
+    return bow_frames_kf_kf_run(c, nnratio, check_ori, kf1, mp1, kf2, mp2, match12, nmatches);
+}
+
 /* SearchForTriangulation  ORBmatcher.cc:657-823: no cross-query dependence (vbMatched2 is never
  * set, :738), so every (idx1, node) item is decided on the GPU. */
 }  // extern "C"
@@ -825,16 +969,13 @@ __attribute__((always_inline)) inline void tri_geometry_body(TriItem* items, int
     for (int i = ib; i < ie; i++) {
         TriItem& q = items[i];
         const float x = q.la, y = q.lb;
-        q.la = __builtin_fmaf(x, F[0], y * F[3]) + F[6];
-        q.lb = __builtin_fmaf(x, F[1], y * F[4]) + F[7];
-        q.lc = __builtin_fmaf(y, F[5], x * F[2]) + F[8];
+        tri_line(x, y, F, q.la, q.lb, q.lc);
     }
     for (int j = tb; j < te; j++) {
         TriTrain& t = trains[j];
         const int oct = (int)t.sigma2;
-        const float dex = ex - t.x, dey = ey - t.y;
-        if (__builtin_fmaf(dex, dex, dey * dey) < 100 * scale2[oct]) t.flags |= 2;
-        t.sigma2 = sigma2[oct];
+        if (tri_near_epipole(ex, ey, t.x, t.y, scale2, oct)) t.flags |= 2;
+        t.sigma2 = tri_sigma2(sigma2, oct);
     }
 }
 #if !defined(__HIP_DEVICE_COMPILE__)   // (host code: the x86-64 FMA form and its dispatch)
@@ -986,6 +1127,107 @@ int orb_search_for_triangulation_batch(orb_ctx* h, int check_ori, int only_stere
         if (!tri_pair_ok(pairs[p])) return arg_error("orb_search_for_triangulation_batch", "bad pair arguments");
     if (npairs == 0) return ORB_OK;
     return tri_run(c, check_ori, only_stereo, TriSide{n1, desc1, kps1, has_mp1, uright1, fv1}, npairs, pairs);
+}
+
+int orb_search_for_triangulation_frames(orb_ctx* h, int check_ori, int only_stereo, const orb_frame* F1,
+                                        const uint8_t* has_mp1, int npairs, const orb_tri_frame_pair* pairs) {
+    const char* const fn = "orb_search_for_triangulation_frames";
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    const auto side_fault = [](const orb_frame* F) -> const char* {
+        if (!F) return "NULL frame";
+        if (!F->bow) return "a frame carries no BoW";
+        if (!F->has_ur) return "a frame was created without uright";
+        return nullptr;
+    };
+    if (npairs < 0 || npairs > 65535 || (npairs > 0 && !pairs)) return arg_error(fn, "bad arguments");
+    for (int p = 0; p < npairs; p++)
+        if (pairs[p].nlevels2 < 1 || pairs[p].nlevels2 > ORBGPU_MAX_LEVELS)
+            return arg_error(fn, "nlevels2 outside [1, ORBGPU_MAX_LEVELS]");
+    if (const char* why = side_fault(F1)) return arg_error(fn, why);
+    // k_triangulation_frames finds a KF1 feature's node in a per-feature array: one node per feature
+    if (!F1->bow->unique) return arg_error(fn, "frame1's FeatureVector lists a feature twice");
+    if (F1->n > 0 && !has_mp1) return arg_error(fn, "bad arguments");
+    for (int p = 0; p < npairs; p++) {
+        const orb_tri_frame_pair& P = pairs[p];
+        if (const char* why = side_fault(P.frame2)) return arg_error(fn, why);
+        if (P.frame2->device != F1->device) return arg_error(fn, "frames of different devices");
+        if (!P.npairs || !P.F12 || !P.scale2 || !P.sigma2_2 || (P.frame2->n > 0 && !P.has_mp2))
+            return arg_error(fn, "bad pair arguments");
+        // the kernel indexes scale2 / sigma2_2 with the octaves of frame2's keypoints
+        if (P.frame2->n > 0 && (P.frame2->oct_min < 0 || P.frame2->oct_max >= P.nlevels2))
+            return arg_error(fn, "a frame2 octave outside [0, nlevels2)");
+    }
+    if (!c) return set_error("NULL context", hipSuccess), ORB_ERR_ARG;
+    if (F1->device != c->device) return arg_error(fn, "frame of another device");
+    CTX_GUARD(c);
+    if (npairs == 0) return ORB_OK;
+    const int n1 = F1->n;
+    const orb_frame_bow* B1 = F1->bow;
+    // [table | has_mp1 | has_mp2 ...] go up in one DMA (every candidate's flag is read by each KF1 feature of its
+    // node: device memory, not the pinned mirror); the kernel stores its results into the mirror
+    Stage st{c};
+    const size_t o_tab = st.add((size_t)npairs * sizeof(TriFramePair)), o_f1 = st.add((size_t)n1);
+    std::vector<size_t> o_f2(npairs);
+    for (int p = 0; p < npairs; p++) o_f2[p] = st.add((size_t)pairs[p].frame2->n);
+    const size_t in_end = st.off, o_out = st.add((size_t)npairs * (size_t)n1 * 4);
+    if (n1 > 0) {
+        if ((size_t)npairs * (size_t)n1 > (size_t)INT_MAX / 2) return arg_error(fn, "too many records");
+        const int r = st.alloc();
+        if (r != ORB_OK) return r;
+        TriFramePair* tab = st.hi<TriFramePair>(o_tab);
+        st.put(o_f1, has_mp1, (size_t)n1);
+        for (int p = 0; p < npairs; p++) {
+            const orb_tri_frame_pair& P = pairs[p];
+            const orb_frame* F2 = P.frame2;
+            const orb_frame_bow* B2 = F2->bow;
+            st.put(o_f2[p], P.has_mp2, (size_t)F2->n);
+            TriFramePair& T = tab[p];
+            T = TriFramePair{};
+            T.desc = F2->d_desc;
+            T.kps = F2->d_kps;
+            T.ur = F2->d_ur;
+            T.fv_nodes = B2->d<uint32_t>(B2->L.o_nodes);
+            T.fv_off = B2->d<int>(B2->L.o_off);
+            T.fv_idx = B2->d<int>(B2->L.o_idx);
+            T.has_mp = st.d<uint8_t>(o_f2[p]);
+            T.nnodes = B2->nnodes;
+            T.ex = P.ex;
+            T.ey = P.ey;
+            std::memcpy(T.F, P.F12, sizeof(T.F));
+            std::memcpy(T.scale2, P.scale2, (size_t)P.nlevels2 * 4);
+            std::memcpy(T.sigma2, P.sigma2_2, (size_t)P.nlevels2 * 4);
+        }
+        hipError_t e;
+        if ((e = st.up(0, in_end)) != hipSuccess) return set_error("upload", e), ORB_ERR_HIP;
+        const TriFrameKf1 A{F1->d_desc, F1->d_kps, F1->d_ur, B1->d<uint32_t>(B1->L.o_nodeof), st.d<uint8_t>(o_f1), n1};
+        if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 1, c->stream);
+        e = launch_triangulation_frames(A, st.d<TriFramePair>(o_tab), npairs, only_stereo, st.h<int>(o_out), c->stream);
+        if (c->prof_on) Ctx::marker(c, ORB_K_HAMMING, 0, c->stream);
+        if (e != hipSuccess) return set_error("triangulation kernel", e), ORB_ERR_HIP;
+        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_error("download", e), ORB_ERR_HIP;
+    }
+    // the replay's items: KF1's FeatureVector in CSR order, once per pair (a feature outside it matches nothing)
+    const orb_featvec fv1 = B1->featvec();
+    const int nnz1 = B1->nnz;
+    std::vector<int>& item_q = c->tri_item_q;
+    std::vector<int>& best = c->tri_best;
+    item_q.resize((size_t)npairs * nnz1);
+    best.resize((size_t)npairs * nnz1);
+    const int* out = n1 > 0 ? st.h<int>(o_out) : nullptr;
+    int rc = ORB_OK;
+    for (int p = 0; p < npairs; p++) {
+        const orb_tri_frame_pair& P = pairs[p];
+        const size_t ib = (size_t)p * nnz1;
+        for (int k = 0; k < nnz1; k++) {
+            item_q[ib + k] = fv1.indices[k];
+            best[ib + k] = out[(size_t)p * n1 + fv1.indices[k]];
+        }
+        if (tri_replay_pair(c, check_ori, n1, F1->kps.data(), P.frame2->kps.data(), (int)ib, (int)ib + nnz1, best.data(),
+                            P.pairs_out, P.cap, P.npairs) != ORB_OK)
+            rc = ORB_ERR_CAPACITY;
+    }
+    if (rc != ORB_OK) set_error("pairs_out too small", hipSuccess);
+    return rc;
 }
 
 }  // extern "C"

@@ -296,6 +296,53 @@ struct Stage {
 
 }  // namespace orbgpu
 
+// A resident frame's BoW part (frame_bow.hip): an allocation of its own, laid out by bow_layout() as
+// [meta | fv_nodes | fv_off | fv_idx | node_of | word | weight | tnode], each region 256-byte aligned:
+//   meta     2 ints: nnodes, nnz (written by k_frame_featvec; the host copy is authoritative after the attach)
+//   fv_*     the FeatureVector as CSR: node ids strictly ascending, nnodes + 1 offsets, a node's features ascending
+//            (n, n + 1 and n slots, or as many as a given CSR holds)
+//   node_of  per feature its FeatureVector node, kBowNoNode outside the FeatureVector
+//   word / weight / tnode   k_vocab_transform's per-feature triples (orb_frame_compute_bow only)
+// `h` is the host copy of the whole allocation, filled by the attach's one synchronisation (orb_frame_compute_bow) or
+// built on the host and uploaded (orb_frame_set_featvec); the replays and orb_frame_bow_read use it.
+namespace orbgpu {
+constexpr uint32_t kBowNoNode = 0xFFFFFFFFu;
+struct BowLayout {
+    size_t o_nodes, o_off, o_idx, o_nodeof, o_word, o_weight, o_tnode, bytes;
+};
+// n features, room for ncap nodes and icap indices (n of each for a FeatureVector transform() builds; a given one may
+// hold empty nodes and list a feature twice)
+inline BowLayout bow_layout(int n, int ncap, int icap, bool triples) {
+    const auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nn = (size_t)n;
+    BowLayout L{};
+    L.o_nodes = 256;
+    L.o_off = al(L.o_nodes + (size_t)ncap * 4);
+    L.o_idx = al(L.o_off + ((size_t)ncap + 1) * 4);
+    L.o_nodeof = al(L.o_idx + (size_t)icap * 4);
+    L.o_word = al(L.o_nodeof + nn * 4);
+    L.o_weight = triples ? al(L.o_word + nn * 4) : L.o_word;
+    L.o_tnode = triples ? al(L.o_weight + nn * 4) : L.o_word;
+    L.bytes = triples ? al(L.o_tnode + nn * 4) : L.o_word;
+    return L;
+}
+}  // namespace orbgpu
+struct orb_frame_bow {
+    orbgpu::DevBuf<uint8_t> d_base;
+    std::vector<uint8_t> h;
+    orbgpu::BowLayout L{};
+    bool triples = false;
+    bool unique = true;   // no feature is listed twice (a FeatureVector built by transform(); a given one may)
+    int nnodes = 0, nnz = 0;
+    template <class T>
+    const T* d(size_t o) const { return reinterpret_cast<const T*>(d_base.get() + o); }
+    template <class T>
+    const T* hp(size_t o) const { return reinterpret_cast<const T*>(h.data() + o); }
+    orb_featvec featvec() const {   // the host CSR copy
+        return orb_featvec{nnodes, hp<uint32_t>(L.o_nodes), hp<int>(L.o_off), hp<int>(L.o_idx)};
+    }
+};
+
 // A device-resident Frame / KeyFrame (the object behind the opaque orb_frame*, frame.hip): the train side of the grid
 // searches, uploaded once.  One device allocation holds [desc | kps | uright | cell_off | cell_idx], each region
 // 256-byte aligned; cell_off / cell_idx are the Frame grid k_frame_grid built from the keypoints.  The host keeps the
@@ -313,9 +360,37 @@ struct orb_frame {
     const int* d_cidx = nullptr;   // n slots (cell_off[kFrameGridCells] of them used)
     std::vector<orb_keypoint> kps;
     int oct_min = 0, oct_max = -1;   // the octaves of kps, found once by the creator (n > 0)
+    // the optional BoW part, owned (orb_frame_compute_bow / orb_frame_set_featvec attach it; again: replace it)
+    orb_frame_bow* bow = nullptr;
+    orb_frame() = default;
+    orb_frame(const orb_frame&) = delete;
+    orb_frame& operator=(const orb_frame&) = delete;
+    ~orb_frame() { delete bow; }
 };
 
 namespace orbgpu {
+
+// A FeatureVector CSR the walks can trust (matcher.hip): offsets start at 0 and never decrease, every feature index
+// lies in [0, n), node ids ascend strictly.  O(nnodes + nnz).
+bool featvec_ok(const orb_featvec& v, int n);
+
+// vocab.hip, for frame_bow.hip (orb_vocab is defined there).  One k_vocab_transform launch over nframes resident
+// frames: row f of d_tab names frame f's descriptors, count and the three output arrays; max_n the largest count.
+struct VocabFrameRow {
+    const uint8_t* desc;
+    int* word;
+    float* weight;
+    uint32_t* node;
+    int n;
+    int pad;
+};
+hipError_t launch_vocab_transform_frames(const orb_vocab* v, int levelsup, const VocabFrameRow* d_tab, int nframes,
+                                         int max_n, hipStream_t stream);
+int vocab_device(const orb_vocab* v);
+bool vocab_empty(const orb_vocab* v);   // no words: transform() returns empty vectors
+// orb_vocab_bow's BowVector half (words ascending, values in double, summed in feature order, normalised): the count
+int vocab_bow_vector(const orb_vocab* v, int n, const int* word_id, const float* weight, int* bow_words,
+                     double* bow_values);
 
 // The one place the handle is laid out (frame.hip): F for n keypoints over grid g, its allocation made, the five device
 // pointers set (d_ur only with has_ur), the host keypoint copy sized but not filled.  nullptr, or the step that failed

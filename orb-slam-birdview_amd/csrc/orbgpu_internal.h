@@ -394,6 +394,57 @@ static_assert(sizeof(TriItem) == 64 && sizeof(TriTrain) == 48, "k_triangulation'
 hipError_t launch_triangulation(const TriItem* d_items, const TriTrain* d_trains, int nitems, int* d_best,
                                 hipStream_t stream);
 
+// SearchForTriangulation between resident frames (k_triangulation_frames): nothing per feature is staged.  KF1 is a
+// kernel argument, each KF2 a row of a table; every pointer but the flags is into a frame's own allocations (its
+// arrays and its BoW part), the flags (has_mp, one byte per feature) are the call's only upload.
+struct TriFrameKf1 {
+    const uint8_t* desc;
+    const orb_keypoint* kps;
+    const float* ur;
+    const uint32_t* node_of;   // per feature: its FeatureVector node, 0xFFFFFFFF outside
+    const uint8_t* has_mp;
+    int n;
+};
+struct TriFramePair {
+    const uint8_t* desc;
+    const orb_keypoint* kps;
+    const float* ur;
+    const uint32_t* fv_nodes;  // KF2's FeatureVector CSR
+    const int* fv_off;
+    const int* fv_idx;
+    const uint8_t* has_mp;
+    int nnodes;
+    float ex, ey;
+    float F[9];
+    float scale2[ORBGPU_MAX_LEVELS];   // the octaves of KF2's keypoints index these: checked on the host
+    float sigma2[ORBGPU_MAX_LEVELS];
+};
+// One wavefront per (pair, KF1 feature): best_out[pair * n1 + idx1] = idx2 or -1.
+hipError_t launch_triangulation_frames(const TriFrameKf1& a, const TriFramePair* d_tab, int npairs, int only_stereo,
+                                       int* best_out, hipStream_t stream);
+
+// SearchByBoW between resident frames: k_bow_items is the device form of the for_common_nodes loops of bow_kf_f_run /
+// bow_kf_kf_run (matcher.hip).  Row p is one keyframe of the batch: the query side's FeatureVector CSR, descriptors
+// and map-point flags, the train side's node list and offsets, and the keyframe's segment [seg0, seg0 + seg_cap) of
+// the item arrays (seg_cap = the query CSR's length, the most items it can emit).
+struct BowItemsRow {
+    const uint32_t* q_nodes;
+    const int* q_off;
+    const int* q_idx;
+    const uint8_t* q_desc;
+    const uint8_t* q_flag;     // per query feature: nonzero = has a (good) map point
+    const uint32_t* t_nodes;
+    const int* t_off;
+    int q_nnodes, q_nnz, t_nnodes;
+    int seg0;
+    int rng_base;              // added to the train CSR's offsets (the train's place in the candidate list: 0)
+    int pad;
+};
+// item_q (host-coherent) and item_rng / qbuf (device) at [seg0, seg0 + seg_cap); seg_len[p] items are live, the rest
+// of the segment gets an empty range.
+hipError_t launch_bow_items(const BowItemsRow* d_tab, int nkf, int* item_q, int2* d_item_rng, uint8_t* d_qbuf,
+                            int* seg_len, hipStream_t stream);
+
 // Frame::ComputeStereoMatches (stereo.hip).  One side of a rectified pair: its pyramid (level 0 in
 // `frames`, levels >= 1 in `pyr`) and extraction outputs, for pair p at frame frame0 + p*frame_step.
 struct StereoSide {

@@ -34,6 +34,9 @@ namespace orbgpu {
 
 constexpr int kVocabMaxDepth = 64;   // descent bound: every lane exits even on a malformed tree
 
+// TAB: the frames are resident handles (orb_frame_compute_bow): row f of tab gives frame f's descriptors, count and
+// output arrays, each an allocation of its own; else one descriptor array of slot_stride slots per frame.
+template <bool TAB>
 __global__ __launch_bounds__(256) void k_vocab_transform(const int* __restrict__ cbeg, const int* __restrict__ ccnt,
                                                          const int* __restrict__ child,
                                                          const uint8_t* __restrict__ cdesc,
@@ -41,12 +44,24 @@ __global__ __launch_bounds__(256) void k_vocab_transform(const int* __restrict__
                                                          const uint8_t* __restrict__ desc, const int* __restrict__ counts,
                                                          int n_fixed, long long slot_stride, int nid_level,
                                                          int* __restrict__ word_out, float* __restrict__ weight_out,
-                                                         uint32_t* __restrict__ node_out) {
+                                                         uint32_t* __restrict__ node_out,
+                                                         const VocabFrameRow* __restrict__ tab) {
     const int f = blockIdx.y;
-    const int n = counts ? counts[f] : n_fixed;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const long long slot = (long long)f * slot_stride + i;
+    long long slot;
+    if (TAB) {
+        const VocabFrameRow R = tab[f];
+        if (i >= R.n) return;
+        desc = R.desc;
+        word_out = R.word;
+        weight_out = R.weight;
+        node_out = R.node;
+        slot = i;
+    } else {
+        const int n = counts ? counts[f] : n_fixed;
+        if (i >= n) return;
+        slot = (long long)f * slot_stride + i;
+    }
     const uint4* fp = reinterpret_cast<const uint4*>(desc + slot * 32);
     const uint4 a = fp[0], b = fp[1];
     int node = 0;
@@ -72,6 +87,60 @@ __global__ __launch_bounds__(256) void k_vocab_transform(const int* __restrict__
     word_out[slot] = word[node];
     weight_out[slot] = weight[node];
     node_out[slot] = nid;
+}
+
+hipError_t launch_vocab_transform_frames(const orb_vocab* v, int levelsup, const VocabFrameRow* d_tab, int nframes,
+                                         int max_n, hipStream_t stream) {
+    if (nframes <= 0 || max_n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_vocab_transform<true>, dim3((max_n + 255) / 256, nframes), dim3(256), 0, stream,
+                       v->d_cbeg.get(), v->d_ccnt.get(), v->d_child.get(), v->d_cdesc.get(), v->d_word.get(),
+                       v->d_weight.get(), nullptr, nullptr, 0, 0, v->L - levelsup, nullptr, nullptr, nullptr, d_tab);
+    return hipGetLastError();
+}
+
+int vocab_device(const orb_vocab* v) { return v->device; }
+bool vocab_empty(const orb_vocab* v) { return v->nwords <= 0; }
+
+int vocab_bow_vector(const orb_vocab* v, int n, const int* word_id, const float* weight, int* bow_words,
+                     double* bow_values) {
+    // std::map order = ascending word id, and within a word the features in input order: sorting (id, feature) keys
+    // gives the same order and the same summation order as the map inserts.
+    const bool tf = v->weighting == 0 || v->weighting == 1;   // TF_IDF, TF: addWeight; IDF, BINARY: addIfNotExist
+    const bool must = v->scoring != 5;                        // DotProductScoring does not normalise
+    const bool l1 = v->scoring != 1;                          // L2Scoring normalises with L2
+    int b = 0;
+    if (v->nwords <= 0) return 0;   // if(empty()) return; (:1146-1149)
+    std::vector<unsigned long long> kw;
+    kw.reserve(n);
+    for (int i = 0; i < n; i++)
+        if ((double)weight[i] > 0)   // not stopped
+            kw.push_back(((unsigned long long)(uint32_t)word_id[i] << 32) | (uint32_t)i);
+    std::sort(kw.begin(), kw.end());
+    for (size_t a = 0; a < kw.size();) {
+        const uint32_t w = (uint32_t)(kw[a] >> 32);
+        double acc = (double)weight[(uint32_t)kw[a]];
+        size_t e = a + 1;
+        for (; e < kw.size() && (uint32_t)(kw[e] >> 32) == w; e++)
+            if (tf) acc += (double)weight[(uint32_t)kw[e]];   // bow[word] += w, in feature order
+        bow_words[b] = (int)w;
+        bow_values[b] = acc;
+        b++;
+        a = e;
+    }
+    if (tf && b > 0 && !must)
+        for (int i = 0; i < b; i++) bow_values[i] /= (double)b;
+    if (must) {   // BowVector::normalize (BowVector.cpp:61-86), in map order
+        double norm = 0.0;
+        if (l1) {
+            for (int i = 0; i < b; i++) norm += std::fabs(bow_values[i]);
+        } else {
+            for (int i = 0; i < b; i++) norm += bow_values[i] * bow_values[i];
+            norm = std::sqrt(norm);
+        }
+        if (norm > 0.0)
+            for (int i = 0; i < b; i++) bow_values[i] /= norm;
+    }
+    return b;
 }
 
 }  // namespace orbgpu
@@ -204,10 +273,10 @@ int orb_vocab_transform(orb_ctx* h, const orb_vocab* v, const uint8_t* desc, int
     std::memcpy(st.hi<uint8_t>(o_desc), desc, (size_t)n * 32);
     hipError_t e = st.up(o_desc, o_w);
     if (e != hipSuccess) return set_error("vocab upload", e), ORB_ERR_HIP;
-    hipLaunchKernelGGL(k_vocab_transform, dim3((n + 255) / 256, 1), dim3(256), 0, c->stream, v->d_cbeg.get(),
+    hipLaunchKernelGGL(k_vocab_transform<false>, dim3((n + 255) / 256, 1), dim3(256), 0, c->stream, v->d_cbeg.get(),
                        v->d_ccnt.get(), v->d_child.get(), v->d_cdesc.get(), v->d_word.get(), v->d_weight.get(),
                        st.di<uint8_t>(o_desc), nullptr, n, 0, v->L - levelsup, st.h<int>(o_w), st.h<float>(o_wt),
-                       st.h<uint32_t>(o_nd));
+                       st.h<uint32_t>(o_nd), nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return set_error("vocab kernel", e), ORB_ERR_HIP;
     // the kernel writes [word | weight | node] straight into the pinned mirror: no D2H command
     (void)o_end;
@@ -228,10 +297,10 @@ int orb_vocab_transform_batch_device(orb_ctx* h, const orb_vocab* v, int nframes
         return set_error("orb_vocab_transform_batch_device: no such frames in the last batch", hipSuccess),
                ORB_ERR_ARG;
     const int cap = c->last_kp_cap;
-    hipLaunchKernelGGL(k_vocab_transform, dim3((cap + 255) / 256, nframes), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_vocab_transform<false>, dim3((cap + 255) / 256, nframes), dim3(256), 0, c->stream,
                        v->d_cbeg.get(), v->d_ccnt.get(), v->d_child.get(), v->d_cdesc.get(), v->d_word.get(),
                        v->d_weight.get(), c->last_desc, c->last_counts, 0, (long long)cap, v->L - levelsup, d_word,
-                       d_weight, d_node);
+                       d_weight, d_node, nullptr);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("vocab kernel", e), ORB_ERR_HIP);
 }
@@ -245,46 +314,16 @@ int orb_vocab_bow(const orb_vocab* v, int n, const int* word_id, const float* we
     // TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (:1139-1210).
     // std::map order = ascending word / node id, and within a word / node the features in input order:
     // sorting (id, feature) keys gives the same order and the same summation order as the map inserts.
-    const bool tf = v->weighting == 0 || v->weighting == 1;   // TF_IDF, TF: addWeight; IDF, BINARY: addIfNotExist
-    const bool must = v->scoring != 5;                        // DotProductScoring does not normalise
-    const bool l1 = v->scoring != 1;                          // L2Scoring normalises with L2
-    int b = 0, j = 0, o = 0;
+    const int b = vocab_bow_vector(v, n, word_id, weight, bow_words, bow_values);
+    int j = 0, o = 0;
     fv_off[0] = 0;
     if (v->nwords > 0) {   // if(empty()) return; (:1146-1149)
-        std::vector<unsigned long long> kw, kn;
-        kw.reserve(n);
+        std::vector<unsigned long long> kn;
         kn.reserve(n);
         for (int i = 0; i < n; i++)
-            if ((double)weight[i] > 0) {   // not stopped
-                kw.push_back(((unsigned long long)(uint32_t)word_id[i] << 32) | (uint32_t)i);
+            if ((double)weight[i] > 0)   // not stopped
                 kn.push_back(((unsigned long long)node_id[i] << 32) | (uint32_t)i);
-            }
-        std::sort(kw.begin(), kw.end());
         std::sort(kn.begin(), kn.end());
-        for (size_t a = 0; a < kw.size();) {
-            const uint32_t w = (uint32_t)(kw[a] >> 32);
-            double acc = (double)weight[(uint32_t)kw[a]];
-            size_t e = a + 1;
-            for (; e < kw.size() && (uint32_t)(kw[e] >> 32) == w; e++)
-                if (tf) acc += (double)weight[(uint32_t)kw[e]];   // bow[word] += w, in feature order
-            bow_words[b] = (int)w;
-            bow_values[b] = acc;
-            b++;
-            a = e;
-        }
-        if (tf && b > 0 && !must)
-            for (int i = 0; i < b; i++) bow_values[i] /= (double)b;
-        if (must) {   // BowVector::normalize (BowVector.cpp:61-86), in map order
-            double norm = 0.0;
-            if (l1) {
-                for (int i = 0; i < b; i++) norm += std::fabs(bow_values[i]);
-            } else {
-                for (int i = 0; i < b; i++) norm += bow_values[i] * bow_values[i];
-                norm = std::sqrt(norm);
-            }
-            if (norm > 0.0)
-                for (int i = 0; i < b; i++) bow_values[i] /= norm;
-        }
         for (size_t a = 0; a < kn.size(); a++) {   // FeatureVector::addFeature (FeatureVector.cpp:31-45)
             const uint32_t nd = (uint32_t)(kn[a] >> 32);
             if (a == 0 || (uint32_t)(kn[a - 1] >> 32) != nd) {

@@ -37,6 +37,9 @@ public:
     unsigned int size() const { return (unsigned int)nwords_; }
     int getBranchingFactor() const { return k_; }
     int getDepthLevels() const { return L_; }
+    // the C-ABI objects behind it, for ResidentFrame::ComputeBoW / BoW (ORBmatcher.h)
+    orb_ctx* context() const { return ctx_; }
+    const orb_vocab* handle() const { return voc_; }
 
 private:
     orb_ctx* ctx_ = nullptr;

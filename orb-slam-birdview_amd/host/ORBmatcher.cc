@@ -311,7 +311,8 @@ void ComputeImageBounds(float fx, float fy, float cx, float cy, const float dist
 
 ResidentFrame::~ResidentFrame() { orb_frame_destroy(h_); }
 
-ResidentFrame::ResidentFrame(ResidentFrame&& o) noexcept : h_(o.h_), n_(o.n_), hasURight_(o.hasURight_) {
+ResidentFrame::ResidentFrame(ResidentFrame&& o) noexcept
+    : h_(o.h_), n_(o.n_), hasURight_(o.hasURight_), fvCap_(o.fvCap_) {
     o.h_ = nullptr;
     o.n_ = 0;
     o.hasURight_ = false;
@@ -323,6 +324,7 @@ ResidentFrame& ResidentFrame::operator=(ResidentFrame&& o) noexcept {
         h_ = o.h_;
         n_ = o.n_;
         hasURight_ = o.hasURight_;
+        fvCap_ = o.fvCap_;
         o.h_ = nullptr;
         o.n_ = 0;
         o.hasURight_ = false;
@@ -360,6 +362,48 @@ void ResidentFrame::Grid(std::vector<int>& off, std::vector<int>& idx) const {
     int nslots = 0;
     check(orb_frame_grid_read(h_, off.data(), idx.data(), n_, &nslots), "ResidentFrame::Grid");
     idx.resize(nslots);
+}
+
+void ResidentFrame::ComputeBoW(orb_ctx* ctx, const orb_vocab* vocab, int levelsup) {
+    require(h_ != nullptr, "ResidentFrame::ComputeBoW: empty handle");
+    orb_frame* one = h_;
+    check(orb_frame_compute_bow(ctx, vocab, levelsup, 1, &one), "ResidentFrame::ComputeBoW");
+    fvCap_ = 0;
+}
+
+void ResidentFrame::ComputeBoW(orb_ctx* ctx, const orb_vocab* vocab, const std::vector<ResidentFrame*>& frames,
+                               int levelsup) {
+    std::vector<orb_frame*> h(frames.size());
+    for (size_t f = 0; f < frames.size(); f++) {
+        require(frames[f] && frames[f]->h_, "ResidentFrame::ComputeBoW: empty handle");
+        h[f] = frames[f]->h_;
+    }
+    check(orb_frame_compute_bow(ctx, vocab, levelsup, (int)h.size(), h.data()), "ResidentFrame::ComputeBoW(batch)");
+    for (ResidentFrame* f : frames) f->fvCap_ = 0;
+}
+
+void ResidentFrame::SetFeatVec(const FeatureVector& featVec) {
+    require(h_ != nullptr, "ResidentFrame::SetFeatVec: empty handle");
+    Csr a(&featVec);
+    check(orb_frame_set_featvec(matcher_ctx(), h_, a.fv), "ResidentFrame::SetFeatVec");
+    fvCap_ = std::max(a.ids.size(), a.idx.size());
+}
+
+void ResidentFrame::BoW(const orb_vocab* vocab, std::map<unsigned int, double>& bowVec, FeatureVector& featVec) const {
+    require(h_ != nullptr, "ResidentFrame::BoW: empty handle");
+    // (a FeatureVector given by SetFeatVec may hold more entries than features)
+    const size_t nw = (size_t)std::max(n_, 1), cap = std::max(nw, fvCap_);
+    std::vector<int> words(nw), off(cap + 1), idx(cap);
+    std::vector<double> values(nw);
+    std::vector<uint32_t> nodes(cap);
+    int nb = 0, nf = 0;
+    check(orb_frame_bow_read(vocab, h_, words.data(), values.data(), &nb, nodes.data(), off.data(), idx.data(), &nf),
+          "ResidentFrame::BoW");
+    bowVec.clear();
+    featVec.clear();
+    for (int i = 0; i < nb; i++) bowVec[(unsigned int)words[i]] = values[i];
+    for (int j = 0; j < nf; j++)
+        featVec[nodes[j]] = std::vector<unsigned int>(idx.begin() + off[j], idx.begin() + off[j + 1]);
 }
 
 namespace {
@@ -934,6 +978,64 @@ int ORBmatcher::SearchByProjection(FrameData& CurrentFrame, const ProjectedKeyFr
     // the rotation cull of :1577-1596 is statement for statement that of :1448-1467, which BEST mode replays
     return projection_search(ORB_PROJ_BEST, CurrentFrame, false, q, qdesc, vpMapPointMatches, "SearchByProjection(F, KF)",
                              ORBdist);
+}
+
+/* ---------------- the vocabulary-gated searches between ResidentFrames that carry BoW ---------------- */
+int ORBmatcher::SearchByBoW(const ResidentFrame& KF, const uint8_t* hasMapPointKF, const ResidentFrame& F,
+                            std::vector<int>& vpMapPointMatches) {
+    require(KF && F, "SearchByBoW: empty ResidentFrame");
+    const int nF = F.N();
+    vpMapPointMatches.assign(nF, -1);
+    std::vector<int> out(std::max(nF, 1), -1);
+    int nmatches = 0;
+    const orb_bow_frame_kf K{KF.handle(), hasMapPointKF, out.data(), &nmatches};
+    check(orb_search_by_bow_frames_kf_f(matcher_ctx(), mfNNratio, mbCheckOrientation, F.handle(), 1, &K),
+          "SearchByBoW(KF,F) resident");
+    std::copy(out.begin(), out.begin() + nF, vpMapPointMatches.begin());
+    return nmatches;
+}
+
+int ORBmatcher::SearchByBoW(const ResidentFrame& KF1, const uint8_t* hasMapPoint1, const ResidentFrame& KF2,
+                            const uint8_t* hasMapPoint2, std::vector<int>& vpMatches12) {
+    require(KF1 && KF2, "SearchByBoW: empty ResidentFrame");
+    const int n1 = KF1.N();
+    vpMatches12.assign(n1, -1);
+    std::vector<int> out(std::max(n1, 1), -1);
+    int nmatches = 0;
+    check(orb_search_by_bow_frames_kf_kf(matcher_ctx(), mfNNratio, mbCheckOrientation, KF1.handle(), hasMapPoint1,
+                                         KF2.handle(), hasMapPoint2, out.data(), &nmatches),
+          "SearchByBoW(KF,KF) resident");
+    std::copy(out.begin(), out.begin() + n1, vpMatches12.begin());
+    return nmatches;
+}
+
+int ORBmatcher::SearchForTriangulation(const ResidentFrame& KF1, const uint8_t* hasMapPoint1,
+                                       const std::vector<ResidentTriangulationNeighbour>& neighbours,
+                                       std::vector<std::vector<std::pair<size_t, size_t> > >& vvMatchedPairs,
+                                       const bool bOnlyStereo) {
+    require((bool)KF1, "SearchForTriangulation: empty ResidentFrame");
+    const int n1 = KF1.N(), np = (int)neighbours.size();
+    std::vector<std::vector<int> > pairs(np);
+    std::vector<int> count(np, 0);
+    std::vector<orb_tri_frame_pair> P(np);
+    for (int p = 0; p < np; p++) {
+        const ResidentTriangulationNeighbour& nb = neighbours[p];
+        require(nb.KF2 && *nb.KF2, "SearchForTriangulation: neighbour ResidentFrame");
+        pairs[p].resize(2 * (size_t)std::max(n1, 1));
+        P[p] = orb_tri_frame_pair{nb.KF2->handle(), nb.hasMapPoint, nb.F12, nb.ex, nb.ey, nb.scaleFactors,
+                                  nb.levelSigma2, nb.nlevels, pairs[p].data(), std::max(n1, 1), &count[p]};
+    }
+    check(orb_search_for_triangulation_frames(matcher_ctx(), mbCheckOrientation, bOnlyStereo, KF1.handle(), hasMapPoint1,
+                                              np, P.data()),
+          "SearchForTriangulation resident");
+    vvMatchedPairs.assign(np, std::vector<std::pair<size_t, size_t> >());
+    int total = 0;
+    for (int p = 0; p < np; p++) {
+        for (int i = 0; i < count[p]; i++)
+            vvMatchedPairs[p].push_back(std::make_pair((size_t)pairs[p][2 * i], (size_t)pairs[p][2 * i + 1]));
+        total += count[p];
+    }
+    return total;
 }
 
 /* ---------------- the ResidentFrame overloads: the FeatureSet forms with `resident` set ---------------- */

@@ -133,10 +133,23 @@ public:
     // the grid the GPU built, as FrameGrid::Csr gives the host one (cell_off: 64 * 48 + 1 entries)
     void Grid(std::vector<int>& off, std::vector<int>& idx) const;
 
+    // BoW on the handle (orb_frame_compute_bow): Frame::ComputeBoW / KeyFrame::ComputeBoW over the resident
+    // descriptors, the FeatureVector built on the GPU.  ctx / vocab: ORBVocabulary::context() / handle().  The static
+    // form serves several frames with one pair of launches.  SetFeatVec attaches an mFeatVec the caller holds; BoW
+    // reads both vectors back (an empty BowVector after SetFeatVec).  The handle then serves the ResidentFrame
+    // overloads of ORBmatcher::SearchByBoW / SearchForTriangulation.
+    void ComputeBoW(orb_ctx* ctx, const orb_vocab* vocab, int levelsup = 4);
+    static void ComputeBoW(orb_ctx* ctx, const orb_vocab* vocab, const std::vector<ResidentFrame*>& frames,
+                           int levelsup = 4);
+    void SetFeatVec(const FeatureVector& featVec);
+    void BoW(const orb_vocab* vocab, std::map<unsigned int, double>& bowVec, FeatureVector& featVec) const;
+    bool hasBoW() const { return orb_frame_has_bow(h_) != 0; }
+
 private:
     orb_frame* h_ = nullptr;
     int n_ = 0;
     bool hasURight_ = false;
+    size_t fvCap_ = 0;   // the entries of a FeatureVector given by SetFeatVec (BoW sizes its arrays by it)
 };
 
 // Map points kept on the device (the C-ABI's orb_points): per slot GetWorldPos, GetNormal, the raw mfMinDistance /
@@ -305,6 +318,28 @@ public:
     };
     int SearchForTriangulation(const KeyFrameData& KF1, const std::vector<TriangulationNeighbour>& neighbours,
                                std::vector<std::vector<std::pair<size_t, size_t> > >& vvMatchedPairs, const bool bOnlyStereo);
+
+    // The three vocabulary-gated searches between ResidentFrames that carry BoW (ComputeBoW / SetFeatVec; the
+    // triangulation also needs uRight on both): results equal the KeyFrameData forms' on the same members, and only
+    // the map-point flags (one byte per feature, n entries each) go up per call.  The KeyFrameData forms above do not
+    // route here.
+    int SearchByBoW(const ResidentFrame& KF, const uint8_t* hasMapPointKF, const ResidentFrame& F,
+                    std::vector<int>& vpMapPointMatches);
+    int SearchByBoW(const ResidentFrame& KF1, const uint8_t* hasMapPoint1, const ResidentFrame& KF2,
+                    const uint8_t* hasMapPoint2, std::vector<int>& vpMatches12);
+    struct ResidentTriangulationNeighbour {
+        const ResidentFrame* KF2;
+        const uint8_t* hasMapPoint;     // GetMapPoint(i) != NULL, KF2->N() entries
+        const float* scaleFactors;      // pKF2->mvScaleFactors
+        const float* levelSigma2;       // pKF2->mvLevelSigma2
+        int nlevels;
+        float F12[9];
+        float ex, ey;
+    };
+    int SearchForTriangulation(const ResidentFrame& KF1, const uint8_t* hasMapPoint1,
+                               const std::vector<ResidentTriangulationNeighbour>& neighbours,
+                               std::vector<std::vector<std::pair<size_t, size_t> > >& vvMatchedPairs,
+                               const bool bOnlyStereo);
 
     // ORBmatcher.cc:1667-1789 (window around vPrevMatched, level-0 only, updates vPrevMatched) and
     // :1790-1899 (window around each keypoint).  F1: keys (mvKeysBird), descriptors;

@@ -843,6 +843,36 @@ class Frame:
         check(lib().orb_frame_grid_read(self.h, _p(off), _p(idx), self.n, ctypes.byref(ns)), "orb_frame_grid_read")
         return off, idx[:ns.value]
 
+    def compute_bow(self, vocab, levelsup=4, ctx_or_matcher=None):
+        """Frame::ComputeBoW on the device (orb_frame_compute_bow): the handle then carries its FeatureVector (and
+        the per-feature triples) for the vocabulary-gated searches; bow() reads both vectors back."""
+        compute_bow(vocab, [self], levelsup, ctx_or_matcher)
+
+    def set_featvec(self, featvec, ctx_or_matcher):
+        """Attach a FeatureVector the caller holds ({node: [feature indices]}, a KeyFrame's mFeatVec)."""
+        fv, keep = _featvec(featvec)
+        check(lib().orb_frame_set_featvec(_ctx_handle(ctx_or_matcher), self.h, fv), "orb_frame_set_featvec")
+        self._fv_sizes = (len(keep[0]), int(keep[1][-1]))
+
+    @property
+    def has_bow(self):
+        return lib().orb_frame_has_bow(self.h) != 0
+
+    def bow(self, vocab=None):
+        """(BowVector {word: value}, FeatureVector {node: [i]}) as ORBVocabulary.transform returns them; the BowVector
+        is empty for a handle whose FeatureVector came from set_featvec."""
+        n = max(self.n, 1)
+        bw, bv = np.zeros(n, np.int32), np.zeros(n, np.float64)
+        size = max(n, *(getattr(self, "_fv_sizes", None) or (0, 0)))   # a given CSR may hold more than n entries
+        fn, fo, fi = np.zeros(size, np.uint32), np.zeros(size + 1, np.int32), np.zeros(size, np.int32)
+        nb, nf = ctypes.c_int(), ctypes.c_int()
+        v = None if vocab is None else vocab.v
+        check(lib().orb_frame_bow_read(v, self.h, _p(bw), _p(bv), ctypes.byref(nb), _p(fn), _p(fo), _p(fi),
+                                       ctypes.byref(nf)), "orb_frame_bow_read")
+        bowv = {int(bw[i]): float(bv[i]) for i in range(nb.value)}
+        fv = {int(fn[j]): fi[fo[j]:fo[j + 1]].tolist() for j in range(nf.value)}
+        return bowv, fv
+
     def close(self):
         if getattr(self, "h", None):
             lib().orb_frame_destroy(self.h)
@@ -850,6 +880,17 @@ class Frame:
 
     def __del__(self):
         self.close()
+
+
+def compute_bow(vocab, frames, levelsup=4, ctx_or_matcher=None):
+    """orb_frame_compute_bow for a list of Frames in one call: one vocabulary-transform launch over all their resident
+    descriptors and one FeatureVector launch.  vocab: an ORBVocabulary of the frames' GPU (its context runs the call
+    unless ctx_or_matcher is given)."""
+    hs = (ctypes.c_void_p * max(len(frames), 1))(*[f.h for f in frames])
+    h = vocab._ctx.h if ctx_or_matcher is None else _ctx_handle(ctx_or_matcher)
+    check(lib().orb_frame_compute_bow(h, vocab.v, int(levelsup), len(frames), hs), "orb_frame_compute_bow")
+    for f in frames:
+        f._fv_sizes = None
 
 
 def distortion(fx, fy, cx, cy, k):
@@ -1205,6 +1246,66 @@ class ORBmatcher:
                                                        len(others), ctypes.cast(arr, ctypes.c_void_p)),
               "SearchForTriangulationBatch")
         return [out[:n.value] for out, n in zip(outs, counts)]
+
+    def SearchForTriangulationFrames(self, frame1, has_mp1, others, bOnlyStereo=False, cap=None):
+        """orb_search_for_triangulation_frames: SearchForTriangulationBatch between Frame handles that carry BoW
+        (compute_bow / set_featvec) and uright.  others: a list of dicts with frame2, has_mp2, F12, ex, ey,
+        scale_factors2, level_sigma2_2.  Returns one (n, 2) array per KF2.  cap: the pair capacity per KF2 (default
+        len(frame1) + 1; a smaller one raises ORB_ERR_CAPACITY as the C call does)."""
+        from ._lib import OrbTriFramePair
+        m1 = np.ascontiguousarray(has_mp1, np.uint8)
+        assert len(m1) == len(frame1)
+        cap = len(frame1) + 1 if cap is None else int(cap)
+        keep, arr, outs, counts = [m1], (OrbTriFramePair * max(len(others), 1))(), [], []
+        for p, o in enumerate(others):
+            b = [np.ascontiguousarray(x) for x in (np.asarray(o["has_mp2"], np.uint8),
+                                                    np.asarray(o["F12"], np.float32).reshape(9),
+                                                    np.asarray(o["scale_factors2"], np.float32),
+                                                    np.asarray(o["level_sigma2_2"], np.float32))]
+            assert len(b[0]) == len(o["frame2"])
+            out = np.zeros((max(cap, 1), 2), np.int32)
+            n = ctypes.c_int()
+            keep += [b, out, n]
+            outs.append(out)
+            counts.append(n)
+            arr[p] = OrbTriFramePair(o["frame2"].h, _p(b[0]), _p(b[1]), float(o["ex"]), float(o["ey"]), _p(b[2]), _p(b[3]),
+                                     len(b[2]), _p(out), cap, ctypes.pointer(n))
+        self.last_tri_counts = counts
+        check(lib().orb_search_for_triangulation_frames(self._ctx.h, int(self.mbCheckOrientation), int(bOnlyStereo),
+                                                        frame1.h, _p(m1), len(others), ctypes.cast(arr, ctypes.c_void_p)),
+              "SearchForTriangulationFrames")
+        return [out[:n.value] for out, n in zip(outs, counts)]
+
+    def SearchByBoW_Frames_KF_F(self, kfs, frame_f):
+        """orb_search_by_bow_frames_kf_f: SearchByBoW(pKF, F) for every keyframe of kfs (dicts with frame, mp) against
+        the Frame handle frame_f; all handles carry BoW.  Returns a list of (nmatches, match_f)."""
+        from ._lib import OrbBowFrameKf
+        nf = len(frame_f)
+        arr, outs, counts, keep = (OrbBowFrameKf * max(len(kfs), 1))(), [], [], []
+        for p, k in enumerate(kfs):
+            mp = np.ascontiguousarray(k["mp"], np.uint8)
+            assert len(mp) == len(k["frame"])
+            out = np.full(max(nf, 1), -1, np.int32)
+            n = ctypes.c_int()
+            keep += [mp, out, n]
+            outs.append(out[:nf])
+            counts.append(n)
+            arr[p] = OrbBowFrameKf(k["frame"].h, _p(mp), _p(out), ctypes.pointer(n))
+        check(lib().orb_search_by_bow_frames_kf_f(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation), frame_f.h,
+                                                  len(kfs), ctypes.cast(arr, ctypes.c_void_p)), "SearchByBoW(KF,F) frames")
+        return [(n.value, o) for n, o in zip(counts, outs)]
+
+    def SearchByBoW_Frames_KF_KF(self, kf1, mp1, kf2, mp2):
+        """orb_search_by_bow_frames_kf_kf: SearchByBoW(pKF1, pKF2) between two Frame handles that carry BoW.  Returns
+        (nmatches, match12)."""
+        a = [np.ascontiguousarray(x, np.uint8) for x in (mp1, mp2)]
+        assert len(a[0]) == len(kf1) and len(a[1]) == len(kf2)
+        out = np.full(max(len(kf1), 1), -1, np.int32)
+        nm = ctypes.c_int()
+        check(lib().orb_search_by_bow_frames_kf_kf(self._ctx.h, self.mfNNratio, int(self.mbCheckOrientation), kf1.h,
+                                                   _p(a[0]), kf2.h, _p(a[1]), _p(out), ctypes.byref(nm)),
+              "SearchByBoW(KF,KF) frames")
+        return nm.value, out[:len(kf1)]
 
     def _window(self, level0_only, desc1, kps1, desc2, kps2, cand_off, cand_idx):
         a = [np.ascontiguousarray(x) for x in (desc1, np.asarray(kps1, KP_DTYPE), desc2, np.asarray(kps2, KP_DTYPE),

@@ -47,6 +47,15 @@ class OrbBowKf(ctypes.Structure):   # orb_bow_kf
                 ("nmatches", ctypes.POINTER(ci))]
 
 
+class OrbTriFramePair(ctypes.Structure):   # orb_tri_frame_pair
+    _fields_ = [("frame2", vp), ("has_mp2", vp), ("F12", vp), ("ex", cf), ("ey", cf), ("scale2", vp), ("sigma2_2", vp),
+                ("nlevels2", ci), ("pairs_out", vp), ("cap", ci), ("npairs", ctypes.POINTER(ci))]
+
+
+class OrbBowFrameKf(ctypes.Structure):   # orb_bow_frame_kf
+    _fields_ = [("frame", vp), ("mp", vp), ("match", vp), ("nmatches", ctypes.POINTER(ci))]
+
+
 class OrbFrameGrid(ctypes.Structure):
     _fields_ = [("min_x", cf), ("min_y", cf), ("inv_w", cf), ("inv_h", cf), ("cell_off", vp), ("cell_idx", vp)]
 
@@ -141,6 +150,13 @@ SIGNATURES = {
     "orb_frame_destroy": (None, [vp]),
     "orb_frame_count": (ci, [vp]),
     "orb_frame_grid_read": (ci, [vp, vp, vp, ci, ctypes.POINTER(ci)]),
+    "orb_frame_compute_bow": (ci, [vp, vp, ci, ci, vp]),
+    "orb_frame_set_featvec": (ci, [vp, vp, OrbFeatVec]),
+    "orb_frame_has_bow": (ci, [vp]),
+    "orb_frame_bow_read": (ci, [vp, vp, vp, vp, ctypes.POINTER(ci), vp, vp, vp, ctypes.POINTER(ci)]),
+    "orb_search_for_triangulation_frames": (ci, [vp, ci, ci, vp, vp, ci, vp]),
+    "orb_search_by_bow_frames_kf_f": (ci, [vp, cf, ci, vp, ci, vp]),
+    "orb_search_by_bow_frames_kf_kf": (ci, [vp, cf, ci, vp, vp, vp, vp, vp, ctypes.POINTER(ci)]),
     "orb_search_by_projection_frame": (ci, [vp, ci, cf, ci, ci, ci, vp, vp, vp, vp, ci, vp, ctypes.POINTER(ci)]),
     "orb_window_match_frame": (ci, [vp, cf, ci, ci, ci, vp, vp, vp, cf, vp, vp, ctypes.POINTER(ci)]),
     "orb_search_by_match_bird_resident": (ci, [vp, cf, ci, ci, cf, ci, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ci)]),
