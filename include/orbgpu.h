@@ -350,7 +350,9 @@ typedef struct orb_tri_pair {
     float ex, ey;                /* KF1's centre projected in KF2 */
     const float* scale2;         /* pKF2->mvScaleFactors */
     const float* sigma2_2;       /* pKF2->mvLevelSigma2 */
-    int nlevels2;
+    int nlevels2;                /* entries of scale2 / sigma2_2, in [1, ORBGPU_MAX_LEVELS]; every keypoint of kps2 has
+                                    its octave in [0, nlevels2).  Otherwise the call (the single form and the batch
+                                    alike) returns ORB_ERR_ARG and writes nothing for any pair */
     int* pairs_out;              /* 2 ints per pair */
     int cap;
     int* npairs;

@@ -9,8 +9,6 @@
 
 namespace orbgpu {
 
-static_assert(kCellGridCols == kFrameGridCols && kCellGridRows == kFrameGridRows, "frame_cell.h's grid");
-
 constexpr int kGridThreads = 1024;
 constexpr int kGridWaves = kGridThreads / 64;
 constexpr int kGridCellsPerThread = kFrameGridCells / kGridThreads;   // 3

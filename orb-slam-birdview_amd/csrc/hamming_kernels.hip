@@ -9,6 +9,7 @@
 // (matcher.hip).
 #include <algorithm>
 
+#include "grid_window.h"
 #include "orbgpu_internal.h"
 #include "tri_geometry.h"
 
@@ -21,16 +22,76 @@ __device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, cons
            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+// minimum / sum over a row of W lanes (64: the wavefront; 16: one DPP row, the shuffles stay below lane offset 16)
+template <int W>
+__device__ __forceinline__ unsigned long long row_min_u64(unsigned long long v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int o = W / 2; o > 0; o >>= 1) {
         const unsigned long long w = __shfl_xor(v, o);
         v = w < v ? w : v;
     }
     return v;
 }
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) { return row_min_u64<64>(v); }
+template <int W>
+__device__ __forceinline__ int row_sum(int v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 constexpr int kMaxK = 8;
+
+// The top-k list of k_topk, k_window_topk and k_projection_topk: each lane keeps the k smallest keys it saw, ascending
+// (key = dist << 32 | the candidate's rank in the reference's iteration order: ascending key = ascending distance,
+// then first wins on ties); emit() merges the lanes' lists of a row of W lanes.  In registers: every index into lst
+// is a constant after unrolling.
+struct TopkList {
+    unsigned long long lst[kMaxK];
+
+    __device__ __forceinline__ TopkList() {
+#pragma unroll
+        for (int j = 0; j < kMaxK; j++) lst[j] = ~0ull;
+    }
+
+    __device__ __forceinline__ void insert(unsigned long long key, int k) {
+#pragma unroll
+        for (int j = 0; j < kMaxK; j++) {   // sorted insert (compare-swap chain)
+            if (j < k && key < lst[j]) {
+                const unsigned long long tmp = lst[j];
+                lst[j] = key;
+                key = tmp;
+            }
+        }
+    }
+
+    // The row's k smallest keys in order: k times the minimum of the lanes' heads, the lane that holds it steps on
+    // (keys are unique within a row).  The writer lane (one per row, or none) stores entry j of out_dist / out_idx
+    // at row * k + j: the key's distance and idx_of(its low word), or -1, -1 once the row's lists are exhausted.
+    // Every lane of the row must call (shuffles).
+    template <int W, class IdxOf>
+    __device__ __forceinline__ void emit(int k, bool writer, long long row, IdxOf idx_of, int* __restrict__ out_dist,
+                                         int* __restrict__ out_idx) const {
+        int head = 0;
+        for (int j = 0; j < k; j++) {
+            unsigned long long mine = ~0ull;
+#pragma unroll
+            for (int s = 0; s < kMaxK; s++)
+                if (s == head) mine = lst[s];
+            const unsigned long long m = row_min_u64<W>(mine);
+            if (mine == m && m != ~0ull) head++;
+            if (writer) {
+                int dd = -1, ii = -1;
+                if (m != ~0ull) {
+                    dd = (int)(m >> 32);
+                    ii = idx_of((int)(m & 0xFFFFFFFFu));
+                }
+                out_dist[row * k + j] = dd;
+                out_idx[row * k + j] = ii;
+            }
+        }
+    }
+};
 
 }  // namespace
 
@@ -53,9 +114,7 @@ __global__ __launch_bounds__(256) void k_topk(const uint8_t* __restrict__ q, int
         c0 = r.x;
         c1 = r.y;
     }
-    unsigned long long lst[kMaxK];
-#pragma unroll
-    for (int j = 0; j < kMaxK; j++) lst[j] = ~0ull;
+    TopkList top;
     int nvalid = 0;
     for (int pos = c0 + lane; pos < c1; pos += 64) {
         const int ti = ranges ? cand_idx[pos] : pos;
@@ -63,43 +122,17 @@ __global__ __launch_bounds__(256) void k_topk(const uint8_t* __restrict__ q, int
         const int d = hamming256(qa, qb, tp[0], tp[1]);
         if (thr && thr[ti] <= d) continue;
         nvalid++;
-        unsigned long long key = ((unsigned long long)d << 32) | (unsigned)(pos - c0);
-#pragma unroll
-        for (int j = 0; j < kMaxK; j++) {   // sorted insert (compare-swap chain)
-            if (j < k && key < lst[j]) {
-                const unsigned long long tmp = lst[j];
-                lst[j] = key;
-                key = tmp;
-            }
-        }
+        top.insert(((unsigned long long)d << 32) | (unsigned)(pos - c0), k);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nvalid += __shfl_xor(nvalid, o);
-    int head = 0;
-    for (int j = 0; j < k; j++) {
-        unsigned long long mine = ~0ull;
-#pragma unroll
-        for (int s = 0; s < kMaxK; s++)
-            if (s == head) mine = lst[s];
-        const unsigned long long m = wave_min_u64(mine);
-        if (mine == m && m != ~0ull) head++;
-        if (lane == 0) {
-            int dd = -1, ii = -1;
-            if (m != ~0ull) {
-                dd = (int)(m >> 32);
-                const int pos = (int)(m & 0xFFFFFFFFu) + c0;
-                ii = ranges ? cand_idx[pos] : pos;
-            }
-            out_dist[(long long)qi * k + j] = dd;
-            out_idx[(long long)qi * k + j] = ii;
-        }
-    }
+    nvalid = row_sum<64>(nvalid);
+    top.emit<64>(k, lane == 0, qi, [&](int rank) { return ranges ? cand_idx[rank + c0] : rank + c0; }, out_dist, out_idx);
     if (lane == 0 && out_nvalid) out_nvalid[qi] = nvalid;
 }
 
 // The window searches' candidate lists built on the device (SearchForInitialization :416-437,
 // BirdviewMatch :1680-1700 / :1801-1812): Frame::GetFeaturesInArea(cx, cy, r, lv, lv) with lv = the
-// query's octave (:494-547) over F2's grid in its CSR form.  The reference visits cells ix-major, iy
+// query's octave (:494-547; the rectangle and the box are grid_window.h's) over F2's grid in its CSR form.  The
+// reference visits cells ix-major, iy
 // inner, a cell's keypoints in vector order: that is increasing CSR slot, so a candidate's slot is its
 // rank in vIndices2 and (dist, slot) breaks ties as the reference's first minimum does.  One wave per
 // item; the rectangle's column ranges are contiguous slot runs.
@@ -112,7 +145,6 @@ __global__ __launch_bounds__(256) void k_window_topk(const uint8_t* __restrict__
                                                      const int* __restrict__ cell_idx, WinGrid wg,
                                                      const int* __restrict__ thr, int k, int* __restrict__ out_dist,
                                                      int* __restrict__ out_idx, int* __restrict__ out_nvalid) {
-    constexpr int COLS = 64, ROWS = 48;   // Frame.h:39-40
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (qi >= nitems) return;
@@ -130,67 +162,34 @@ __global__ __launch_bounds__(256) void k_window_topk(const uint8_t* __restrict__
         y = kps1[i1].y;
     }
     const float r = wg.r;
-    // cell rectangle, the reference's float expressions (-ffp-contract=off: no fused forms)
-    const int nMinCellX = max(0, (int)floorf((x - wg.min_x - r) * wg.inv_w));
-    const int nMaxCellX = min(COLS - 1, (int)ceilf((x - wg.min_x + r) * wg.inv_w));
-    const int nMinCellY = max(0, (int)floorf((y - wg.min_y - r) * wg.inv_h));
-    const int nMaxCellY = min(ROWS - 1, (int)ceilf((y - wg.min_y + r) * wg.inv_h));
-    const bool empty = nMinCellX >= COLS || nMaxCellX < 0 || nMinCellY >= ROWS || nMaxCellY < 0;
-    unsigned long long lst[kMaxK];
-#pragma unroll
-    for (int j = 0; j < kMaxK; j++) lst[j] = ~0ull;
+    const CellRect c = cell_rect(x, y, r, wg.min_x, wg.min_y, wg.inv_w, wg.inv_h);
+    TopkList top;
     int nvalid = 0;
-    if (!empty) {
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-            const int s0 = cell_off[ix * ROWS + nMinCellY], s1 = cell_off[ix * ROWS + nMaxCellY + 1];
+    if (!c.empty) {
+        for (int ix = c.x0; ix <= c.x1; ix++) {
+            const int s0 = cell_off[ix * kCellGridRows + c.y0], s1 = cell_off[ix * kCellGridRows + c.y1 + 1];
             for (int s = s0 + lane; s < s1; s += 64) {
                 const int ti = cell_idx[s];
                 const orb_keypoint kp = kps2[ti];
-                if (kp.octave != lv) continue;                                        // :518-525 with min = max = lv
-                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;          // :530-533
+                if (kp.octave != lv) continue;   // the query's own level (grid_window.h on why not window_admits)
+                if (!window_box(kp, x, y, r)) continue;
                 const uint4* tp = reinterpret_cast<const uint4*>(t + (long long)ti * 32);
                 const int d = hamming256(qa, qb, tp[0], tp[1]);
                 if (thr && thr[ti] <= d) continue;
                 nvalid++;
-                unsigned long long key = ((unsigned long long)d << 32) | (unsigned)s;
-#pragma unroll
-                for (int j = 0; j < kMaxK; j++) {   // sorted insert (compare-swap chain)
-                    if (j < k && key < lst[j]) {
-                        const unsigned long long tmp = lst[j];
-                        lst[j] = key;
-                        key = tmp;
-                    }
-                }
+                top.insert(((unsigned long long)d << 32) | (unsigned)s, k);
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nvalid += __shfl_xor(nvalid, o);
-    int head = 0;
-    for (int j = 0; j < k; j++) {
-        unsigned long long mine = ~0ull;
-#pragma unroll
-        for (int s = 0; s < kMaxK; s++)
-            if (s == head) mine = lst[s];
-        const unsigned long long m = wave_min_u64(mine);
-        if (mine == m && m != ~0ull) head++;
-        if (lane == 0) {
-            int dd = -1, ii = -1;
-            if (m != ~0ull) {
-                dd = (int)(m >> 32);
-                ii = cell_idx[(int)(m & 0xFFFFFFFFu)];
-            }
-            out_dist[(long long)qi * k + j] = dd;
-            out_idx[(long long)qi * k + j] = ii;
-        }
-    }
+    nvalid = row_sum<64>(nvalid);
+    top.emit<64>(k, lane == 0, qi, [&](int slot) { return cell_idx[slot]; }, out_dist, out_idx);
     if (lane == 0 && out_nvalid) out_nvalid[qi] = nvalid;
 }
 
 // The projection-gated searches' candidates (SearchByProjection(Frame&, const Frame&) :1383-1413,
 // SearchByProjection(Frame&, vector<MapPoint*>) :68-96, SearchByProjectionBird :1945-1965):
-// Frame::GetFeaturesInArea(u, v, r, min_level, max_level) (Frame.cc:494-547) over the train frame's grid in its
-// CSR form, each query with its own centre, radius and level range, then the stereo gate on mvuRight.  As in
+// Frame::GetFeaturesInArea(u, v, r, min_level, max_level) (Frame.cc:494-547: cell_rect and window_admits,
+// grid_window.h) over the train frame's grid in its CSR form, each query with its own centre, radius and level range, then the stereo gate on mvuRight.  As in
 // k_window_topk a candidate's CSR slot is its rank in vIndices, so (dist, slot) is the reference's first minimum.
 // A projection window holds a few to a few dozen candidates; a query gets W lanes: 64 (one wavefront, the form in
 // use) or 16 (one DPP row: four queries per wavefront, sixteen per block; the reductions stay below lane offset 16;
@@ -208,7 +207,6 @@ __global__ __launch_bounds__(256) void k_projection_topk(const orb_proj_query* _
                                                          const int* __restrict__ thr, int k,
                                                          int* __restrict__ out_dist, int* __restrict__ out_idx,
                                                          int* __restrict__ out_nvalid) {
-    constexpr int COLS = 64, ROWS = 48;   // Frame.h:39-40
     static_assert(W == 16 || W == 64, "one DPP row or one wavefront per query");
     const int qi = blockIdx.x * (256 / W) + (int)(threadIdx.x / W);
     const int lane = threadIdx.x & (W - 1);
@@ -218,28 +216,16 @@ __global__ __launch_bounds__(256) void k_projection_topk(const orb_proj_query* _
     const uint4* qp = reinterpret_cast<const uint4*>(q + (long long)qc * 32);
     const uint4 qa = qp[0], qb = qp[1];
     const float x = P.u, y = P.v, r = P.r;
-    // cell rectangle, the reference's float expressions (-ffp-contract=off: no fused forms)
-    const int nMinCellX = max(0, (int)floorf((x - g.min_x - r) * g.inv_w));
-    const int nMaxCellX = min(COLS - 1, (int)ceilf((x - g.min_x + r) * g.inv_w));
-    const int nMinCellY = max(0, (int)floorf((y - g.min_y - r) * g.inv_h));
-    const int nMaxCellY = min(ROWS - 1, (int)ceilf((y - g.min_y + r) * g.inv_h));
-    const bool empty = !live || nMinCellX >= COLS || nMaxCellX < 0 || nMinCellY >= ROWS || nMaxCellY < 0;
-    const bool bCheckLevels = P.min_level > 0 || P.max_level >= 0;   // Frame.cc:515
-    unsigned long long lst[kMaxK];
-#pragma unroll
-    for (int j = 0; j < kMaxK; j++) lst[j] = ~0ull;
+    const CellRect c = cell_rect(x, y, r, g.min_x, g.min_y, g.inv_w, g.inv_h);
+    TopkList top;
     int nvalid = 0;
-    if (!empty) {
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-            const int s0 = cell_off[ix * ROWS + nMinCellY], s1 = cell_off[ix * ROWS + nMaxCellY + 1];
+    if (live && !c.empty) {
+        for (int ix = c.x0; ix <= c.x1; ix++) {
+            const int s0 = cell_off[ix * kCellGridRows + c.y0], s1 = cell_off[ix * kCellGridRows + c.y1 + 1];
             for (int s = s0 + lane; s < s1; s += W) {
                 const int ti = cell_idx[s];
                 const orb_keypoint kp = kps2[ti];
-                if (bCheckLevels) {                                                   // :520-527
-                    if (kp.octave < P.min_level) continue;
-                    if (P.max_level >= 0 && kp.octave > P.max_level) continue;
-                }
-                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;          // :530-533
+                if (!window_admits(kp, x, y, r, P.min_level, P.max_level)) continue;
                 if (uright) {                                                         // ORBmatcher.cc:91-96, :1407-1413
                     const float urt = uright[ti];
                     if (urt > 0 && fabsf(P.ur - urt) > P.ur_tol) continue;
@@ -248,43 +234,12 @@ __global__ __launch_bounds__(256) void k_projection_topk(const orb_proj_query* _
                 const int d = hamming256(qa, qb, tp[0], tp[1]);
                 if (thr && thr[ti] <= d) continue;
                 nvalid++;
-                unsigned long long key = ((unsigned long long)d << 32) | (unsigned)s;
-#pragma unroll
-                for (int j = 0; j < kMaxK; j++) {   // sorted insert (compare-swap chain)
-                    if (j < k && key < lst[j]) {
-                        const unsigned long long tmp = lst[j];
-                        lst[j] = key;
-                        key = tmp;
-                    }
-                }
+                top.insert(((unsigned long long)d << 32) | (unsigned)s, k);
             }
         }
     }
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) nvalid += __shfl_xor(nvalid, o);
-    int head = 0;
-    for (int j = 0; j < k; j++) {
-        unsigned long long mine = ~0ull;
-#pragma unroll
-        for (int s = 0; s < kMaxK; s++)
-            if (s == head) mine = lst[s];
-        unsigned long long m = mine;
-#pragma unroll
-        for (int o = W / 2; o > 0; o >>= 1) {
-            const unsigned long long w = __shfl_xor(m, o);
-            m = w < m ? w : m;
-        }
-        if (mine == m && m != ~0ull) head++;
-        if (lane == 0 && live) {
-            int dd = -1, ii = -1;
-            if (m != ~0ull) {
-                dd = (int)(m >> 32);
-                ii = cell_idx[(int)(m & 0xFFFFFFFFu)];
-            }
-            out_dist[(long long)qi * k + j] = dd;
-            out_idx[(long long)qi * k + j] = ii;
-        }
-    }
+    nvalid = row_sum<W>(nvalid);
+    top.emit<W>(k, lane == 0 && live, qi, [&](int slot) { return cell_idx[slot]; }, out_dist, out_idx);
     if (lane == 0 && live) out_nvalid[qi] = nvalid;
 }
 
@@ -296,16 +251,15 @@ __global__ __launch_bounds__(256) void k_projection_topk(const orb_proj_query* _
 // Frame::GetFeaturesInArea without levels; the level filter of the callers is the query's (min_level, max_level));
 // a lane keeps one key dist << 32 | slot (a slot is the candidate's rank in vIndices), so the wave minimum is the
 // reference's first minimum.
-// GATE 1: the chi-square reprojection test of :914-938 in the reference build's contracted forms
-// (tools/fuse_flags_probe.cpp; this file builds -ffp-contract=off, so the fmaf below are the only fused operations);
-// the octave indexes inv_sigma2, which the host validated.  Waves past the last item stay in with an empty window.
+// GATE 1: the chi-square reprojection test of :914-938, fuse_gate_skips (grid_window.h: the reference build's
+// contracted forms; this file builds -ffp-contract=off, so its fmaf are the only fused operations); the octave
+// indexes inv_sigma2, which the host validated.  Waves past the last item stay in with an empty window.
 template <int GATE>
 __global__ __launch_bounds__(256) void k_projection_best(const ProjTarget* __restrict__ tab,
                                                          const int* __restrict__ item_tgt,
                                                          const orb_proj_query* __restrict__ pq,
                                                          const uint8_t* __restrict__ q, int nitems,
                                                          int* __restrict__ out_idx, int* __restrict__ out_dist) {
-    constexpr int COLS = 64, ROWS = 48;   // KeyFrame.h: FRAME_GRID_COLS / ROWS
     const int it = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const bool live = it < nitems;
@@ -322,37 +276,18 @@ __global__ __launch_bounds__(256) void k_projection_best(const ProjTarget* __res
     const int* cell_idx = T.cell_idx;
     const ProjGrid g = T.g;
     const float x = P.u, y = P.v, r = P.r;
-    const int nMinCellX = max(0, (int)floorf((x - g.min_x - r) * g.inv_w));
-    const int nMaxCellX = min(COLS - 1, (int)ceilf((x - g.min_x + r) * g.inv_w));
-    const int nMinCellY = max(0, (int)floorf((y - g.min_y - r) * g.inv_h));
-    const int nMaxCellY = min(ROWS - 1, (int)ceilf((y - g.min_y + r) * g.inv_h));
-    const bool empty = !live || nMinCellX >= COLS || nMaxCellX < 0 || nMinCellY >= ROWS || nMaxCellY < 0;
-    const bool bCheckLevels = P.min_level > 0 || P.max_level >= 0;
+    const CellRect c = cell_rect(x, y, r, g.min_x, g.min_y, g.inv_w, g.inv_h);
     unsigned long long best = ~0ull;
-    if (!empty) {
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-            const int s0 = cell_off[ix * ROWS + nMinCellY], s1 = cell_off[ix * ROWS + nMaxCellY + 1];
+    if (live && !c.empty) {
+        for (int ix = c.x0; ix <= c.x1; ix++) {
+            const int s0 = cell_off[ix * kCellGridRows + c.y0], s1 = cell_off[ix * kCellGridRows + c.y1 + 1];
             for (int s = s0 + lane; s < s1; s += 64) {
                 const int ti = cell_idx[s];
                 const orb_keypoint kp = kps[ti];
-                if (bCheckLevels) {
-                    if (kp.octave < P.min_level) continue;
-                    if (P.max_level >= 0 && kp.octave > P.max_level) continue;
-                }
-                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;   // KeyFrame.cc:615-619
-                if (GATE == ORB_PROJ_GATE_FUSE) {                               // ORBmatcher.cc:914-938
-                    const float urt = uright ? uright[ti] : -1.0f;
-                    const float ex = x - kp.x, ey = y - kp.y;
-                    const float e2m = fmaf(ex, ex, ey * ey);
-                    const float is2 = inv_sigma2[kp.octave];
-                    if (urt >= 0) {
-                        const float er = P.ur - urt;
-                        const float e2 = fmaf(er, er, e2m);
-                        if ((double)(e2 * is2) > 7.8) continue;
-                    } else {
-                        if ((double)(e2m * is2) > 5.99) continue;
-                    }
-                }
+                if (!window_admits(kp, x, y, r, P.min_level, P.max_level)) continue;
+                if (GATE == ORB_PROJ_GATE_FUSE &&
+                    fuse_gate_skips(x, y, P.ur, kp.x, kp.y, uright ? uright[ti] : -1.0f, inv_sigma2[kp.octave]))
+                    continue;
                 const uint4* tp = reinterpret_cast<const uint4*>(t + (long long)ti * 32);
                 const int d = hamming256(qa, qb, tp[0], tp[1]);
                 const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)s;
@@ -360,11 +295,7 @@ __global__ __launch_bounds__(256) void k_projection_best(const ProjTarget* __res
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(best, o);
-        best = w < best ? w : best;
-    }
+    best = wave_min_u64(best);
     if (lane == 0 && live) {
         int dd = -1, ii = -1;
         if (best != ~0ull) {
@@ -390,8 +321,7 @@ __global__ __launch_bounds__(256) void k_triangulation(const TriItem* __restrict
     if (it >= nitems) return;
     const TriItem q = items[it];
     const bool st1 = q.stereo != 0;
-    // CheckDistEpipolarLine (the reference's contracted float forms, tools/ref_flags_probe.cpp): the line a, b, c
-    // comes staged with the query
+    // CheckDistEpipolarLine (tri_epipolar_ok, tri_geometry.h): the line a, b, c comes staged with the query
     const float la = q.la, lb = q.lb, lc = q.lc;
     const float den = __builtin_fmaf(la, la, lb * lb);
     unsigned long long bestKey = ~0ull;
@@ -403,10 +333,10 @@ __global__ __launch_bounds__(256) void k_triangulation(const TriItem* __restrict
         if (dist > 50) continue;
         const int fl = tr.flags;
         if (!st1 && !(fl & 1) && (fl & 2)) continue;   // neither stereo and too close to the epipole (:743-748)
+        // (den is the item's, wave-uniform: tested here as well, ahead of the record's loads from the host mirror, the
+        // function's own test folds away; without this line the loop gains a scalar branch and measured slower)
         if (den == 0) continue;
-        const float num = __builtin_fmaf(lb, tr.y, la * tr.x) + lc;
-        const float dsqr = num * num / den;
-        if (!((double)dsqr < 3.84 * (double)tr.sigma2)) continue;
+        if (!tri_epipolar_ok(la, lb, lc, den, tr.x, tr.y, tr.sigma2)) continue;
         const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(0x7FFFFFFF - (pos - c0));
         bestKey = key < bestKey ? key : bestKey;
     }
@@ -467,10 +397,7 @@ __global__ __launch_bounds__(256) void k_triangulation_frames(TriFrameKf1 A, con
         const float x2 = k2.x, y2 = k2.y;
         const int oct = k2.octave;
         if (!st1 && !st2 && tri_near_epipole(P.ex, P.ey, x2, y2, P.scale2, oct)) continue;   // :743-748
-        if (den == 0) continue;
-        const float num = __builtin_fmaf(lb, y2, la * x2) + lc;
-        const float dsqr = num * num / den;
-        if (!((double)dsqr < 3.84 * (double)tri_sigma2(P.sigma2, oct))) continue;
+        if (!tri_epipolar_ok(la, lb, lc, den, x2, y2, tri_sigma2(P.sigma2, oct))) continue;
         const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(0x7FFFFFFF - (pos - c0));
         bestKey = key < bestKey ? key : bestKey;
     }

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "grid_window.h"
 #include "orbgpu_ctx.h"
 #include "point_project.h"
 #include "topk_scan.h"
@@ -1091,9 +1092,16 @@ int tri_run(Ctx* c, int check_ori, int only_stereo, const TriSide& a, int npairs
     return rc;
 }
 
+// A pair of the host-pointer forms.  tri_geometry_body indexes scale2 / sigma2_2 with the octave of the KF2 keypoints
+// the staging reads: every KF2 keypoint's octave lies in [0, nlevels2), as the _frames form asks of a frame (one
+// sequential pass without a branch: about half the time of a pass over fv2.indices).
 bool tri_pair_ok(const orb_tri_pair& P) {
-    return P.n2 >= 0 && P.npairs && P.nlevels2 >= 1 && P.nlevels2 <= ORBGPU_MAX_LEVELS && P.F12 && P.scale2 &&
-           P.sigma2_2 && featvec_ok(P.fv2, P.n2) && (P.n2 == 0 || (P.desc2 && P.kps2 && P.has_mp2 && P.uright2));
+    if (!(P.n2 >= 0 && P.npairs && P.nlevels2 >= 1 && P.nlevels2 <= ORBGPU_MAX_LEVELS && P.F12 && P.scale2 &&
+          P.sigma2_2 && featvec_ok(P.fv2, P.n2) && (P.n2 == 0 || (P.desc2 && P.kps2 && P.has_mp2 && P.uright2))))
+        return false;
+    int bad = 0;
+    for (int i = 0; i < P.n2; i++) bad += (unsigned)P.kps2[i].octave >= (unsigned)P.nlevels2;
+    return bad == 0;
 }
 }  // namespace
 }  // namespace orbgpu
@@ -1108,11 +1116,12 @@ int orb_search_for_triangulation(orb_ctx* h, int check_ori, int only_stereo, int
                                  int* pairs_out, int cap, int* npairs) {
     Ctx* c = reinterpret_cast<Ctx*>(h);
     CTX_GUARD(c);
-    if (n1 < 0 || n2 < 0 || !npairs || nlevels2 < 1 || nlevels2 > ORBGPU_MAX_LEVELS) return ORB_ERR_ARG;
-    if (!featvec_ok(fv1, n1) || !featvec_ok(fv2, n2))
-        return arg_error("orb_search_for_triangulation", "malformed FeatureVector CSR");
+    if (n1 < 0) return ORB_ERR_ARG;
+    if (!featvec_ok(fv1, n1)) return arg_error("orb_search_for_triangulation", "malformed FeatureVector CSR");
     const orb_tri_pair P{n2, desc2, kps2, has_mp2, uright2, fv2, F12, ex, ey, scale2, sigma2_2, nlevels2, pairs_out, cap,
                          npairs};
+    if (!tri_pair_ok(P))
+        return arg_error("orb_search_for_triangulation", "bad pair arguments (or a KF2 octave outside [0, nlevels2))");
     return tri_run(c, check_ori, only_stereo, TriSide{n1, desc1, kps1, has_mp1, uright1, fv1}, 1, &P);
 }
 
@@ -1124,7 +1133,9 @@ int orb_search_for_triangulation_batch(orb_ctx* h, int check_ori, int only_stere
     if (n1 < 0 || npairs < 0 || (npairs > 0 && !pairs)) return ORB_ERR_ARG;
     if (!featvec_ok(fv1, n1)) return arg_error("orb_search_for_triangulation_batch", "malformed FeatureVector CSR");
     for (int p = 0; p < npairs; p++)
-        if (!tri_pair_ok(pairs[p])) return arg_error("orb_search_for_triangulation_batch", "bad pair arguments");
+        if (!tri_pair_ok(pairs[p]))
+            return arg_error("orb_search_for_triangulation_batch",
+                             "bad pair arguments (or a KF2 octave outside [0, nlevels2))");
     if (npairs == 0) return ORB_OK;
     return tri_run(c, check_ori, only_stereo, TriSide{n1, desc1, kps1, has_mp1, uright1, fv1}, npairs, pairs);
 }
@@ -1443,45 +1454,24 @@ const char* proj_target_fault(int gate, const ProjView& V, int q0, int q1) {
     return nullptr;
 }
 
-// Fuse's reprojection gate (ORBmatcher.cc:914-938): true = the candidate is skipped.  The sums in the reference
-// build's contracted forms (tools/fuse_flags_probe.cpp); fmaf is exact whether it is an instruction or libm's.
-bool fuse_gate_skips(float u, float v, float ur, const orb_keypoint& kp, float urt, float inv_sigma2) {
-    const float ex = u - kp.x, ey = v - kp.y;
-    const float e2m = __builtin_fmaf(ex, ex, ey * ey);
-    if (urt >= 0) {
-        const float er = ur - urt;
-        const float e2 = __builtin_fmaf(er, er, e2m);
-        return (double)(e2 * inv_sigma2) > 7.8;
-    }
-    return (double)(e2m * inv_sigma2) > 5.99;
-}
-
-// One query of a (validated) target on the CPU: k_projection_best's walk over the grid CSR, sequentially.
+// One query of a (validated) target on the CPU: k_projection_best's walk over the grid CSR (grid_window.h),
+// sequentially.
 void proj_best_one(int gate, const orb_proj_target& T, const orb_proj_query& P, const uint8_t* qdesc, int* best_idx,
                    int* best_dist) {
-    const int COLS = kFrameGridCols, ROWS = kFrameGridRows;
     const orb_frame_grid& g = T.grid;
     *best_idx = -1;
     *best_dist = -1;
     const float x = P.u, y = P.v, r = P.r;
-    const int x0 = std::max(0, (int)std::floor((x - g.min_x - r) * g.inv_w));
-    const int x1 = std::min(COLS - 1, (int)std::ceil((x - g.min_x + r) * g.inv_w));
-    const int y0 = std::max(0, (int)std::floor((y - g.min_y - r) * g.inv_h));
-    const int y1 = std::min(ROWS - 1, (int)std::ceil((y - g.min_y + r) * g.inv_h));
-    if (x0 >= COLS || x1 < 0 || y0 >= ROWS || y1 < 0) return;
-    const bool checkLevels = P.min_level > 0 || P.max_level >= 0;
+    const CellRect c = cell_rect(x, y, r, g.min_x, g.min_y, g.inv_w, g.inv_h);
+    if (c.empty) return;
     int bestDist = INT_MAX, bestIdx = -1;
-    for (int ix = x0; ix <= x1; ix++)
-        for (int s = g.cell_off[ix * ROWS + y0]; s < g.cell_off[ix * ROWS + y1 + 1]; s++) {
+    for (int ix = c.x0; ix <= c.x1; ix++)
+        for (int s = g.cell_off[ix * kFrameGridRows + c.y0]; s < g.cell_off[ix * kFrameGridRows + c.y1 + 1]; s++) {
             const int ti = g.cell_idx[s];
             const orb_keypoint& kp = T.kps_t[ti];
-            if (checkLevels) {
-                if (kp.octave < P.min_level) continue;
-                if (P.max_level >= 0 && kp.octave > P.max_level) continue;
-            }
-            if (!(std::fabs(kp.x - x) < r && std::fabs(kp.y - y) < r)) continue;
-            if (gate == ORB_PROJ_GATE_FUSE &&
-                fuse_gate_skips(x, y, P.ur, kp, T.t_uright ? T.t_uright[ti] : -1.0f, T.inv_sigma2[kp.octave]))
+            if (!window_admits(kp, x, y, r, P.min_level, P.max_level)) continue;
+            if (gate == ORB_PROJ_GATE_FUSE && fuse_gate_skips(x, y, P.ur, kp.x, kp.y, T.t_uright ? T.t_uright[ti] : -1.0f,
+                                                              T.inv_sigma2[kp.octave]))
                 continue;
             const int d = orb_descriptor_distance(qdesc, T.tdesc + (size_t)ti * 32);
             if (d < bestDist) {
@@ -1843,24 +1833,14 @@ int orb_features_in_area(int n, const orb_keypoint* kps_un, float mnMinX, float 
         grid[(size_t)px * ROWS + py].push_back(i);
     }
     int cnt = 0;
-    const int x0 = std::max(0, (int)std::floor((x - mnMinX - r) * gw));
-    const int x1 = std::min(COLS - 1, (int)std::ceil((x - mnMinX + r) * gw));
-    const int y0 = std::max(0, (int)std::floor((y - mnMinY - r) * gh));
-    const int y1 = std::min(ROWS - 1, (int)std::ceil((y - mnMinY + r) * gh));
-    if (x0 >= COLS || x1 < 0 || y0 >= ROWS || y1 < 0) return 0;
-    const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
-    for (int ix = x0; ix <= x1; ix++)
-        for (int iy = y0; iy <= y1; iy++)
+    const CellRect c = cell_rect(x, y, r, mnMinX, mnMinY, gw, gh);
+    if (c.empty) return 0;
+    for (int ix = c.x0; ix <= c.x1; ix++)
+        for (int iy = c.y0; iy <= c.y1; iy++)
             for (int idx : grid[(size_t)ix * ROWS + iy]) {
-                const orb_keypoint& k = kps_un[idx];
-                if (checkLevels) {
-                    if (k.octave < minLevel) continue;
-                    if (maxLevel >= 0 && k.octave > maxLevel) continue;
-                }
-                if (std::fabs(k.x - x) < r && std::fabs(k.y - y) < r) {
-                    if (cnt < cap && out) out[cnt] = idx;
-                    cnt++;
-                }
+                if (!window_admits(kps_un[idx], x, y, r, minLevel, maxLevel)) continue;
+                if (cnt < cap && out) out[cnt] = idx;
+                cnt++;
             }
     return cnt > cap ? -cnt - 1 : cnt;
 }

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/orbgpu.h"
+#include "frame_cell.h"
 
 namespace orbgpu {
 
@@ -38,9 +39,10 @@ constexpr int kRrStrip = 8;
 constexpr int kRrMaxRows = 64;        // source rows of a tile it stages at most (8 per staging pass)
 constexpr int kRrMaxChunks = 32;      // 16-byte chunks of a source row it stages at most (one per staging lane)
 // the Frame grid (FRAME_GRID_COLS / FRAME_GRID_ROWS, Frame.h:39-40): an orb_frame_grid's cell_off has
-// kFrameGridCells + 1 entries, cell (ix, iy) at ix * kFrameGridRows + iy
-constexpr int kFrameGridCols = 64;
-constexpr int kFrameGridRows = 48;
+// kFrameGridCells + 1 entries, cell (ix, iy) at ix * kFrameGridRows + iy.  The size is frame_cell.h's (the header a
+// host compiler can read); these names are its aliases.
+constexpr int kFrameGridCols = kCellGridCols;
+constexpr int kFrameGridRows = kCellGridRows;
 constexpr int kFrameGridCells = kFrameGridCols * kFrameGridRows;
 
 // Per-level geometry (host-computed once per image size; lives in device memory).

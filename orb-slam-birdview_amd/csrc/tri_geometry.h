@@ -1,7 +1,7 @@
 // SearchForTriangulation's pair-dependent float work, in the reference build's contracted forms
 // (tools/ref_flags_probe.cpp), compiled by the host (tri_geometry_body, matcher.hip: the staged records of
-// k_triangulation) and by the device (k_triangulation_frames, hamming_kernels.hip: resident frames): one definition
-// of each form.  Every fma is exact whether it is an instruction or libm's fmaf; the translation units that include
+// k_triangulation) and by the device (k_triangulation_frames, hamming_kernels.hip: resident frames; the distance test
+// of both kernels): one definition of each form.  Every fma is exact whether it is an instruction or libm's fmaf; the translation units that include
 // this build with -ffp-contract=off, so the fmaf below are the only fused operations.
 #pragma once
 
@@ -32,5 +32,17 @@ __attribute__((always_inline)) ORB_TRI_HD inline bool tri_near_epipole(float ex,
 
 // pKF2->mvLevelSigma2[kp2.octave] (:156)
 __attribute__((always_inline)) ORB_TRI_HD inline float tri_sigma2(const float* sigma2, int oct) { return sigma2[oct]; }
+
+// CheckDistEpipolarLine's distance test of a KF2 keypoint (x, y) against the line a, b, c (:147-156), den =
+// fma(a, a, b b) computed once per line: den == 0 refuses; num = fma(b, y, a x) + c, dsqr = num num / den in float, and
+// the compare dsqr < 3.84 sigma2 in double (a NaN refuses).  Device only in use: both triangulation kernels call it,
+// and the host has no copy of this test.
+__attribute__((always_inline)) ORB_TRI_HD inline bool tri_epipolar_ok(float la, float lb, float lc, float den, float x,
+                                                                      float y, float sigma2) {
+    if (den == 0) return false;
+    const float num = __builtin_fmaf(lb, y, la * x) + lc;
+    const float dsqr = num * num / den;
+    return (double)dsqr < 3.84 * (double)sigma2;
+}
 
 }  // namespace orbgpu

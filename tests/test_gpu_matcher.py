@@ -579,8 +579,9 @@ def test_search_for_triangulation_batch_local_mapping_order(orbgpu_mod, oracle_m
 
 def test_search_for_triangulation_batch_edges(orbgpu_mod, oracle_mod, frames):
     """An empty pair list, a KF2 without features or without a common node, a malformed KF2 FeatureVector (the whole
-    call refused with ORB_ERR_ARG before anything runs or is written), and one pair's list overflowing (ORB_ERR_CAPACITY,
-    every pair's count and lists still filled)."""
+    call refused with ORB_ERR_ARG before anything runs or is written), one pair's list overflowing (ORB_ERR_CAPACITY,
+    every pair's count and lists still filled), and a KF2 keypoint of the FeatureVector with octave nlevels2 or -1
+    (ORB_ERR_ARG from the single call and from the batch, nothing written)."""
     import ctypes
     from orbgpu import _lib
     ka, da, kb, db = frames
@@ -632,6 +633,28 @@ def test_search_for_triangulation_batch_edges(orbgpu_mod, oracle_mod, frames):
     assert _lib.STATUS.get(st) == "ORB_ERR_CAPACITY"
     assert cnt[0].value == len(single) and cnt[1].value == len(single)
     assert np.array_equal(outs[0][:len(single)], single) and np.array_equal(outs[1][:2], single[:2])
+    # a KF2 keypoint of the FeatureVector with octave nlevels2 or -1 (the host indexes scale2 / sigma2_2 by it):
+    # refused through the single call and as the later pair of a batch, nothing written for any pair
+    i2 = int(np.asarray(next(iter(o["featvec2"].values()))).ravel()[0])
+    for bad_oct in (len(b[5]), -1):
+        kbad = b[1].copy()
+        kbad["octave"][i2] = bad_oct
+        outs = [np.full((n1 + 1, 2), -7, np.int32) for _ in range(2)]
+        cnt = [ctypes.c_int(-5) for _ in range(2)]
+        st = L.orb_search_for_triangulation(m._ctx.h, 0, 0, n1, p(a[0]), p(a[1]), p(a[2]), p(a[3]), fa, len(b[0]),
+                                            p(b[0]), p(kbad), p(b[2]), p(b[3]), fb, p(b[4]), o["ex"], o["ey"], p(b[5]),
+                                            p(b[6]), len(b[5]), p(outs[0]), n1 + 1, ctypes.pointer(cnt[0]))
+        assert _lib.STATUS.get(st) == "ORB_ERR_ARG"
+        assert "orb_search_for_triangulation:" in L.orb_last_error().decode()
+        assert cnt[0].value == -5 and (outs[0] == -7).all()
+        for i, kp2 in enumerate((b[1], kbad)):
+            arr[i] = _lib.OrbTriPair(len(b[0]), p(b[0]), p(kp2), p(b[2]), p(b[3]), fb, p(b[4]), o["ex"], o["ey"],
+                                     p(b[5]), p(b[6]), len(b[5]), p(outs[i]), n1 + 1, ctypes.pointer(cnt[i]))
+        st = L.orb_search_for_triangulation_batch(m._ctx.h, 0, 0, n1, p(a[0]), p(a[1]), p(a[2]), p(a[3]), fa, 2,
+                                                  ctypes.cast(arr, ctypes.c_void_p))
+        assert _lib.STATUS.get(st) == "ORB_ERR_ARG"
+        assert "orb_search_for_triangulation_batch:" in L.orb_last_error().decode()
+        assert all(c.value == -5 for c in cnt) and all((x == -7).all() for x in outs)
 
 
 @pytest.mark.parametrize("level0_only,window", [(True, 100), (False, 15), (True, 40)])

@@ -1,7 +1,8 @@
 // Built with -ffp-contract=off and linked with tools/fuse_flags_probe.cpp (built with the reference's
 // -O3 -march=native -std=c++11).  Checks that the explicit float forms of Fuse's reprojection gate that
-// k_projection_best (csrc/hamming_kernels.hip), orb_project_best_host (csrc/matcher.hip) and
-// tests/kf_projection_ref.py use are the ones GCC produces for the reference's expressions (ORBmatcher.cc:914-938):
+// fuse_gate_skips (csrc/grid_window.h: the one definition k_projection_best and orb_project_best_host compile, called
+// here for the verdict) and tests/kf_projection_ref.py use are the ones GCC produces for the reference's expressions
+// (ORBmatcher.cc:914-938):
 //   stereo  e2 = fmaf(er, er, fmaf(ex, ex, ey * ey)),   skipped when (double)(e2 * invSigma2) > 7.8
 //   mono    e2 = fmaf(ex, ex, ey * ey),                 skipped when (double)(e2 * invSigma2) > 5.99
 // and how often the uncontracted sums would differ.
@@ -16,6 +17,8 @@
 #include <cstring>
 #include <random>
 #include <vector>
+
+#include "../orb-slam-birdview_amd/csrc/grid_window.h"   // (relative to this file: the compile line needs no -I)
 
 namespace fuse_probe {
 struct KeyPoint { float x, y; int octave; };
@@ -64,16 +67,16 @@ int main(int argc, char** argv) {
             const bool stereo = uright[i] >= 0;
             const float is2 = inv[kps[i].octave];
             float want, sep;
-            bool skip, skip_sep;
+            bool skip_sep;
+            // the verdict is the library's own function; e2 is written out here for the bit comparison
+            const bool skip = orbgpu::fuse_gate_skips(u, v, ur, kps[i].x, kps[i].y, uright[i], is2);
             if (stereo) {
                 want = std::fmaf(er, er, std::fmaf(ex, ex, ey * ey));
                 sep = ex * ex + ey * ey + er * er;
-                skip = (double)(want * is2) > 7.8;
                 skip_sep = (double)(sep * is2) > 7.8;
             } else {
                 want = std::fmaf(ex, ex, ey * ey);
                 sep = ex * ex + ey * ey;
-                skip = (double)(want * is2) > 5.99;
                 skip_sep = (double)(sep * is2) > 5.99;
             }
             nstereo += stereo;
