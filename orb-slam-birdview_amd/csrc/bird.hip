@@ -638,6 +638,18 @@ void retain_best(std::vector<SelKey>& kps, int n_points) {
     }
 }
 
+// what Bird::fetch_candidates hands the selection, per frame
+struct BirdCands {
+    std::vector<const BirdCand*> cands;       // the frame's candidates in level order (NULL: it has none)
+    std::vector<int> lvl;                     // kBirdMaxLevels level counts per frame
+    std::vector<size_t> total;                // their sum per frame
+    std::vector<std::vector<BirdCand>> big;   // frames put together from the prefix and the second download
+};
+
+struct BatchFrame {   // keypoints [off, off + ns) of the device buffers are this frame's selection
+    int frame, off, ns;
+};
+
 }  // namespace
 
 struct Bird {
@@ -674,17 +686,26 @@ struct Bird {
     DevBuf<uint8_t> d_desc;
     size_t kp_cap = 0;              // keypoints the four buffers above hold
     DevBuf<float> d_pts;
-    PinBuf<uint8_t> h_pin;
 
-    // batch form: the pyramid, score, blur and row-count buffers hold nb_cap frames fpitch() bytes (or nr + 1
-    // counts) apart, the mask pyramid mnb_cap frames; the single calls use frame 0
+    // the pyramid, score, blur and row-count buffers hold nb_cap frames fpitch() bytes (or nr + 1 counts) apart,
+    // the mask pyramid mnb_cap frames; the single calls are the one-frame case and use frame 0
     int nb_cap = 0, mnb_cap = 0;
     int batch_group = 4;            // frames whose keypoints go up in one upload + angle / subpix / desc launch
                                     // (measured, DESIGN 5.2: 2 .. 8 are within 5 % of each other, 1 and 64 lose more)
-    PinBuf<uint8_t> h_up, h_res;    // pinned: keypoint uploads (device layout), second download / results
+    // pinned staging: h_pin the level counts and candidate prefixes; h_up the keypoint uploads in device layout
+    // (kp_cap keypoints, then kp_cap frame indices); h_res the second candidate download, then the results
+    PinBuf<uint8_t> h_pin, h_up, h_res;
+    orb_keypoint* up_kps() const { return (orb_keypoint*)h_up.get(); }
+    int* up_frames() const { return (int*)(up_kps() + kp_cap); }
     unsigned fpitch() const { return (unsigned)pyr_bytes; }
 
-    // last detect (debug view): candidates per level
+    // host scratch of a call, members for their capacity (a warm call allocates nothing here): the candidates
+    // fetch_candidates hands the selection, one frame's selection, the frames whose keypoints are in flight
+    BirdCands cs;
+    std::vector<HostKP> sel;
+    std::vector<BatchFrame> done;
+
+    // debug view of the last single detect / extract: candidates per level (empty after a batch call)
     std::vector<BirdCand> last_cands;
     std::vector<int> last_lvlcnt;
 
@@ -693,18 +714,19 @@ struct Bird {
     int ensure_geometry(int W, int H, int nl, int nb = 1);
     int ensure_mask_frames(int n);
     int ensure_kp(size_t n);
-    int ensure_pin(size_t bytes);
+    int reserve_kp(size_t n);
     int ensure_pinned(PinBuf<uint8_t>& p, size_t bytes);
     int upload(const uint8_t* img, size_t stride, const uint8_t* mask, size_t mstride, bool footprint, bool device_src,
                int frame = 0, int mask_frame = 0);
     int build_pyramid(int nl, bool with_mask, int nframes = 1, int nmasks = 1);
     int launch_candidates(bool with_mask, int nframes, bool per_frame_mask);
     void select(const BirdCand* cands, const int* lvlcnt, std::vector<HostKP>& sel) const;
-    int detect_select(bool with_mask, std::vector<HostKP>& sel, int blur_levels);
-    int launch_angle(int n);
-    int launch_subpix(int n, bool keep);
+    int fetch_candidates(int nframes, int nmasks, int blur_levels, bool debug_view);
+    int upload_kps(int first, int n, bool frame_table);
+    int launch_angle(int first, int n, const int* kframe);
+    int launch_subpix(int first, int n, const int* kframe);
     int launch_blur(int nl, int nframes = 1);
-    int launch_desc(int n, bool keep);
+    int launch_desc(int first, int n, bool keep, const int* kframe);
 };
 
 void Bird::free_geom() {
@@ -881,7 +903,11 @@ int Bird::ensure_pinned(PinBuf<uint8_t>& p, size_t bytes) {
     return ORB_OK;
 }
 
-int Bird::ensure_pin(size_t bytes) { return ensure_pinned(h_pin, bytes); }
+// keypoint buffers for n keypoints and the pinned staging their upload comes from
+int Bird::reserve_kp(size_t n) {
+    const int r = ensure_kp(n);
+    return r != ORB_OK ? r : ensure_pinned(h_up, kp_cap * (sizeof(orb_keypoint) + sizeof(int)));
+}
 
 // Frame.cc:320-327 footprint rectangle (doubles truncated into cv::Rect, filled, clipped)
 static void footprint_rect(int W, int H, int& x0, int& y0, int& x1, int& y1) {
@@ -958,51 +984,80 @@ int Bird::launch_candidates(bool with_mask, int nframes, bool per_frame_mask) {
     return ORB_OK;
 }
 
-// computeKeyPoints up to the final per-level selection; sel receives the kept keypoints (level coords,
-// octave, size, Harris response) in the reference's order.
-int Bird::detect_select(bool with_mask, std::vector<HostKP>& sel, int blur_levels) {
-    sel.clear();
-    const int nl = g.nlevels;
-    const int nc = (int)crows.size();
+// computeKeyPoints up to the selection, for nframes frames whose pyramids (and nmasks = 0, 1 or nframes mask
+// pyramids) are built: the candidate launches, the blurred pyramid of blur_levels levels behind them (it only
+// needs the pyramid, so it runs while the host selects), then one download of every frame's level counts and
+// speculative candidate prefix (sized from the previous call) and one synchronise; the frames that have more get
+// a second download together.  debug_view (one frame): the frame's candidates are put together in last_cands /
+// last_lvlcnt, which orb_bird_debug_candidates reads; otherwise those are left empty.  The result is in cs.
+int Bird::fetch_candidates(int nframes, int nmasks, int blur_levels, bool debug_view) {
+    const int nl = g.nlevels, B = nframes;
+    BirdCands& out = cs;
+    std::vector<size_t>& total = out.total;
+    int r;
     hipError_t e;
-    last_lvlcnt.assign(nl, 0);
+    out.cands.assign(B, nullptr);
+    out.lvl.assign((size_t)B * kBirdMaxLevels, 0);
+    total.assign(B, 0);
+    out.big.clear();
+    last_lvlcnt.assign(debug_view ? nl : 0, 0);
     last_cands.clear();
-    if (nc > 0) {
-        int r;
-        if ((r = launch_candidates(with_mask, 1, false)) != ORB_OK) return r;
-        // the blurred pyramid only needs the pyramid: it runs while the host selects
-        if (blur_levels > 0 && (r = launch_blur(blur_levels)) != ORB_OK) return r;
-        // one download of the level counts and a speculative prefix of the candidates (sized from the
-        // previous frame); a second only if this frame has more
-        const size_t hdr = 64, guess = std::min(cand_guess, d_cand.cap());
-        if ((r = ensure_pin(hdr + guess * sizeof(BirdCand))) != ORB_OK) return r;
-        uint8_t* hp = h_pin.get();
-        if ((e = hipMemcpyAsync(hp, d_lvlcnt.get(), nl * sizeof(int), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-            (guess && (e = hipMemcpyAsync(hp + hdr, d_cand.get(), guess * sizeof(BirdCand), hipMemcpyDeviceToHost, stream)) !=
-                          hipSuccess) ||
-            (e = hipStreamSynchronize(stream)) != hipSuccess)
+    if (crows.empty()) return blur_levels > 0 ? launch_blur(blur_levels, B) : ORB_OK;
+    if ((r = launch_candidates(nmasks > 0, B, nmasks > 1)) != ORB_OK) return r;
+    if (blur_levels > 0 && (r = launch_blur(blur_levels, B)) != ORB_OK) return r;
+    const size_t slot = cand_slot, guess = std::min(cand_guess, slot);
+    const size_t cnt_bytes = (size_t)B * kBirdMaxLevels * sizeof(int), hdr = (cnt_bytes + 63) & ~(size_t)63;
+    if ((r = ensure_pinned(h_pin, hdr + (size_t)B * guess * sizeof(BirdCand))) != ORB_OK) return r;
+    const int* cnt = (const int*)h_pin.get();
+    BirdCand* pre = (BirdCand*)(h_pin.get() + hdr);
+    if ((e = hipMemcpyAsync(h_pin.get(), d_lvlcnt.get(), cnt_bytes, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+        return set_error("birdview count download", e), ORB_ERR_HIP;
+    for (int f = 0; f < B && guess; f++)
+        if ((e = hipMemcpyAsync(pre + f * guess, d_cand.get() + f * slot, guess * sizeof(BirdCand), hipMemcpyDeviceToHost,
+                                stream)) != hipSuccess)
             return set_error("birdview candidate download", e), ORB_ERR_HIP;
-        std::memcpy(last_lvlcnt.data(), hp, nl * sizeof(int));
-        size_t total = 0;
-        for (int l = 0; l < nl; l++) total += last_lvlcnt[l];
-        if (total > cand_slot) return set_error("birdview candidate overflow", hipSuccess), ORB_ERR_INTERNAL;
-        last_cands.resize(total);
-        std::memcpy(last_cands.data(), hp + hdr, std::min(total, guess) * sizeof(BirdCand));
-        if (total > guess) {
-            const size_t rest = total - guess;
-            if ((r = ensure_pin(rest * sizeof(BirdCand))) != ORB_OK) return r;
-            if ((e = hipMemcpyAsync(h_pin.get(), d_cand.get() + guess, rest * sizeof(BirdCand), hipMemcpyDeviceToHost, stream)) !=
-                    hipSuccess ||
-                (e = hipStreamSynchronize(stream)) != hipSuccess)
-                return set_error("birdview candidates download", e), ORB_ERR_HIP;
-            std::memcpy(last_cands.data() + guess, h_pin.get(), rest * sizeof(BirdCand));
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return set_error("birdview candidate download", e), ORB_ERR_HIP;
+    size_t rest_total = 0, max_total = 0;
+    for (int f = 0; f < B; f++) {
+        for (int l = 0; l < nl; l++) {
+            const int i = f * kBirdMaxLevels + l;
+            out.lvl[i] = cnt[i];
+            total[f] += cnt[i];
         }
-        cand_guess = total + total / 8 + 256;
-    } else if (blur_levels > 0) {
-        int r;
-        if ((r = launch_blur(blur_levels)) != ORB_OK) return r;
+        if (total[f] > slot) return set_error("birdview candidate overflow", hipSuccess), ORB_ERR_INTERNAL;
+        out.cands[f] = pre + f * guess;
+        if (total[f] > guess) rest_total += total[f] - guess;
+        max_total = std::max(max_total, total[f]);
     }
-    select(last_cands.data(), last_lvlcnt.data(), sel);
+    if (rest_total) {
+        if ((r = ensure_pinned(h_res, rest_total * sizeof(BirdCand))) != ORB_OK) return r;
+        BirdCand* hr = (BirdCand*)h_res.get();
+        for (int f = 0; f < B; f++)
+            if (total[f] > guess) {
+                const size_t rest = total[f] - guess;
+                if ((e = hipMemcpyAsync(hr, d_cand.get() + f * slot + guess, rest * sizeof(BirdCand), hipMemcpyDeviceToHost,
+                                        stream)) != hipSuccess)
+                    return set_error("birdview candidates download", e), ORB_ERR_HIP;
+                hr += rest;
+            }
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return set_error("birdview candidates download", e), ORB_ERR_HIP;
+        if (!debug_view) out.big.resize(B);
+    }
+    // a frame above the prefix is put together on the host; so is the frame of the debug view (hr walks the second
+    // download and is read only where a frame has a rest, that is, only when rest_total > 0 has allocated h_res)
+    const BirdCand* hr = (const BirdCand*)h_res.get();
+    for (int f = 0; f < B; f++)
+        if (total[f] > guess || debug_view) {
+            std::vector<BirdCand>& all = debug_view ? last_cands : out.big[f];
+            const size_t head = std::min(total[f], guess), rest = total[f] - head;
+            all.resize(total[f]);
+            if (head) std::memcpy(all.data(), pre + f * guess, head * sizeof(BirdCand));
+            if (rest) std::memcpy(all.data() + head, hr, rest * sizeof(BirdCand));
+            hr += rest;
+            out.cands[f] = all.data();
+        }
+    if (debug_view) last_lvlcnt.assign(out.lvl.begin(), out.lvl.begin() + nl);
+    cand_guess = max_total + max_total / 8 + 256;
     return ORB_OK;
 }
 
@@ -1034,20 +1089,35 @@ void Bird::select(const BirdCand* cands, const int* lvlcnt, std::vector<HostKP>&
     }
 }
 
-int Bird::launch_angle(int n) {
+// keypoints [first, first + n) of the pinned staging to the device, with their frame indices for a frame table
+int Bird::upload_kps(int first, int n, bool frame_table) {
+    hipError_t e;
+    if (n && ((e = hipMemcpyAsync(d_kps.get() + first, up_kps() + first, (size_t)n * sizeof(orb_keypoint),
+                                  hipMemcpyHostToDevice, stream)) != hipSuccess ||
+              (frame_table && (e = hipMemcpyAsync(d_kframe.get() + first, up_frames() + first, (size_t)n * sizeof(int),
+                                                  hipMemcpyHostToDevice, stream)) != hipSuccess)))
+        return set_error("birdview keypoint upload", e), ORB_ERR_HIP;
+    return ORB_OK;
+}
+
+// The per-keypoint launches work on keypoints [first, first + n) of the device buffers.  kframe: the frame of each
+// of them (a pointer into d_kframe), or NULL when the call has one frame: then the kernels read frame 0 and no
+// frame pitch.
+int Bird::launch_angle(int first, int n, const int* kframe) {
     if (n)
-        hipLaunchKernelGGL(k_bird_angle, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom.get(), d_pyr.get(), d_kps.get(), n,
-                           (const int*)nullptr, 0u);
+        hipLaunchKernelGGL(k_bird_angle, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom.get(), d_pyr.get(), d_kps.get() + first, n,
+                           kframe, kframe ? fpitch() : 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_angle", e), ORB_ERR_HIP);
 }
 
-int Bird::launch_subpix(int n, bool keep) {
+// cornerSubPix on the level-0 image of the keypoint's frame, with the border (keep) flag
+int Bird::launch_subpix(int first, int n, const int* kframe) {
     SubpixSrc s{d_pyr.get() + g.L[0].off, g.L[0].pitch, g.L[0].w, g.L[0].h};
     if (n)
         hipLaunchKernelGGL(k_bird_subpix, dim3((n + 3) / 4), dim3(256), 0, stream, s, d_wmask.get(),
-                           reinterpret_cast<float*>(d_kps.get()), 7, n, 40, 0.001 * 0.001, edge, keep ? d_keep.get() : nullptr,
-                           (const int*)nullptr, 0u);
+                           reinterpret_cast<float*>(d_kps.get() + first), 7, n, 40, 0.001 * 0.001, edge, d_keep.get() + first,
+                           kframe, kframe ? fpitch() : 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_subpix", e), ORB_ERR_HIP);
 }
@@ -1062,10 +1132,12 @@ int Bird::launch_blur(int nl, int nframes) {
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_blur", e), ORB_ERR_HIP);
 }
 
-int Bird::launch_desc(int n, bool keep) {
+// descriptors on the blurred pyramid; keep: zero those of the keypoints launch_subpix flagged as culled
+int Bird::launch_desc(int first, int n, bool keep, const int* kframe) {
     if (n)
-        hipLaunchKernelGGL(k_bird_desc, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom.get(), d_pyr.get(), d_blur.get(), d_pattern.get(), d_kps.get(),
-                           keep ? d_keep.get() : nullptr, n, d_desc.get(), (const int*)nullptr, 0u);
+        hipLaunchKernelGGL(k_bird_desc, dim3((n + 3) / 4), dim3(256), 0, stream, d_geom.get(), d_pyr.get(), d_blur.get(), d_pattern.get(),
+                           d_kps.get() + first, keep ? d_keep.get() + first : nullptr, n, d_desc.get() + (size_t)first * 32, kframe,
+                           kframe ? fpitch() : 0u);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ORB_OK : (set_error("k_bird_desc", e), ORB_ERR_HIP);
 }
@@ -1156,116 +1228,11 @@ static void to_kp(const HostKP& h, orb_keypoint& k) {
     k.class_id = h.class_id;
 }
 
-// detect (+ optional cornerSubPix and compute) on an image already in the level-0 slot
-static int bird_run(orb_bird* b, bool with_mask, bool subpix_compute, orb_keypoint* kps, int cap, int* n,
-                    uint8_t* desc) {
-    int r;
-    std::vector<HostKP> sel;
-    if ((r = b->build_pyramid(b->g.nlevels, with_mask)) != ORB_OK) return r;
-    // the fused call blurs every level while the host selects (compute() would blur max octave + 1 of
-    // them; the extra levels are never read)
-    if ((r = b->detect_select(with_mask, sel, subpix_compute ? b->g.nlevels : 0)) != ORB_OK) return r;
-    const int ns = (int)sel.size();
-    if (!subpix_compute && ns > cap) {
-        *n = ns;
-        return set_error("orb_bird_detect: capacity", hipSuccess), ORB_ERR_CAPACITY;
-    }
-    if ((r = b->ensure_kp(std::max(ns, 1))) != ORB_OK) return r;
-    std::vector<orb_keypoint> hk(ns);
-    for (int i = 0; i < ns; i++) to_kp(sel[i], hk[i]);
-    hipError_t e;
-    if (ns && (e = hipMemcpyAsync(b->d_kps.get(), hk.data(), ns * sizeof(orb_keypoint), hipMemcpyHostToDevice, b->stream)) !=
-                  hipSuccess)
-        return set_error("birdview keypoint upload", e), ORB_ERR_HIP;
-    if ((r = b->launch_angle(ns)) != ORB_OK) return r;
-    if (!subpix_compute) {
-        if (ns && ((e = hipMemcpyAsync(kps, b->d_kps.get(), ns * sizeof(orb_keypoint), hipMemcpyDeviceToHost, b->stream)) !=
-                       hipSuccess ||
-                   (e = hipStreamSynchronize(b->stream)) != hipSuccess))
-            return set_error("birdview keypoint download", e), ORB_ERR_HIP;
-        *n = ns;
-        return ORB_OK;
-    }
-    // cornerSubPix on the level-0 image, border flag, descriptors on the blurred pyramid
-    if ((r = b->launch_subpix(ns, true)) != ORB_OK) return r;
-    if ((r = b->launch_desc(ns, true)) != ORB_OK) return r;
-    const size_t kb = (size_t)ns * sizeof(orb_keypoint), fb = (size_t)ns * sizeof(int), db = (size_t)ns * 32;
-    if ((r = b->ensure_pin(kb + fb + db + 64)) != ORB_OK) return r;
-    uint8_t* hp = b->h_pin.get();
-    if (ns && ((e = hipMemcpyAsync(hp, b->d_kps.get(), kb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-               (e = hipMemcpyAsync(hp + kb, b->d_keep.get(), fb, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
-               (e = hipMemcpyAsync(hp + kb + fb, b->d_desc.get(), db, hipMemcpyDeviceToHost, b->stream)) != hipSuccess))
-        return set_error("birdview result download", e), ORB_ERR_HIP;
-    if ((e = hipStreamSynchronize(b->stream)) != hipSuccess) return set_error("birdview sync", e), ORB_ERR_HIP;
-    const orb_keypoint* rk = (const orb_keypoint*)hp;
-    const int* keep = (const int*)(hp + kb);
-    const uint8_t* rd = hp + kb + fb;
-    int m = 0;
-    for (int i = 0; i < ns; i++) m += keep[i] != 0;
-    *n = m;
-    if (m > cap) return set_error("orb_bird_extract: capacity", hipSuccess), ORB_ERR_CAPACITY;
-    for (int i = 0, j = 0; i < ns; i++)
-        if (keep[i]) {
-            kps[j] = rk[i];
-            if (desc) std::memcpy(desc + (size_t)j * 32, rd + (size_t)i * 32, 32);
-            j++;
-        }
-    return ORB_OK;
-}
-
-extern "C" int orb_bird_detect(orb_bird* b, const uint8_t* img, int w, int h, size_t stride, const uint8_t* mask,
-                               size_t mask_stride, orb_keypoint* kps, int cap, int* n) {
-    int r;
-    if ((r = bird_enter(b)) != ORB_OK) return r;
-    if (!n || cap < 0 || (cap && !kps)) return set_error("orb_bird_detect: bad arguments", hipSuccess), ORB_ERR_ARG;
-    if (!img || w <= 0 || h <= 0) {   // Feature2D::detect: empty image -> keypoints.clear()
-        *n = 0;
-        return ORB_OK;
-    }
-    if (stride < (size_t)w || (mask && mask_stride < (size_t)w)) return ORB_ERR_ARG;
-    if ((r = b->ensure_geometry(w, h, b->nlevels)) != ORB_OK) return r;
-    if ((r = b->upload(img, stride, mask, mask_stride, false, false)) != ORB_OK) return r;
-    return bird_run(b, mask != nullptr, false, kps, cap, n, nullptr);
-}
-
-static int bird_extract(orb_bird* b, const uint8_t* img, int w, int h, size_t stride, const uint8_t* mask,
-                        size_t mask_stride, orb_keypoint* kps, int cap, int* n, uint8_t* desc, bool device_src) {
-    int r;
-    if ((r = bird_enter(b)) != ORB_OK) return r;
-    if (!n || cap < 0 || (cap && (!kps || !desc))) return set_error("orb_bird_extract: bad arguments", hipSuccess), ORB_ERR_ARG;
-    if (!img || w <= 0 || h <= 0) {
-        *n = 0;
-        return ORB_OK;
-    }
-    if (stride < (size_t)w || (mask && mask_stride < (size_t)w)) return ORB_ERR_ARG;
-    if ((r = b->ensure_geometry(w, h, b->nlevels)) != ORB_OK) return r;
-    if ((r = b->upload(img, stride, mask, mask_stride, true, device_src)) != ORB_OK) return r;
-    return bird_run(b, mask != nullptr, true, kps, cap, n, desc);
-}
-
-extern "C" int orb_bird_extract(orb_bird* b, const uint8_t* img, int w, int h, size_t stride, const uint8_t* mask,
-                                size_t mask_stride, orb_keypoint* kps, int cap, int* n, uint8_t* desc) {
-    return bird_extract(b, img, w, h, stride, mask, mask_stride, kps, cap, n, desc, false);
-}
-
-extern "C" int orb_bird_extract_device(orb_bird* b, const uint8_t* d_img, int w, int h, size_t stride,
-                                       const uint8_t* d_mask, size_t mask_stride, orb_keypoint* kps, int cap, int* n,
-                                       uint8_t* desc) {
-    return bird_extract(b, d_img, w, h, stride, d_mask, mask_stride, kps, cap, n, desc, true);
-}
-
-/* ---------------- batch form: nframes images of one size through the chain in one call -----------------
+/* ---------------- the host body: nframes images of one size through the chain in one call --------------
  * Every stage before the selection is one launch over all frames; the selection runs frame by frame on
  * the host, and the keypoints of each group of batch_group frames go up and through angle / subpix / desc
- * while the host selects the next group.  One synchronise for the candidates, one at the end. */
-namespace {
-
-struct BatchFrame {   // keypoints [off, off + ns) of the device buffers are this frame's selection
-    int frame, off, ns;
-};
-
-}  // namespace
-
+ * while the host selects the next group.  One synchronise for the candidates, one at the end.  The single
+ * calls are the case of one frame: no frame table is written or uploaded, the kernels get kframe == NULL. */
 // download everything launched so far; compact each frame by its keep flags into the caller's slot
 static int bird_batch_flush(orb_bird* b, std::vector<BatchFrame>& done, int used, orb_keypoint* kps, uint8_t* desc,
                             int cap, int* counts, bool& over) {
@@ -1303,117 +1270,39 @@ static int bird_batch_flush(orb_bird* b, std::vector<BatchFrame>& done, int used
     return ORB_OK;
 }
 
-// the frames (and nmasks = 0, 1 or B footprint-zeroed masks) are in the level-0 slots
-static int bird_batch_run(orb_bird* b, int B, int nmasks, orb_keypoint* kps, uint8_t* desc, int cap, int* counts) {
+// Frame.cc:329-342 for B frames: level 0 of every frame, and of nmasks = 0, 1 or B footprint-zeroed masks, is in
+// its slot, and bird_reserve has run.  fn names the entry point in the capacity error.  debug_view: see
+// Bird::fetch_candidates.
+static int bird_body(orb_bird* b, const char* fn, int B, int nmasks, bool debug_view, orb_keypoint* kps, uint8_t* desc,
+                     int cap, int* counts) {
     int r;
-    hipError_t e;
-    const int nl = b->g.nlevels, nc = (int)b->crows.size();
-    const bool with_mask = nmasks > 0;
-    if ((r = b->build_pyramid(nl, with_mask, B, std::max(nmasks, 1))) != ORB_OK) return r;
-    b->last_lvlcnt.clear();   // the debug views describe single calls only
-    b->last_cands.clear();
-    std::vector<const BirdCand*> cands(B, nullptr);
-    std::vector<int> lvl((size_t)B * kBirdMaxLevels, 0);
-    std::vector<std::vector<BirdCand>> big;   // frames whose candidates exceed the speculative prefix
-    if (nc > 0) {
-        if ((r = b->launch_candidates(with_mask, B, nmasks > 1)) != ORB_OK) return r;
-        // the blurred pyramids only need the pyramids: they run while the host selects
-        if ((r = b->launch_blur(nl, B)) != ORB_OK) return r;
-        // one download of every frame's level counts and speculative candidate prefix, one synchronise;
-        // a second download only for the frames that have more
-        const size_t slot = b->cand_slot, guess = std::min(b->cand_guess, slot);
-        const size_t hdr = ((size_t)B * kBirdMaxLevels * sizeof(int) + 63) & ~(size_t)63;
-        if ((r = b->ensure_pin(hdr + (size_t)B * guess * sizeof(BirdCand))) != ORB_OK) return r;
-        uint8_t* hp = b->h_pin.get();
-        if ((e = hipMemcpyAsync(hp, b->d_lvlcnt.get(), (size_t)B * kBirdMaxLevels * sizeof(int), hipMemcpyDeviceToHost,
-                                b->stream)) != hipSuccess)
-            return set_error("birdview count download", e), ORB_ERR_HIP;
-        const BirdCand* pre = (const BirdCand*)(hp + hdr);
-        for (int f = 0; f < B && guess; f++)
-            if ((e = hipMemcpyAsync((void*)(pre + f * guess), b->d_cand.get() + f * slot, guess * sizeof(BirdCand),
-                                    hipMemcpyDeviceToHost, b->stream)) != hipSuccess)
-                return set_error("birdview candidate download", e), ORB_ERR_HIP;
-        if ((e = hipStreamSynchronize(b->stream)) != hipSuccess)
-            return set_error("birdview candidate download", e), ORB_ERR_HIP;
-        std::vector<size_t> total(B, 0);
-        size_t rest_total = 0, max_total = 0;
-        for (int f = 0; f < B; f++) {
-            for (int l = 0; l < nl; l++) {
-                lvl[(size_t)f * kBirdMaxLevels + l] = ((const int*)hp)[f * kBirdMaxLevels + l];
-                total[f] += lvl[(size_t)f * kBirdMaxLevels + l];
-            }
-            if (total[f] > slot) return set_error("birdview candidate overflow", hipSuccess), ORB_ERR_INTERNAL;
-            cands[f] = pre + f * guess;
-            if (total[f] > guess) rest_total += total[f] - guess;
-            max_total = std::max(max_total, total[f]);
-        }
-        if (rest_total) {
-            if ((r = b->ensure_pinned(b->h_res, rest_total * sizeof(BirdCand))) != ORB_OK) return r;
-            BirdCand* hr = (BirdCand*)b->h_res.get();
-            size_t ro = 0;
-            for (int f = 0; f < B; f++)
-                if (total[f] > guess) {
-                    const size_t rest = total[f] - guess;
-                    if ((e = hipMemcpyAsync(hr + ro, b->d_cand.get() + f * slot + guess, rest * sizeof(BirdCand),
-                                            hipMemcpyDeviceToHost, b->stream)) != hipSuccess)
-                        return set_error("birdview candidates download", e), ORB_ERR_HIP;
-                    ro += rest;
-                }
-            if ((e = hipStreamSynchronize(b->stream)) != hipSuccess)
-                return set_error("birdview candidates download", e), ORB_ERR_HIP;
-            big.resize(B);
-            ro = 0;
-            for (int f = 0; f < B; f++)
-                if (total[f] > guess) {
-                    const size_t rest = total[f] - guess;
-                    big[f].resize(total[f]);
-                    std::memcpy(big[f].data(), pre + f * guess, guess * sizeof(BirdCand));
-                    std::memcpy(big[f].data() + guess, hr + ro, rest * sizeof(BirdCand));
-                    ro += rest;
-                    cands[f] = big[f].data();
-                }
-        }
-        b->cand_guess = max_total + max_total / 8 + 256;
-    } else if ((r = b->launch_blur(nl, B)) != ORB_OK) {
-        return r;
-    }
+    const int nl = b->g.nlevels;
+    if ((r = b->build_pyramid(nl, nmasks > 0, B, std::max(nmasks, 1))) != ORB_OK) return r;
+    // every level is blurred (compute() would blur max octave + 1 of them; the extra levels are never read)
+    if ((r = b->fetch_candidates(B, nmasks, nl, debug_view)) != ORB_OK) return r;
+    const BirdCands& c = b->cs;
 
     // selection frame by frame; each full group goes up and through its kernels behind the host
-    orb_keypoint* up_k = (orb_keypoint*)b->h_up.get();
-    int* up_f = (int*)(b->h_up.get() + b->kp_cap * sizeof(orb_keypoint));
-    std::vector<BatchFrame> done;
-    std::vector<HostKP> sel;
+    std::vector<BatchFrame>& done = b->done;
+    std::vector<HostKP>& sel = b->sel;
+    done.clear();
     int used = 0, g0 = 0, gframes = 0;
     bool over = false;
-    const unsigned fp = b->fpitch();
-    const BirdLevel L0 = b->g.L[0];
+    const bool frame_table = B > 1;
     auto launch_group = [&]() -> int {
         const int n = used - g0;
-        if (n) {
-            hipError_t le;
-            if ((le = hipMemcpyAsync(b->d_kps.get() + g0, up_k + g0, (size_t)n * sizeof(orb_keypoint), hipMemcpyHostToDevice,
-                                     b->stream)) != hipSuccess ||
-                (le = hipMemcpyAsync(b->d_kframe.get() + g0, up_f + g0, (size_t)n * sizeof(int), hipMemcpyHostToDevice,
-                                     b->stream)) != hipSuccess)
-                return set_error("birdview keypoint upload", le), ORB_ERR_HIP;
-            const dim3 grid((n + 3) / 4), block(256);
-            const int* kf = b->d_kframe.get() + g0;
-            hipLaunchKernelGGL(k_bird_angle, grid, block, 0, b->stream, b->d_geom.get(), b->d_pyr.get(), b->d_kps.get() + g0, n, kf, fp);
-            SubpixSrc s{b->d_pyr.get() + L0.off, L0.pitch, L0.w, L0.h};
-            hipLaunchKernelGGL(k_bird_subpix, grid, block, 0, b->stream, s, b->d_wmask.get(),
-                               reinterpret_cast<float*>(b->d_kps.get() + g0), 7, n, 40, 0.001 * 0.001, b->edge, b->d_keep.get() + g0,
-                               kf, fp);
-            hipLaunchKernelGGL(k_bird_desc, grid, block, 0, b->stream, b->d_geom.get(), b->d_pyr.get(), b->d_blur.get(), b->d_pattern.get(),
-                               b->d_kps.get() + g0, b->d_keep.get() + g0, n, b->d_desc.get() + (size_t)g0 * 32, kf, fp);
-            if ((le = hipGetLastError()) != hipSuccess) return set_error("birdview keypoint kernels", le), ORB_ERR_HIP;
-        }
+        const int* kf = frame_table ? b->d_kframe.get() + g0 : nullptr;
+        int lr;
+        if (n && ((lr = b->upload_kps(g0, n, frame_table)) != ORB_OK || (lr = b->launch_angle(g0, n, kf)) != ORB_OK ||
+            (lr = b->launch_subpix(g0, n, kf)) != ORB_OK || (lr = b->launch_desc(g0, n, true, kf)) != ORB_OK))
+            return lr;
         g0 = used;
         gframes = 0;
         return ORB_OK;
     };
     for (int f = 0; f < B; f++) {
         sel.clear();
-        if (cands[f]) b->select(cands[f], &lvl[(size_t)f * kBirdMaxLevels], sel);
+        if (c.cands[f]) b->select(c.cands[f], &c.lvl[(size_t)f * kBirdMaxLevels], sel);
         const int ns = (int)sel.size();
         if ((size_t)used + ns > b->kp_cap) {
             // boundary ties kept more than nfeatures per frame: drain what is in flight, then grow if needed
@@ -1421,42 +1310,38 @@ static int bird_batch_run(orb_bird* b, int B, int nmasks, orb_keypoint* kps, uin
                 (r = bird_batch_flush(b, done, used, kps, desc, cap, counts, over)) != ORB_OK)
                 return r;
             used = g0 = 0;
-            if ((r = b->ensure_kp(ns)) != ORB_OK ||
-                (r = b->ensure_pinned(b->h_up, b->kp_cap * (sizeof(orb_keypoint) + sizeof(int)))) != ORB_OK)
-                return r;
-            up_k = (orb_keypoint*)b->h_up.get();
-            up_f = (int*)(b->h_up.get() + b->kp_cap * sizeof(orb_keypoint));
+            if ((r = b->reserve_kp(ns)) != ORB_OK) return r;
         }
-        for (int i = 0; i < ns; i++) {
-            to_kp(sel[i], up_k[used + i]);
-            up_f[used + i] = f;
-        }
+        for (int i = 0; i < ns; i++) to_kp(sel[i], b->up_kps()[used + i]);
+        if (frame_table) std::fill_n(b->up_frames() + used, ns, f);
         done.push_back({f, used, ns});
         used += ns;
         if (++gframes >= b->batch_group && (r = launch_group()) != ORB_OK) return r;
     }
     if ((r = launch_group()) != ORB_OK) return r;
     if ((r = bird_batch_flush(b, done, used, kps, desc, cap, counts, over)) != ORB_OK) return r;
-    if (over) return set_error("orb_bird_extract_batch: capacity", hipSuccess), ORB_ERR_CAPACITY;
+    if (over) return set_error((std::string(fn) + ": capacity").c_str(), hipSuccess), ORB_ERR_CAPACITY;
     return ORB_OK;
 }
 
-// argument rules shared by the two batch forms; *done: the call is complete (nothing to do)
-static int bird_batch_enter(orb_bird* b, int nframes, const void* imgs, int w, int h, size_t stride, size_t frame_pitch,
-                            bool with_mask, size_t mask_stride, size_t mask_frame_pitch, const orb_keypoint* kps,
-                            const uint8_t* desc, int cap, int* counts, bool* done) {
+// argument rules of detect, extract and the batch forms, named fn in the messages (a single call is nframes 1 with
+// its count as counts); *done: the call is complete (nothing to do)
+static int bird_frames_enter(orb_bird* b, const char* fn, int nframes, const void* imgs, int w, int h, size_t stride,
+                             size_t frame_pitch, bool with_mask, size_t mask_stride, size_t mask_frame_pitch,
+                             const orb_keypoint* kps, const uint8_t* desc, bool need_desc, int cap, int* counts,
+                             bool* done) {
     *done = true;
     if (!b) return set_error("NULL orb_bird", hipSuccess), ORB_ERR_ARG;
-    if (nframes < 0 || nframes > ORB_BIRD_MAX_BATCH || !counts || cap < 0 || (cap && (!kps || !desc)))
-        return set_error("orb_bird_extract_batch: bad arguments", hipSuccess), ORB_ERR_ARG;
+    if (nframes < 0 || nframes > ORB_BIRD_MAX_BATCH || !counts || cap < 0 || (cap && (!kps || (need_desc && !desc))))
+        return arg_error(fn, "bad arguments");
     if (nframes == 0) return ORB_OK;
-    if (!imgs || w <= 0 || h <= 0) {
+    if (!imgs || w <= 0 || h <= 0) {   // Feature2D::detect: empty image -> keypoints.clear()
         for (int f = 0; f < nframes; f++) counts[f] = 0;
         return ORB_OK;
     }
     if (stride < (size_t)w || frame_pitch < stride * (size_t)h ||
         (with_mask && (mask_stride < (size_t)w || (mask_frame_pitch && mask_frame_pitch < mask_stride * (size_t)h))))
-        return set_error("orb_bird_extract_batch: bad strides", hipSuccess), ORB_ERR_ARG;
+        return arg_error(fn, "bad strides");
     int r;
     if ((r = bird_enter(b)) != ORB_OK) return r;
     *done = false;
@@ -1464,26 +1349,85 @@ static int bird_batch_enter(orb_bird* b, int nframes, const void* imgs, int w, i
 }
 
 // buffers for B frames of w x h with nmasks mask pyramids, keypoint buffers for the expected selection
-static int bird_batch_reserve(orb_bird* b, int B, int w, int h, int nmasks) {
+static int bird_reserve(orb_bird* b, int B, int w, int h, int nmasks) {
     int r;
     if ((r = b->ensure_geometry(w, h, b->nlevels, B)) != ORB_OK) return r;
     if ((r = b->ensure_mask_frames(nmasks)) != ORB_OK) return r;
-    if ((r = b->ensure_kp((size_t)B * ((size_t)b->nfeatures + 64))) != ORB_OK) return r;
-    return b->ensure_pinned(b->h_up, b->kp_cap * (sizeof(orb_keypoint) + sizeof(int)));
+    return b->reserve_kp((size_t)B * ((size_t)b->nfeatures + 64));
+}
+
+extern "C" int orb_bird_detect(orb_bird* b, const uint8_t* img, int w, int h, size_t stride, const uint8_t* mask,
+                               size_t mask_stride, orb_keypoint* kps, int cap, int* n) {
+    static const char* fn = "orb_bird_detect";
+    int r;
+    bool done;
+    if ((r = bird_frames_enter(b, fn, 1, img, w, h, stride, stride * (size_t)(h > 0 ? h : 0), mask != nullptr, mask_stride,
+                               0, kps, nullptr, false, cap, n, &done)) != ORB_OK ||
+        done)
+        return r;
+    const int nmasks = mask ? 1 : 0;
+    if ((r = b->ensure_geometry(w, h, b->nlevels)) != ORB_OK) return r;
+    if ((r = b->upload(img, stride, mask, mask_stride, false, false)) != ORB_OK) return r;
+    if ((r = b->build_pyramid(b->g.nlevels, nmasks > 0)) != ORB_OK) return r;
+    if ((r = b->fetch_candidates(1, nmasks, 0, true)) != ORB_OK) return r;
+    const BirdCands& c = b->cs;
+    std::vector<HostKP>& sel = b->sel;
+    sel.clear();
+    if (c.cands[0]) b->select(c.cands[0], c.lvl.data(), sel);
+    const int ns = (int)sel.size();
+    *n = ns;
+    if (ns > cap) return set_error("orb_bird_detect: capacity", hipSuccess), ORB_ERR_CAPACITY;
+    if ((r = b->reserve_kp(std::max(ns, 1))) != ORB_OK) return r;
+    for (int i = 0; i < ns; i++) to_kp(sel[i], b->up_kps()[i]);
+    if ((r = b->upload_kps(0, ns, false)) != ORB_OK || (r = b->launch_angle(0, ns, nullptr)) != ORB_OK) return r;
+    hipError_t e;
+    if (ns && ((e = hipMemcpyAsync(kps, b->d_kps.get(), ns * sizeof(orb_keypoint), hipMemcpyDeviceToHost, b->stream)) !=
+                   hipSuccess ||
+               (e = hipStreamSynchronize(b->stream)) != hipSuccess))
+        return set_error("birdview keypoint download", e), ORB_ERR_HIP;
+    return ORB_OK;
+}
+
+// the fused single call: one frame of the body, level 0 by strided copies from the host or the device
+static int bird_extract(orb_bird* b, const uint8_t* img, int w, int h, size_t stride, const uint8_t* mask,
+                        size_t mask_stride, orb_keypoint* kps, int cap, int* n, uint8_t* desc, bool device_src) {
+    static const char* fn = "orb_bird_extract";
+    int r;
+    bool done;
+    if ((r = bird_frames_enter(b, fn, 1, img, w, h, stride, stride * (size_t)(h > 0 ? h : 0), mask != nullptr, mask_stride,
+                               0, kps, desc, true, cap, n, &done)) != ORB_OK ||
+        done)
+        return r;
+    const int nmasks = mask ? 1 : 0;
+    if ((r = bird_reserve(b, 1, w, h, nmasks)) != ORB_OK) return r;
+    if ((r = b->upload(img, stride, mask, mask_stride, true, device_src)) != ORB_OK) return r;
+    return bird_body(b, fn, 1, nmasks, true, kps, desc, cap, n);
+}
+
+extern "C" int orb_bird_extract(orb_bird* b, const uint8_t* img, int w, int h, size_t stride, const uint8_t* mask,
+                                size_t mask_stride, orb_keypoint* kps, int cap, int* n, uint8_t* desc) {
+    return bird_extract(b, img, w, h, stride, mask, mask_stride, kps, cap, n, desc, false);
+}
+
+extern "C" int orb_bird_extract_device(orb_bird* b, const uint8_t* d_img, int w, int h, size_t stride,
+                                       const uint8_t* d_mask, size_t mask_stride, orb_keypoint* kps, int cap, int* n,
+                                       uint8_t* desc) {
+    return bird_extract(b, d_img, w, h, stride, d_mask, mask_stride, kps, cap, n, desc, true);
 }
 
 extern "C" int orb_bird_extract_batch_device(orb_bird* b, int nframes, const uint8_t* d_imgs, int w, int h,
                                              size_t stride, size_t frame_pitch, const uint8_t* d_masks,
                                              size_t mask_stride, size_t mask_frame_pitch, orb_keypoint* kps,
                                              uint8_t* desc, int cap, int* counts) {
+    static const char* fn = "orb_bird_extract_batch";
     int r;
     bool done;
-    if ((r = bird_batch_enter(b, nframes, d_imgs, w, h, stride, frame_pitch, d_masks != nullptr, mask_stride,
-                              mask_frame_pitch, kps, desc, cap, counts, &done)) != ORB_OK ||
+    if ((r = bird_frames_enter(b, fn, nframes, d_imgs, w, h, stride, frame_pitch, d_masks != nullptr, mask_stride,
+                               mask_frame_pitch, kps, desc, true, cap, counts, &done)) != ORB_OK ||
         done)
         return r;
     const int nmasks = !d_masks ? 0 : (mask_frame_pitch ? nframes : 1);
-    if ((r = bird_batch_reserve(b, nframes, w, h, nmasks)) != ORB_OK) return r;
+    if ((r = bird_reserve(b, nframes, w, h, nmasks)) != ORB_OK) return r;
     int x0, y0, x1, y1;
     footprint_rect(w, h, x0, y0, x1, y1);
     hipLaunchKernelGGL(k_bird_ingest, dim3((w + 255) / 256, h, nframes + nmasks), dim3(256), 0, b->stream, b->d_geom.get(),
@@ -1491,12 +1435,13 @@ extern "C" int orb_bird_extract_batch_device(orb_bird* b, int nframes, const uin
                        b->fpitch(), x0, y0, x1, y1);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error("k_bird_ingest", e), ORB_ERR_HIP;
-    return bird_batch_run(b, nframes, nmasks, kps, desc, cap, counts);
+    return bird_body(b, fn, nframes, nmasks, false, kps, desc, cap, counts);
 }
 
 extern "C" int orb_bird_extract_batch(orb_bird* b, int nframes, const uint8_t* const* imgs, int w, int h, size_t stride,
                                       const uint8_t* const* masks, int nmasks, size_t mask_stride, orb_keypoint* kps,
                                       uint8_t* desc, int cap, int* counts) {
+    static const char* fn = "orb_bird_extract_batch";
     int r;
     bool done;
     if (nframes >= 0 && nmasks != 0 && nmasks != 1 && nmasks != nframes)
@@ -1508,16 +1453,16 @@ extern "C" int orb_bird_extract_batch(orb_bird* b, int nframes, const uint8_t* c
         for (int m = 0; m < nmasks; m++)
             if (!masks[m]) return set_error("orb_bird_extract_batch: NULL mask", hipSuccess), ORB_ERR_ARG;
     }
-    if ((r = bird_batch_enter(b, nframes, imgs, w, h, stride, stride * (size_t)(h > 0 ? h : 0), nmasks > 0, mask_stride, 0,
-                              kps, desc, cap, counts, &done)) != ORB_OK ||
+    if ((r = bird_frames_enter(b, fn, nframes, imgs, w, h, stride, stride * (size_t)(h > 0 ? h : 0), nmasks > 0, mask_stride,
+                               0, kps, desc, true, cap, counts, &done)) != ORB_OK ||
         done)
         return r;
-    if ((r = bird_batch_reserve(b, nframes, w, h, nmasks)) != ORB_OK) return r;
+    if ((r = bird_reserve(b, nframes, w, h, nmasks)) != ORB_OK) return r;
     for (int f = 0; f < nframes; f++)
         if ((r = b->upload(imgs[f], stride, nullptr, 0, false, false, f, 0)) != ORB_OK) return r;
     for (int m = 0; m < nmasks; m++)
         if ((r = b->upload(nullptr, 0, masks[m], mask_stride, true, false, 0, m)) != ORB_OK) return r;
-    return bird_batch_run(b, nframes, nmasks, kps, desc, cap, counts);
+    return bird_body(b, fn, nframes, nmasks, false, kps, desc, cap, counts);
 }
 
 extern "C" int orb_bird_batch_group(orb_bird* b, int group) {
@@ -1573,7 +1518,7 @@ extern "C" int orb_bird_compute(orb_bird* b, const uint8_t* img, int w, int h, s
     if ((he = hipMemcpyAsync(b->d_kps.get(), v.data(), m * sizeof(orb_keypoint), hipMemcpyHostToDevice, b->stream)) !=
         hipSuccess)
         return set_error("birdview keypoint upload", he), ORB_ERR_HIP;
-    if ((r = b->launch_blur(nl)) != ORB_OK || (r = b->launch_desc(m, false)) != ORB_OK) return r;
+    if ((r = b->launch_blur(nl)) != ORB_OK || (r = b->launch_desc(0, m, false, nullptr)) != ORB_OK) return r;
     if ((he = hipMemcpyAsync(desc, b->d_desc.get(), (size_t)m * 32, hipMemcpyDeviceToHost, b->stream)) != hipSuccess ||
         (he = hipStreamSynchronize(b->stream)) != hipSuccess)
         return set_error("birdview descriptor download", he), ORB_ERR_HIP;

@@ -36,16 +36,26 @@ def expected(nf, fr, mask_idx):
     return k, d
 
 
+def footprint_mask(w, h, mask_idx):
+    """The mask detect sees inside extract: the footprint zeroed (None: no mask)."""
+    if mask_idx is None:
+        return None
+    import orbgpu
+    return orbgpu.bird_footprint_mask(mask(w, h, mask_idx))
+
+
 @functools.lru_cache(maxsize=None)
+def detect_oracle(nf, fr, mask_idx):
+    """(keypoints of the oracle's detect with the footprint mask, its candidates per level)."""
+    import oracle
+    o = oracle.OracleCvORB(nf)
+    k = o.detect(frame(*fr), footprint_mask(fr[0], fr[1], mask_idx))
+    return k, [o.candidates(l) for l in range(8)]
+
+
 def detected(nf, fr, mask_idx):
     """Keypoints the oracle's detect keeps before cornerSubPix and the border cull of compute."""
-    import oracle
-    w, h = fr[0], fr[1]
-    m = None
-    if mask_idx is not None:
-        import orbgpu
-        m = orbgpu.bird_footprint_mask(mask(w, h, mask_idx))
-    return len(oracle.OracleCvORB(nf).detect(frame(*fr), m))
+    return len(detect_oracle(nf, fr, mask_idx)[0])
 
 
 def assert_frame(got, nf, fr, mask_idx, what):

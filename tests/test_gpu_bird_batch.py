@@ -305,3 +305,142 @@ def test_group_size_does_not_change_results(orbgpu_mod, group):
         _check(_run_device(b, frames, ids), NF, frames, ids, f"group {group}")
     finally:
         b.close()
+
+
+# ---------------------------------------------------------------- the single calls: one frame of the same body
+def _views_equal(b, cands, what):
+    """debug_candidates(l) against the oracle's candidates of every level (test_bird_pyramid_and_candidates)."""
+    for l in range(8):
+        co, cg = cands[l], b.debug_candidates(l)
+        assert len(cg) == len(co), f"{what}: level {l}: {len(cg)} vs {len(co)}"
+        for f in ("x", "y", "octave", "class_id"):
+            assert np.array_equal(cg[f], co[f]), (what, l, f)
+        assert cg["response"].tobytes() == co["response"].tobytes(), f"{what}: Harris level {l}"
+
+
+def _detect(b, nf, fr, mask_idx, what):
+    kg = b.detect(bc.frame(*fr), bc.footprint_mask(fr[0], fr[1], mask_idx))
+    ko = bc.detect_oracle(nf, fr, mask_idx)[0]
+    assert len(kg) == len(ko), (what, len(kg), len(ko))
+    assert kg.tobytes() == ko.tobytes(), (what, "detect")
+
+
+def test_single_extract_second_download(orbgpu_mod):
+    """A single extract whose frame has more candidates (55,495) than the 16,384 prefix of a fresh object, and
+    keypoints culled after cornerSubPix; again with the grown prefix (one download); then a frame that fits."""
+    scene, noise = (640, 480, 12, "scene"), (640, 480, 3, "noise")
+    b = orbgpu_mod.BirdORB(2000)
+    try:
+        bc.assert_frame(b.extract(bc.frame(*noise)), 2000, noise, None, "noise, second download")
+        bc.assert_frame(b.extract(bc.frame(*noise)), 2000, noise, None, "noise, one download")
+        bc.assert_frame(b.extract(bc.frame(*scene), bc.mask(640, 480, 12).copy()), 2000, scene, 12, "scene")
+    finally:
+        b.close()
+    assert bc.detected(2000, noise, None) - len(bc.expected(2000, noise, None)[0]) == 2
+
+
+def test_single_calls_after_batch(orbgpu_mod):
+    """After a batch of five the candidate buffer holds five slots: the single calls' prefix stays within one."""
+    ids = [fr[2] for fr in bc.FIVE]
+    noise = bc.FIVE[4]
+    b = orbgpu_mod.BirdORB(NF)
+    try:
+        _check(_run_device(b, bc.FIVE, ids), NF, bc.FIVE, ids, "B=5")
+        bc.assert_frame(b.extract(bc.frame(*noise), bc.mask(320, 240, 8).copy()), NF, noise, 8, "extract after B=5")
+        _detect(b, NF, noise, 8, "detect after B=5")
+        _detect(b, NF, noise, None, "detect after B=5, no mask")
+    finally:
+        b.close()
+
+
+def test_debug_views(orbgpu_mod):
+    """orb_bird_debug_candidates describes the last single detect or extract and nothing after a batch call."""
+    from orbgpu import KP_DTYPE
+    from orbgpu._lib import lib
+    a, c = bc.FIVE[0], bc.FIVE[3]
+    b = orbgpu_mod.BirdORB(NF)
+    try:
+        _detect(b, NF, a, a[2], "detect")
+        _views_equal(b, bc.detect_oracle(NF, a, a[2])[1], "after detect")
+        _check(_run_host(b, [a, c], [a[2], c[2]]), NF, [a, c], [a[2], c[2]], "B=2")
+        out = np.zeros(1 << 16, KP_DTYPE)
+        assert lib().orb_bird_debug_candidates(b.h, 0, out.ctypes.data_as(ctypes.c_void_p), len(out)) == ERR_ARG
+        bc.assert_frame(b.extract(bc.frame(*c), bc.mask(320, 240, c[2]).copy()), NF, c, c[2], "extract")
+        _views_equal(b, bc.detect_oracle(NF, c, c[2])[1], "after extract")
+    finally:
+        b.close()
+
+
+def _raw_single(orbgpu_mod, bird, fr, mask_idx, cap, detect, poison=0xCD):
+    """orb_bird_extract_device, or orb_bird_detect with the footprint mask, on poisoned outputs ->
+    (status, n, kps, desc)."""
+    import torch
+    from orbgpu import KP_DTYPE
+    from orbgpu._lib import lib
+    w, h = fr[:2]
+    kps = np.frombuffer(bytes([poison]) * (max(cap, 1) * KP_DTYPE.itemsize), KP_DTYPE).copy()
+    desc = np.full((max(cap, 1), 32), poison, np.uint8)
+    n = ctypes.c_int(-77)
+    pk, pd = kps.ctypes.data_as(ctypes.c_void_p), desc.ctypes.data_as(ctypes.c_void_p)
+    if detect:
+        img, m = bc.frame(*fr), bc.footprint_mask(w, h, mask_idx)
+        st = lib().orb_bird_detect(bird.h, img.ctypes.data_as(ctypes.c_void_p), w, h, w,
+                                   m.ctypes.data_as(ctypes.c_void_p), w, pk, cap, ctypes.byref(n))
+    else:
+        di = torch.from_numpy(bc.frame(*fr).copy()).cuda()
+        dm = torch.from_numpy(bc.mask(w, h, mask_idx).copy()).cuda()
+        torch.cuda.synchronize()
+        st = lib().orb_bird_extract_device(bird.h, ctypes.c_void_p(di.data_ptr()), w, h, w, ctypes.c_void_p(dm.data_ptr()),
+                                           w, pk, cap, ctypes.byref(n), pd)
+    return st, n.value, kps, desc
+
+
+@pytest.mark.parametrize("detect", [False, True])
+def test_capacity_single_calls(orbgpu_mod, bird, detect):
+    fr, mi = bc.FIVE[0], bc.FIVE[0][2]
+    ko, do = bc.expected(NF, fr, mi)
+    if detect:
+        ko = bc.detect_oracle(NF, fr, mi)[0]
+    want = len(ko)
+    assert want > 1
+    st, n, kps, desc = _raw_single(orbgpu_mod, bird, fr, mi, want - 1, detect)
+    assert st == ERR_CAPACITY and n == want
+    assert _poisoned(kps) and _poisoned(desc)
+    # with room for exactly the count the call succeeds; with two slots more, those keep their poison
+    st, n, kps, desc = _raw_single(orbgpu_mod, bird, fr, mi, want, detect)
+    assert st == 0 and n == want
+    st2, n2, kps2, desc2 = _raw_single(orbgpu_mod, bird, fr, mi, want + 2, detect)
+    assert st2 == 0 and n2 == want
+    for k, d in ((kps, desc), (kps2, desc2)):
+        assert k[:want].tobytes() == ko.tobytes()
+        assert _poisoned(k[want:])
+        if detect:
+            assert _poisoned(d)
+        else:
+            assert d[:want].tobytes() == do.tobytes() and _poisoned(d[want:])
+
+
+@pytest.mark.parametrize("batch_first", [True, False])
+def test_single_call_equals_batch_of_one(orbgpu_mod, batch_first):
+    """One frame through orb_bird_extract_batch_device and through orb_bird_extract_device on one object, in both
+    orders: either call leaves the object's buffers fit for the other."""
+    import torch
+    fr, mi = bc.FIVE[3], bc.FIVE[3][2]
+    di = torch.from_numpy(bc.frame(*fr).copy()).cuda()
+    dm = torch.from_numpy(bc.mask(320, 240, mi).copy()).cuda()
+    torch.cuda.synchronize()
+    b = orbgpu_mod.BirdORB(NF)
+    try:
+        def single():
+            k, d = b.extract_device(di.data_ptr(), 320, 240, dm.data_ptr())
+            return k.copy(), d.copy()
+
+        def batch():
+            return b.extract_batch_device(di.data_ptr(), 1, 320, 240, d_masks=dm.data_ptr())[0]
+
+        runs = [batch(), single(), batch()] if batch_first else [single(), batch(), single()]
+        for i, r in enumerate(runs):
+            bc.assert_frame(r, NF, fr, mi, f"run {i}")
+            assert r[0].tobytes() == runs[0][0].tobytes() and r[1].tobytes() == runs[0][1].tobytes(), i
+    finally:
+        b.close()
